@@ -32,6 +32,14 @@ stream during instrumented passes over the same frames from the same initial map
 (tools/profile.sh -> profiles/*_digest.json, matched on steps / warmup / frames per launch / meshing), null otherwise.
 `cpu_baseline` = the oracle (oracle/liboracle.so: the reference algorithm restated, "faithful mode",
 16 threads as the reference hard-codes) on a bounded sample of the same frames.
+
+A plain run does only what `value` / `ms_per_step` need: set-up, the throw-away warm-up pass, the timed passes, the line.  Everything
+else -- `integration_only`, `roofline` (instrumented passes), `pcie_inclusive`, `e2e` and `cpu_baseline` -- is measured with --full
+(each can still be switched off there with its --no-* option).  --dump-outputs DIR writes what the timed path computed after its last
+step (the map's chunks and meshes, see dump_outputs) as DIR/<name>.npy; with the same arguments the frames are the same in every run.
+What a plain run spends outside its steps grows with W + K: every step is a frame of its own, rendered on the host before timing
+starts and resident in HBM (1.2 MB at 640x480).  Measured on an MI355X node with 16 host threads: about 3.5 s + 1.45 ms per frame
+(W + K = 25: 3.5 s, 2020: 7.3 s, 10020: 18 s), i.e. 30 s at about 18 k frames.  (Past frame ~250 the camera has left the sphere room.)
 """
 import argparse
 import datetime
@@ -46,6 +54,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 METRIC = "depth frames/sec integrated + Mvoxel-updates/sec, 640x480 @ 1 cm, 1/2/4/8 GPU"
+REPEAT_BUDGET_S = 10.0  # plain run: a timed pass starts only while the timed regions before it took less than this together
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 
 
@@ -80,7 +89,8 @@ def parse():
     ap.add_argument("--batch", type=int, default=None,
                     help="frames per chisel_hip_integrate_batch call (<= 16 share one launch set); default: the keyframe interval when "
                          "meshing (10 frames = one launch set, the recompute falls exactly on every 10th frame), else 8")
-    ap.add_argument("--repeats", type=int, default=9, help="timed passes (each from an empty map, with its own warm-up); `value` is the median")
+    ap.add_argument("--repeats", type=int, default=9, help="timed passes (each from an empty map, with its own warm-up); `value` is the median.  "
+                                                          "Without --full: fewer when the timed regions take REPEAT_BUDGET_S together before the last one")
     ap.add_argument("--max-chunks", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-frames", type=int, default=30, help="frames of the same stream the CPU oracle is timed on (about 1 s each at 1 cm)")
@@ -104,7 +114,15 @@ def parse():
                          "4 = four interleaved agents; 5 = 1280x720 @ 0.5 cm, garbage collection + full mesh extraction at the end of the timed region")
     ap.add_argument("--launch-timeout", type=float, default=1500.0, help="seconds after which a self-launched N > 1 run is killed")
     ap.add_argument("--no-e2e-leg", action="store_true", help="skip the end-to-end pass (per-frame depth AND colour from page-locked host buffers, `e2e`, 1 GPU only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: integration_only, roofline, pcie_inclusive, e2e and cpu_baseline "
+                         "(a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes: write the map's chunks and meshes as DIR/<name>.npy (float32 / float64, at most 64 MB: a "
+                         "fixed, seeded sample of the chunks and meshes when all of them would not fit); one process (--gpus 1) only")
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs: one process (--gpus 1) only")
     given = {a.split("=")[0] for a in sys.argv[1:] if a.startswith("--")}
     preset = {2: {"res": 0.02, "no_color": True, "mesh_every": 0, "batch": 16},  # (16 frames per call: at 2 cm a launch is as long as its frames' chain, the front half per launch the rest)
               3: {},
@@ -225,6 +243,83 @@ def cpu_baseline(args, frames, color_img, intr, scale):
                       % (n, c["candidates"], "16 std::threads as Chisel.h:150" if not args.no_color else "serial as Chisel.h:71", dt)}
 
 
+def render_frames(args, n_traj, W, H, total):
+    """The first `total` frames of synth.stream (same order, same arrays), one trajectory index per task on up to 16 host threads:
+    numpy releases the GIL in the per-pixel arithmetic, and one 640x480 frame takes about 20 ms on one core."""
+    from concurrent.futures import ThreadPoolExecutor
+    from cvids_amd import synth
+
+    def one(k):
+        return list(synth.stream(args.scene, 1, W, H, agents=args.agents, noise=args.noise, nan_fraction=args.nan_fraction, start=k))
+    with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0))))) as ex:
+        return [f for fs in ex.map(one, range(n_traj)) for f in fs][:total]
+
+
+DUMP_BYTES = 60 << 20  # (file headers on top: under 64 MB either way one counts)
+DUMP_SEED = 1234
+DUMP_IDS = DUMP_BYTES // 8 // 24  # ids per list (three float64 each)
+
+
+def dump_outputs(m, out_dir):
+    """What a caller of the timed path holds after its last step, as out_dir/<name>.npy:
+      chunk_ids (n, 3) float64        every chunk of the map, in lexicographic order (a seeded sample of DUMP_IDS when there are more)
+      chunk_sample_ids (k, 3)         the chunks whose voxels follow: all of them, or a fixed, seeded sample when they do not fit
+      tsdf_sdf, tsdf_weight (k, V)    float32, as Chisel.GetChunk returns them; tsdf_rgbw (k, V, 4) float32 with colour
+      mesh_ids (j, 3) float64         every mesh, in lexicographic order (as chunk_ids)
+      mesh_sample_ids (l, 3)          the meshes whose arrays follow (all, or a fixed, seeded sample)
+      mesh_counts (l, 2) float64      vertices and grid points of each sampled mesh
+      mesh_vertices, mesh_normals, mesh_colors (sum, 3), mesh_grids (sum, 3)   float32, the sampled meshes concatenated
+    At most DUMP_BYTES in all: up to 1/8 for each id list, about 5/8 of the rest for the voxels, what is left for the meshes."""
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    ids = np.asarray(m.GetChunkIDs(), np.int64).reshape(-1, 3)
+    ids = ids[np.lexsort(ids.T[::-1])]
+    mids = np.asarray(m.GetMeshIDs(), np.int64).reshape(-1, 3)
+    mids = mids[np.lexsort(mids.T[::-1])]
+    out = {}
+    for name, a in (("chunk_ids", ids), ("mesh_ids", mids)):
+        if len(a) > DUMP_IDS:
+            a = a[np.sort(rng.permutation(len(a))[:DUMP_IDS])]
+        out[name] = a.astype(np.float64)
+    budget = DUMP_BYTES - sum(a.nbytes for a in out.values()) - 4096
+
+    per_chunk = m.V * (8 + (16 if m.use_color else 0)) + 24
+    k = min(len(ids), max(0, (budget * 5 // 8) // per_chunk))
+    pick = np.sort(rng.permutation(len(ids))[:k])
+    sdf, wgt, rgbw = [], [], []
+    for cid in ids[pick]:
+        s, w, c = m.GetChunk(cid)
+        sdf.append(s)
+        wgt.append(w)
+        if c is not None:
+            rgbw.append(c.astype(np.float32))
+    out["chunk_sample_ids"] = ids[pick].astype(np.float64).reshape(-1, 3)
+    out["tsdf_sdf"] = np.asarray(sdf, np.float32).reshape(-1, m.V)
+    out["tsdf_weight"] = np.asarray(wgt, np.float32).reshape(-1, m.V)
+    if m.use_color:
+        out["tsdf_rgbw"] = np.asarray(rgbw, np.float32).reshape(-1, m.V, 4)
+    budget -= k * per_chunk
+
+    taken = {}
+    for i in rng.permutation(len(mids)):
+        mesh = m.GetMesh(mids[i])
+        nbytes = 40 + sum(a.nbytes for a in mesh.values() if a is not None)
+        if nbytes > budget:
+            break
+        budget -= nbytes
+        taken[int(i)] = mesh
+    rows = sorted(taken)
+    out["mesh_sample_ids"] = mids[rows].astype(np.float64).reshape(-1, 3)
+    out["mesh_counts"] = np.asarray([(len(taken[i]["vertices"]), len(taken[i]["grids"])) for i in rows], np.float64).reshape(-1, 2)
+    for key in ("vertices", "normals", "colors", "grids"):
+        if key == "colors" and not m.use_color:
+            continue
+        out["mesh_" + key] = np.concatenate([np.zeros((0, 3), np.float32)] + [taken[i][key] for i in rows]).astype(np.float32)
+    assert sum(a.nbytes for a in out.values()) <= DUMP_BYTES
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -266,7 +361,7 @@ def main():
     channels = 3 if use_color else 0
     total = args.warmup + args.steps
     n_traj = (total + args.agents - 1) // args.agents
-    frames = list(synth.stream(args.scene, n_traj, W, H, agents=args.agents, noise=args.noise, nan_fraction=args.nan_fraction))[:total]
+    frames = render_frames(args, n_traj, W, H, total)
     color_img = synth.render_color(W, H, 3) if use_color else None
 
     # frames are handed over a batch at a time; with N ranks frame j of a batch is ingested by rank j * N / K and its
@@ -449,7 +544,7 @@ def main():
     fence()
     # ---- passes C (1 GPU, meshing on): the same stream without the mesh recomputes, for reference ----------------
     no_mesh = None
-    if args.mesh_every and world == 1 and not args.no_roofline:
+    if args.full and args.mesh_every and world == 1 and not args.no_roofline:
         every, args.mesh_every = args.mesh_every, 0
         ts = []
         for _ in range(min(repeats, 5)):
@@ -458,14 +553,18 @@ def main():
         args.mesh_every = every
         no_mesh = {"value": args.steps / median(ts), "unit": "frames/s", "ms_per_step": median(ts) / args.steps * 1e3, "repeats": len(ts)}
 
-    # ---- passes A: the timed region ---------------------------------------------------------------------
+    # ---- passes A: the timed region (--repeats passes; in a plain run no new one starts once they have taken REPEAT_BUDGET_S
+    # together, so that a long region costs a bounded time on top of its own.  timed() returns the slowest rank's time: every rank
+    # stops alike)
     ts, issues = [], []
-    for _ in range(repeats):
+    while len(ts) < repeats and (args.full or sum(ts) < REPEAT_BUDGET_S):
         (m.sharded or m).Reset()
         dt_r, t_issue_r, cnt, n_chunks, _ = timed(m)
         ts.append(dt_r)
         issues.append(t_issue_r)
     dt, t_issue = median(ts), median(issues)
+    if args.dump_outputs:
+        dump_outputs(m, args.dump_outputs)
     vals = torch.tensor([cnt["sdf"] + cnt["carved"], cnt["sdf"], cnt["col"], cnt["col_sat"], cnt["probe"], cnt["carved"],
                          cnt["work_chunks"], n_chunks], dtype=torch.float64, device=dev)
     per_rank_sdf = None
@@ -479,7 +578,7 @@ def main():
 
     # ---- passes B: same frames from the same initial state, hipEvents around every kernel ---------------------
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         avgs, others, dts_b = [], [], []
         for _ in range(min(repeats, 5)):
             (m.sharded or m).Reset()
@@ -511,7 +610,7 @@ def main():
     # ---- pass D (1 GPU): the same stream handed over as page-locked HOST depth frames (what a capture pipeline holds): the
     # PCIe-inclusive rate.  Never `value`.
     pcie = None
-    if world == 1 and not args.no_pcie_leg and not args.host_frames and not args.no_roofline:
+    if args.full and world == 1 and not args.no_pcie_leg and not args.host_frames and not args.no_roofline:
         pins = [torch.from_numpy(f[0]).pin_memory() for f in frames]
         saved = calls
         calls_d = []
@@ -534,7 +633,7 @@ def main():
     # memory (a new colour image per frame, as the caller delivers it: ChiselServer.cpp:379-421), are copied to one of two device
     # buffer sets on a copy stream while the previous batch is integrated (events both ways, no host wait), then integrated.
     e2e = None
-    if world == 1 and not args.no_e2e_leg and not args.host_frames and not args.no_roofline:
+    if args.full and world == 1 and not args.no_e2e_leg and not args.host_frames and not args.no_roofline:
         nb = len(bounds)
         kmax = max(hi - lo for lo, hi in bounds)
         h_depth = [torch.from_numpy(np.stack([frames[i][0] for i in range(lo, hi)])).pin_memory() for lo, hi in bounds]
@@ -634,7 +733,7 @@ def main():
             "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
             "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic" + ((" (host depth buffers, %s: PCIe-inclusive)" % ("page-locked" if args.pinned else "pageable")) if args.host_frames else ""),
             "mvoxel_updates_per_s": vals[0] / dt / 1e6, "host_issue_ms_per_step": t_issue / args.steps * 1e3,
-            "repeats": repeats, "value_p10_p90": [args.steps / pct(ts, 0.9), args.steps / pct(ts, 0.1)],
+            "repeats": len(ts), "value_p10_p90": [args.steps / pct(ts, 0.9), args.steps / pct(ts, 0.1)],
             "ms_per_step_min_max": [min(ts) / args.steps * 1e3, max(ts) / args.steps * 1e3],
             "config": {"workload": "%dx%d %s stream (%s, %d agent%s), %g cm voxels, chunk %d^3, InverseTruncator(%g), carving 0.05 m, "
                                    "projective TSDF integration%s" % (W, H, "depth+BGR colour" if use_color else "depth-only",
@@ -682,11 +781,11 @@ def main():
             out["e2e"] = e2e
         if args.config == 5:
             out["config"]["end_of_region"] = "garbage collection of the chunks behind the last camera + mesh extraction of every remaining chunk (inside the timed region)"
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 out["cpu_baseline"] = {"value": None, "unit": "frames/s", "cores": 16, "kind": "port",
                                        "sample": "infeasible as specified: the reference allocates every chunk of the frustum's bounding box per frame, "
                                                  "about 250 k chunks = 33 GB at 1280x720 / 0.5 cm / 5 m (BASELINE.md section 2)"}
-        elif not args.no_cpu_baseline and world == 1:
+        elif args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, frames[args.warmup:], color_img, intr, scale)
         print(json.dumps(out), flush=True)
     if world > 1:

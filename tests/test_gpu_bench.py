@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -82,10 +83,32 @@ def test_group_on_two_devices_equals_one_map():
 
 def test_config5_line_carries_gc_and_full_extraction():
     line = _bench("--gpus", "1", "--config", "5", "--steps", "8", "--warmup", "4", "--width", "320", "--height", "180", "--res", "0.02",
-                  "--trunc-scale", "2.0", "--no-roofline", "--repeats", "1")
+                  "--trunc-scale", "2.0", "--no-roofline", "--repeats", "1", "--full")
     assert line["config"]["baseline_config"] == 5 and "garbage collection" in line["config"]["end_of_region"]
     assert line["cpu_baseline"]["value"] is None and "infeasible" in line["cpu_baseline"]["sample"]
     assert line["value"] > 0
+
+
+def test_plain_run_times_only_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain line carries the timed figures only (what needs passes of its own is measured with --full), and --dump-outputs writes
+    float32 / float64 arrays under 64 MB that are equal between two runs with the same arguments."""
+    common = ["--gpus", "1", "--steps", "20", "--warmup", "5", "--width", "320", "--height", "240", "--res", "0.02", "--repeats", "2"]
+    extra = ("integration_only", "roofline", "pcie_inclusive", "e2e", "cpu_baseline")
+    runs = [_bench(*common, "--dump-outputs", str(tmp_path / d)) for d in ("a", "b")]
+    for line in runs:
+        assert line["steps"] == 20 and line["warmup"] == 5 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert not [k for k in extra if k in line], line.keys()
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"chunk_ids.npy", "tsdf_sdf.npy", "tsdf_weight.npy", "tsdf_rgbw.npy", "mesh_vertices.npy"} <= set(names)
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64e6
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64), (n, x.dtype)
+        assert np.array_equal(x, y, equal_nan=True), n
+    assert len(np.load(tmp_path / "a" / "tsdf_sdf.npy")) > 10 and len(np.load(tmp_path / "a" / "mesh_vertices.npy")) > 1000
+    full = _bench(*common, "--full", "--cpu-frames", "2")
+    assert all(k in full for k in extra), full.keys()
 
 
 def test_a_hung_rank_is_killed_and_reported():

@@ -6,7 +6,7 @@
 # windows:  drv = the driver's command (--steps 20 --warmup 5), 200 = the default line, 4ag = 4 agents / 16 per launch without meshing,
 #           sh8 / 4ag8 = one rank of eight (1 / 4 agents), c5 = 1280x720 @ 0.5 cm
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
-Q="--no-cpu-baseline --no-pcie-leg --no-e2e-leg"
+Q="--full --no-cpu-baseline --no-pcie-leg --no-e2e-leg"
 W_drv="--steps 20 --warmup 5"; W_200="--steps 200 --warmup 20"
 W_4ag="--agents 4 --mesh-every 0 --batch 16 --steps 320 --warmup 64"
 W_sh8="--sim-shards 8 --sim-rank 0 --mesh-every 0 --batch 16 --steps 320 --warmup 64"
@@ -75,7 +75,7 @@ PY
   final)      # last thing of a round: the GPU suite, the smoke test and the two headline lines on the committed build
     python3 -m pytest tests -m gpu -x -q 2>&1 | tail -3
     python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -1
-    python3 bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 | python3 -c "import sys, json; d = json.loads(sys.stdin.read()); print('driver command: %.0f frames/s, frac %.3f, cpu baseline %.2f frames/s' % (d['value'], d['roofline']['frac'], d['cpu_baseline']['value']))"
-    python3 bench.py 2>/dev/null | tail -1 | python3 -c "import sys, json; d = json.loads(sys.stdin.read()); print('default line:   %.0f frames/s, frac %.3f' % (d['value'], d['roofline']['frac']))" ;;
+    python3 bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 | python3 -c "import sys, json; d = json.loads(sys.stdin.read()); print('driver command: %.0f frames/s, frac %.3f, cpu baseline %.2f frames/s' % (d['value'], d['roofline']['frac'], d['cpu_baseline']['value']))"
+    python3 bench.py --full 2>/dev/null | tail -1 | python3 -c "import sys, json; d = json.loads(sys.stdin.read()); print('default line:   %.0f frames/s, frac %.3f' % (d['value'], d['roofline']['frac']))" ;;
   *) echo "unknown entry $name: see the case list in tools/ab.sh"; exit 2 ;;
 esac

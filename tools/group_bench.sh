@@ -7,7 +7,7 @@ for a in "4 agents:--agents 4 --mesh-every 0 --batch 16 --steps 320 --warmup 64"
   for g in 0 2 8; do
     for thr in 1 0; do
       if [ $g = 0 ] && [ $thr = 0 ]; then continue; fi
-      CHISEL_HIP_GROUP_THREADS=$thr python3 bench.py $args --group $g --no-cpu-baseline --no-pcie-leg --no-e2e-leg --repeats 5 2>/dev/null | tail -1 | show "$name, group $g, threads $thr"
+      CHISEL_HIP_GROUP_THREADS=$thr python3 bench.py $args --group $g --full --no-cpu-baseline --no-pcie-leg --no-e2e-leg --repeats 5 2>/dev/null | tail -1 | show "$name, group $g, threads $thr"
     done
   done
 done

@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT
 row() {
   name=$1; shift
-  python3 bench.py --no-cpu-baseline --no-pcie-leg --no-e2e-leg --repeats 5 "$@" 2>/dev/null | tail -1 | python3 -c "
+  python3 bench.py --full --no-cpu-baseline --no-pcie-leg --no-e2e-leg --repeats 5 "$@" 2>/dev/null | tail -1 | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read()); r = d.get('roofline') or {}
 print('%-40s %9.0f frames/s  %7.2f us/frame | integrate %7.1f us/launch (%s frames) frac %.3f | other %s | int-only %s | shapes %s' % ('$name', d['value'], d['ms_per_step'] * 1e3,
@@ -34,7 +34,7 @@ row "1280x720 @ 0.5 cm" --width 1280 --height 720 --res 0.005 --mesh-every 0 --b
 row "640x480 @ 2 cm depth only" --res 0.02 --no-color --mesh-every 0 --batch 8
 row "4 agents" --agents 4 --mesh-every 0 --batch 16 --steps 320 --warmup 64
 scenes
-python3 bench.py --no-cpu-baseline --repeats 3 --no-roofline 2>/dev/null | tail -1 | python3 -c "
+python3 bench.py --full --no-cpu-baseline --repeats 3 --no-roofline 2>/dev/null | tail -1 | python3 -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print('pcie_inclusive', d.get('pcie_inclusive')); print('e2e', d.get('e2e'))"
 echo "== the reference's call pattern: one frame per call, the caller waits after each (tools/sync_latency_abi.cpp)"

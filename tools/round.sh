@@ -19,7 +19,8 @@ for piece in "$@"; do
     shards)
       bash tools/shard_table.sh > /dev/null 2>&1; cp gpurun_out/shard_table.txt gpurun_out/${TAG}_shard_table.txt
       bash tools/shard_table_c5.sh > gpurun_out/${TAG}_shard_table_c5.txt 2>&1 ;;
-    lines)
+    lines)  # the JSON lines with everything bench.py measures: every `python3 bench.py` of this piece runs with --full
+      python3() { if [ "${1:-}" = bench.py ]; then shift; command python3 bench.py --full "$@"; else command python3 "$@"; fi; }
       python3 bench.py > gpurun_out/${TAG}_default_full_line.json 2> gpurun_out/${TAG}_default_full_line.err
       python3 bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/${TAG}_driver_full_line.json 2> gpurun_out/${TAG}_driver_full_line.err
       python3 bench.py --config 5 > gpurun_out/${TAG}_config5_line.json 2> /dev/null
