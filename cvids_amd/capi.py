@@ -57,6 +57,11 @@ class Statistics(C.Structure):
                 ("n_chunks", C.c_int64), ("id_min", C.c_int32 * 3), ("id_max", C.c_int32 * 3)]
 
 
+class StereoParams(C.Structure):
+    """chisel_hip_stereo_params (include/chisel_hip.h): dense_mapping_parameters.cpp:3-11 and DEP_SAMPLE"""
+    _fields_ = [(n, C.c_float) for n in ("pi1", "pi2", "tau_so", "sgm_q1", "sgm_q2", "var_scale", "sparse_ratio", "dep_sample")]
+
+
 EXPORTS = [
     "chisel_hip_abi_version", "chisel_hip_last_error", "chisel_hip_device_count", "chisel_hip_host_alloc", "chisel_hip_host_free", "chisel_hip_create",
     "chisel_hip_destroy", "chisel_hip_reset", "chisel_hip_set_integrator", "chisel_hip_set_stream",
@@ -68,6 +73,8 @@ EXPORTS = [
     "chisel_hip_save_map", "chisel_hip_load_map", "chisel_hip_export_chunks", "chisel_hip_import_ghost_chunks",
     "chisel_hip_drop_ghost_chunks", "chisel_hip_update_meshes_of", "chisel_hip_condition_depth", "chisel_hip_condition_color", "chisel_hip_publish_cloud",
     "chisel_hip_depth_filter_create", "chisel_hip_depth_filter_destroy", "chisel_hip_depth_filter_update", "chisel_hip_depth_filter_read",
+    "chisel_hip_stereo_default_params", "chisel_hip_stereo_create", "chisel_hip_stereo_destroy", "chisel_hip_stereo_set_reference",
+    "chisel_hip_stereo_update", "chisel_hip_stereo_output", "chisel_hip_stereo_clear", "chisel_hip_stereo_read",
     "chisel_hip_get_counters", "chisel_hip_memory_statistics", "chisel_hip_topology_epoch", "chisel_hip_candidates", "chisel_hip_cloud_candidates", "chisel_hip_mesh_cube", "chisel_hip_write_mesh_ply", "chisel_hip_shade_vertices", "chisel_hip_generate_mesh", "chisel_hip_recompute_mesh", "chisel_hip_integrate_chunk", "chisel_hip_dirty_ids_device", "chisel_hip_mesh_shell_plan",
     "chisel_hip_shell_volume", "chisel_hip_export_shells", "chisel_hip_import_ghost_shells", "chisel_hip_set_profiling", "chisel_hip_get_profile", "chisel_hip_get_launch_stats", "chisel_hip_pool_info", "chisel_hip_mc_tables", "chisel_hip_mesh_cube_values", "chisel_hip_interpolate_vertex", "chisel_hip_raycast", "chisel_hip_chunk_owner", "chisel_hip_frustum", "chisel_hip_frustum_from_vectors", "chisel_hip_create_group",
 ]
@@ -161,6 +168,15 @@ def load_library():
     L.chisel_hip_depth_filter_destroy.argtypes = [vp]
     L.chisel_hip_depth_filter_update.argtypes = [vp, vp, vp, C.c_double, C.c_int, C.c_int]
     L.chisel_hip_depth_filter_read.argtypes = [vp, C.c_int, vp, C.c_int]
+    L.chisel_hip_stereo_default_params.argtypes = [C.POINTER(StereoParams)]
+    L.chisel_hip_stereo_default_params.restype = None
+    L.chisel_hip_stereo_create.argtypes = [C.c_int, C.c_int, C.POINTER(StereoParams), C.c_int, C.POINTER(vp)]
+    L.chisel_hip_stereo_destroy.argtypes = [vp]
+    L.chisel_hip_stereo_set_reference.argtypes = [vp, vp, vp, C.c_int]
+    L.chisel_hip_stereo_update.argtypes = [vp, vp, f32p, f32p, C.c_int]
+    L.chisel_hip_stereo_output.argtypes = [vp, vp, vp, C.c_int]
+    L.chisel_hip_stereo_clear.argtypes = [vp]
+    L.chisel_hip_stereo_read.argtypes = [vp, C.c_int, vp, C.c_int]
     L.chisel_hip_save_map.argtypes = [vp, C.c_char_p]
     L.chisel_hip_load_map.argtypes = [vp, C.c_char_p]
     L.chisel_hip_get_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]

@@ -670,6 +670,108 @@ class DepthFilter:
         return self.read(self.RATIO)
 
 
+def stereo_homography(K1, K2, ref_rotation, ref_translation, match_rotation, match_translation):
+    """StereoMapper::Update's plane-sweep transform (sgm_stereo_mapper.cpp:179-182): R = K2 R_m^T R_r K1^-1 and
+    t = K2 R_m^T (t_r - t_m) in double, narrowed to float32 as ad_calc_cost's float arguments take them (:184-189).  Poses are
+    camera-to-world (R_wc, t_wc).  K1^-1 is numpy's inverse where the reference uses cv::Mat::inv (LU): the last bit may differ."""
+    K1, K2 = np.asarray(K1, np.float64), np.asarray(K2, np.float64)
+    Rr, Rm = np.asarray(ref_rotation, np.float64), np.asarray(match_rotation, np.float64)
+    tr, tm = np.asarray(ref_translation, np.float64).reshape(3), np.asarray(match_translation, np.float64).reshape(3)
+    R = K2 @ Rm.T @ Rr @ np.linalg.inv(K1)
+    t = K2 @ Rm.T @ (tr - tm)
+    return R.astype(np.float32), t.astype(np.float32)
+
+
+def stereo_default_params():
+    """-> capi.StereoParams with the reference's constants (chisel_hip_stereo_default_params)"""
+    p = capi.StereoParams()
+    capi.load_library().chisel_hip_stereo_default_params(C.byref(p))
+    return p
+
+
+def _float32_image(img, shape, what):
+    """-> (address, on_device, keepalive) of a float32 (h, w) map: numpy arrays of any float type are converted, torch CUDA
+    tensors are used in place and must therefore BE float32 (a float64 or half tensor would be read as float32)"""
+    assert tuple(img.shape) == shape, "%s: shape %s, the mapper's is %s" % (what, tuple(img.shape), shape)
+    if not isinstance(img, np.ndarray) and getattr(img, "is_cuda", False):
+        import torch
+        assert img.dtype == torch.float32, "%s: a CUDA tensor must be float32, not %s" % (what, img.dtype)
+    return _image_pointer(img, np.float32)
+
+
+class StereoMapper:
+    """StereoMapper of the dense-mapping thread (server_pose_graph/src/dense_mapping/sgm_stereo_mapper.cpp) with its cost and SGM
+    volumes in HBM (chisel_hip_stereo_*).  Images are the caller's already resized and undistorted float32 (height, width) maps,
+    numpy arrays or torch CUDA tensors; the OpenCV steps around the device work stay with the caller."""
+    COST, SGM, DEPTH, DEPTH64 = range(4)
+    DEP_CNT = 128
+
+    def __init__(self, width, height, params=None, device_id=-1):
+        self.L = capi.load_library()
+        self.shape = (int(height), int(width))
+        self.h = C.c_void_p()
+        check(self.L.chisel_hip_stereo_create(int(width), int(height), C.byref(params) if params is not None else None, int(device_id),
+                                              C.byref(self.h)))
+        self._keep = None
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            self.L.chisel_hip_stereo_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def InitReference(self, ref_image, p2_weight):
+        """InitReference (:55-123): the undistorted reference image and its P2 weight map; the measurement count restarts"""
+        a, dev, k1 = _float32_image(ref_image, self.shape, "ref_image")
+        b, dev2, k2 = _float32_image(p2_weight, self.shape, "p2_weight")
+        assert dev == dev2, "ref_image and p2_weight must both be on the host or both on the device"
+        check(self.L.chisel_hip_stereo_set_reference(self.h, a, b, dev))
+        self._keep = [k1, k2]
+
+    def Update(self, match_image, R, t):
+        """Update (:125-199): R, t as stereo_homography returns them"""
+        a, dev, k1 = _float32_image(match_image, self.shape, "match_image")
+        Rf = (C.c_float * 9)(*np.asarray(R, np.float32).reshape(9).tolist())
+        tf = (C.c_float * 3)(*np.asarray(t, np.float32).reshape(3).tolist())
+        check(self.L.chisel_hip_stereo_update(self.h, a, Rf, tf, dev))
+        self._keep = [k1]
+
+    def Output(self, sparse_depth=None, sparse_dist=None, out=None):
+        """Output (:219-385) up to the device depth map: FuseSparseInfo (when given the sparse maps), SGM, filterCost.  Returns
+        the float32 depth map (numpy), or fills `out` (a torch CUDA tensor, float32 or float64) in place"""
+        if sparse_depth is None:
+            check(self.L.chisel_hip_stereo_output(self.h, None, None, 0))
+        else:
+            a, dev, k1 = _float32_image(sparse_depth, self.shape, "sparse_depth")
+            b, dev2, k2 = _float32_image(sparse_dist, self.shape, "sparse_dist")
+            assert dev == dev2, "sparse_depth and sparse_dist must both be on the host or both on the device"
+            check(self.L.chisel_hip_stereo_output(self.h, a, b, dev))
+            self._keep = [k1, k2]
+        if out is not None:
+            return self.read(self.DEPTH64 if str(out.dtype).endswith("float64") else self.DEPTH, out=out)
+        return self.read(self.DEPTH)
+
+    def ClearRawCost(self):
+        """ClearRawCost (:202-216): cost, SGM and depth zeroed, the measurement count kept"""
+        check(self.L.chisel_hip_stereo_clear(self.h))
+
+    def read(self, which, out=None):
+        """which = COST / SGM (float32 (h, w, 128)), DEPTH (float32 (h, w)), DEPTH64 (float64 (h, w)); `out`: a torch CUDA tensor
+        to fill in place (stays in HBM), default a new numpy array"""
+        if out is not None:
+            check(self.L.chisel_hip_stereo_read(self.h, int(which), out.data_ptr(), 1))
+            return out
+        shape = self.shape + (self.DEP_CNT,) if which in (self.COST, self.SGM) else self.shape
+        a = np.empty(shape, np.float64 if which == self.DEPTH64 else np.float32)
+        check(self.L.chisel_hip_stereo_read(self.h, int(which), a.ctypes.data, 0))
+        return a
+
+
 def condition_depth(depth64, width=640, height=480, intrinsics=None):
     """CollaborativeServer::PublishDenseInfo's depth conditioning (chisel_hip_condition_depth): float64 depth map of any size
     -> (float32 depth of the publish size with NaN outside [0.1, 20] m, rescaled (fx, fy, cx, cy) or None)"""

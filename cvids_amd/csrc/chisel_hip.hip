@@ -36,6 +36,7 @@
 #include "kernels_mesh.h"
 #include "kernels_cloud.h"
 #include "kernels_filter.h"
+#include "kernels_stereo.h"
 
 using namespace chisel_hip;
 
@@ -2099,6 +2100,185 @@ int chisel_hip_depth_filter_read(chisel_hip_depth_filter *f, int which, double *
     hipLaunchKernelGGL(filter_read_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, f->view, which, d_out);
     HIP_TRY(hipGetLastError());
     if (!dst_on_device) HIP_TRY(hipMemcpyAsync(dst, d_out, n * sizeof(double), hipMemcpyDeviceToHost, 0));
+    HIP_TRY(hipStreamSynchronize(0));
+    return CHISEL_HIP_OK;
+}
+
+// ---- StereoMapper (sgm_stereo_mapper.cpp, calc_cost.cu) ---------------------------------------------------------------------
+struct chisel_hip_stereo {
+    int device = 0;
+    int width = 0, height = 0;
+    int measurement_cnt = 0;  // m_nMeasurementCount: reset by InitReference only (sgm_stereo_mapper.cpp:121)
+    bool has_reference = false;
+    StereoParams prm{};
+    StereoView view{};
+    float *ref = nullptr, *match = nullptr, *p2w = nullptr;
+    float *stage_a = nullptr, *stage_b = nullptr;  // host sparse maps pass through these
+    double *stage_out = nullptr;                   // read-out 3 to the host
+};
+
+void chisel_hip_stereo_default_params(chisel_hip_stereo_params *p) {
+    if (!p) return;
+    // dense_mapping_parameters.cpp:3-11; DEP_SAMPLE = 1.0f / (BASE_LINE * FOCAL), dense_mapping_parameters.h:24,36-37
+    const float focal = (float)((461.6 + 460.3) / 2);
+    const float base_line = 0.11f;
+    *p = {16.0f, 64.0f, 8.0f, 1.0f, 1.0f, 1.0f, 15.0f, 1.0f / (base_line * focal)};
+}
+
+int chisel_hip_stereo_create(int width, int height, const chisel_hip_stereo_params *p, int device_id, chisel_hip_stereo **out) {
+    if (!out || width < 2 || height < 2 || width > 16384 || height > 16384 || (int64_t)width * height > (1 << 24))
+        return fail(CHISEL_HIP_ERR_INVALID, "bad stereo size");
+    chisel_hip_stereo_params prm;
+    if (p) prm = *p;
+    else chisel_hip_stereo_default_params(&prm);
+    if (!(prm.dep_sample > 0.0f) || !(prm.sgm_q1 != 0.0f) || !(prm.sgm_q2 != 0.0f)) return fail(CHISEL_HIP_ERR_INVALID, "bad stereo parameters");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(CHISEL_HIP_ERR_HIP, "no HIP device (there is no CPU path)");
+    if (device_id < 0) HIP_TRY(hipGetDevice(&device_id));
+    if (device_id >= n_dev) return fail(CHISEL_HIP_ERR_INVALID, "bad device id");
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device_id));
+    if (!strstr(prop.gcnArchName, "gfx950"))
+        return fail(CHISEL_HIP_ERR_HIP, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 (MI355X) only");
+    HIP_TRY(hipSetDevice(device_id));
+    chisel_hip_stereo *s = new chisel_hip_stereo();
+    s->device = device_id; s->width = width; s->height = height;
+    s->prm = {prm.pi1, prm.pi2, prm.tau_so, prm.sgm_q1, prm.sgm_q2, prm.var_scale, prm.sparse_ratio, prm.dep_sample};
+    const size_t n = (size_t)width * height, nv = n * STEREO_DEP_CNT;
+    bool ok = hipMalloc(&s->ref, n * sizeof(float)) == hipSuccess && hipMalloc(&s->match, n * sizeof(float)) == hipSuccess &&
+              hipMalloc(&s->p2w, n * sizeof(float)) == hipSuccess && hipMalloc(&s->stage_a, n * sizeof(float)) == hipSuccess &&
+              hipMalloc(&s->stage_b, n * sizeof(float)) == hipSuccess && hipMalloc(&s->stage_out, n * sizeof(double)) == hipSuccess &&
+              hipMalloc(&s->view.cost, nv * sizeof(float)) == hipSuccess && hipMalloc(&s->view.sgm, nv * sizeof(float)) == hipSuccess &&
+              hipMalloc(&s->view.depth, n * sizeof(float)) == hipSuccess;
+    if (!ok) {
+        chisel_hip_stereo_destroy(s);
+        return fail(CHISEL_HIP_ERR_HIP, "hipMalloc failed");
+    }
+    s->view.w = width; s->view.h = height;
+    s->view.ref = s->ref; s->view.match = s->match; s->view.p2w = s->p2w;
+    // every image and volume starts zeroed, as after ClearRawCost
+    hipError_t e = hipSuccess;
+    const std::pair<void *, size_t> zeroed[] = {{s->ref, n * sizeof(float)},       {s->match, n * sizeof(float)},
+                                                {s->p2w, n * sizeof(float)},       {s->view.cost, nv * sizeof(float)},
+                                                {s->view.sgm, nv * sizeof(float)}, {s->view.depth, n * sizeof(float)}};
+    for (const auto &z : zeroed)
+        if (e == hipSuccess) e = hipMemsetAsync(z.first, 0, z.second, 0);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        chisel_hip_stereo_destroy(s);
+        return fail(CHISEL_HIP_ERR_HIP, std::string("zeroing the stereo state: ") + hipGetErrorString(e));
+    }
+    *out = s;
+    return CHISEL_HIP_OK;
+}
+
+int chisel_hip_stereo_destroy(chisel_hip_stereo *s) {
+    if (!s) return CHISEL_HIP_OK;
+    (void)hipSetDevice(s->device);
+    (void)hipDeviceSynchronize();
+    void *ptrs[] = {s->ref, s->match, s->p2w, s->stage_a, s->stage_b, s->stage_out, s->view.cost, s->view.sgm, s->view.depth};
+    for (void *p : ptrs)
+        if (p) (void)hipFree(p);
+    delete s;
+    return CHISEL_HIP_OK;
+}
+
+static int stereo_upload(float *dst, const float *src, size_t n, int on_device) {
+    HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, 0));
+    return CHISEL_HIP_OK;
+}
+
+int chisel_hip_stereo_set_reference(chisel_hip_stereo *s, const float *ref, const float *p2_weight, int on_device) {
+    if (!s || !ref || !p2_weight) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = (size_t)s->width * s->height;
+    int rc = stereo_upload(s->ref, ref, n, on_device);
+    if (rc == CHISEL_HIP_OK) rc = stereo_upload(s->p2w, p2_weight, n, on_device);
+    if (rc != CHISEL_HIP_OK) return rc;
+    if (!on_device) HIP_TRY(hipStreamSynchronize(0));
+    s->measurement_cnt = 0;
+    s->has_reference = true;
+    return CHISEL_HIP_OK;
+}
+
+int chisel_hip_stereo_update(chisel_hip_stereo *s, const float *match, const float R[9], const float t[3], int on_device) {
+    if (!s || !match || !R || !t) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
+    if (!s->has_reference) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_stereo_update before chisel_hip_stereo_set_reference");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = (size_t)s->width * s->height;
+    const int rc = stereo_upload(s->match, match, n, on_device);
+    if (rc != CHISEL_HIP_OK) return rc;
+    StereoPose P;
+    memcpy(P.r, R, sizeof(P.r));
+    memcpy(P.t, t, sizeof(P.t));
+    s->measurement_cnt++;
+    hipLaunchKernelGGL(stereo_cost_kernel, dim3((unsigned)((n + 1) / 2)), dim3(256), 0, 0, s->view, P, s->measurement_cnt, s->prm.dep_sample);
+    HIP_TRY(hipGetLastError());
+    if (!on_device) HIP_TRY(hipStreamSynchronize(0));  // the host image may go once this returns
+    return CHISEL_HIP_OK;  // stream 0: ordered against the next call; reads wait
+}
+
+int chisel_hip_stereo_output(chisel_hip_stereo *s, const float *sparse_depth, const float *sparse_dist, int on_device) {
+    if (!s || (!sparse_depth) != (!sparse_dist)) return fail(CHISEL_HIP_ERR_INVALID, "bad argument (sparse depth and distance go together)");
+    HIP_TRY(hipSetDevice(s->device));
+    const int W = s->width, H = s->height;
+    const size_t n = (size_t)W * H, nv = n * STEREO_DEP_CNT;
+    if (sparse_depth) {  // FuseSparseInfo (sgm_stereo_mapper.cpp:366-368); without a prior every nDepth is -1 and it changes nothing
+        const float *dd = sparse_depth, *ds = sparse_dist;
+        if (!on_device) {
+            HIP_TRY(hipMemcpyAsync(s->stage_a, sparse_depth, n * sizeof(float), hipMemcpyHostToDevice, 0));
+            HIP_TRY(hipMemcpyAsync(s->stage_b, sparse_dist, n * sizeof(float), hipMemcpyHostToDevice, 0));
+            dd = s->stage_a;
+            ds = s->stage_b;
+        }
+        hipLaunchKernelGGL(stereo_fuse_sparse_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, 0, s->view, dd, ds,
+                           s->prm.sparse_ratio, s->prm.dep_sample);
+        HIP_TRY(hipGetLastError());
+    }
+    // sgm2 (calc_cost.cu:507-546): right, left, down, up, in that order, each adding its path costs to the volume; the first
+    // writes, which equals adding to the zeroed volume of sgm_stereo_mapper.cpp:371
+    const SgmScan passes[4] = {
+        {H, W, W, 1, 0},
+        {H, W, W, -1, W - 1},
+        {W, H, 1, W, 0},
+        {W, H, 1, -W, (H - 1) * W},
+    };
+    for (int k = 0; k < 4; ++k) {
+        const dim3 grid((unsigned)((passes[k].n_lines + 3) / 4));
+        if (k == 0) hipLaunchKernelGGL(stereo_sgm_kernel<true>, grid, dim3(256), 0, 0, s->view, passes[k], s->prm);
+        else hipLaunchKernelGGL(stereo_sgm_kernel<false>, grid, dim3(256), 0, 0, s->view, passes[k], s->prm);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(stereo_wta_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, 0, s->view, s->prm.var_scale, s->prm.dep_sample);
+    HIP_TRY(hipGetLastError());
+    if (sparse_depth && !on_device) HIP_TRY(hipStreamSynchronize(0));
+    return CHISEL_HIP_OK;
+}
+
+int chisel_hip_stereo_clear(chisel_hip_stereo *s) {
+    if (!s) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = (size_t)s->width * s->height, nv = n * STEREO_DEP_CNT;
+    HIP_TRY(hipMemsetAsync(s->view.cost, 0, nv * sizeof(float), 0));
+    HIP_TRY(hipMemsetAsync(s->view.sgm, 0, nv * sizeof(float), 0));
+    HIP_TRY(hipMemsetAsync(s->view.depth, 0, n * sizeof(float), 0));
+    return CHISEL_HIP_OK;  // the measurement count stays (sgm_stereo_mapper.cpp:202-216)
+}
+
+int chisel_hip_stereo_read(chisel_hip_stereo *s, int which, void *dst, int dst_on_device) {
+    if (!s || !dst || which < 0 || which > 3) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = (size_t)s->width * s->height;
+    const hipMemcpyKind kind = dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (which == 0) HIP_TRY(hipMemcpyAsync(dst, s->view.cost, n * STEREO_DEP_CNT * sizeof(float), kind, 0));
+    else if (which == 1) HIP_TRY(hipMemcpyAsync(dst, s->view.sgm, n * STEREO_DEP_CNT * sizeof(float), kind, 0));
+    else if (which == 2) HIP_TRY(hipMemcpyAsync(dst, s->view.depth, n * sizeof(float), kind, 0));
+    else {
+        double *d_out = dst_on_device ? static_cast<double *>(dst) : s->stage_out;
+        hipLaunchKernelGGL(stereo_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, s->view.depth, d_out, (int)n);
+        HIP_TRY(hipGetLastError());
+        if (!dst_on_device) HIP_TRY(hipMemcpyAsync(dst, d_out, n * sizeof(double), hipMemcpyDeviceToHost, 0));
+    }
     HIP_TRY(hipStreamSynchronize(0));
     return CHISEL_HIP_OK;
 }

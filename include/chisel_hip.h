@@ -43,7 +43,7 @@ extern "C" {
  *   2  round 5-6: chisel_hip_mesh_shell_plan_all removed, CHISEL_HIP_NUM_LAUNCH_STATS 8 -> 10, the device-plan and incremental
  *      meshesToUpdate entries added; later additions within 2 (nothing removed or re-typed): chisel_hip_pool_info,
  *      chisel_hip_frustum_from_vectors, chisel_hip_order_stream_after_map / _map_after_stream, the wait-free sharded recompute
- *      (chisel_hip_shell_plan_queue, _import_shells_fixed, _shell_commit) */
+ *      (chisel_hip_shell_plan_queue, _import_shells_fixed, _shell_commit), the stereo matcher (chisel_hip_stereo_*) */
 #define CHISEL_HIP_ABI_VERSION 2
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -311,6 +311,42 @@ int chisel_hip_depth_filter_destroy(chisel_hip_depth_filter *filter);
 int chisel_hip_depth_filter_update(chisel_hip_depth_filter *filter, const double *mu, const double *cov, double cov_all, int reciprocal,
                                    int on_device);
 int chisel_hip_depth_filter_read(chisel_hip_depth_filter *filter, int which, double *dst, int dst_on_device);
+
+/* ---- the step before that: the stereo matcher (StereoMapper, the reference's only GPU code) --------------------------------
+ * StereoMapper (server_pose_graph/src/dense_mapping/sgm_stereo_mapper.cpp, kernels calc_cost.cu): plane-sweep absolute-difference
+ * cost over STEREO_DEP_CNT = 128 inverse depths i * dep_sample, four-path SGM, winner-takes-all with parabola sub-sample.  The cost
+ * and SGM volumes ([height][width][128] floats, depth fastest: 314 MB at 640 x 480) and the depth map live in HBM.  What stays
+ * with the caller, on the host as in the reference: cv::resize + cv::undistort of both images, the P2 weight map
+ * 0.8 + 1.5 m^3 / (1 + |Sobel(5,5,9)|^3) (sgm_stereo_mapper.cpp:72-83), the sparse prior maps of Output's window loop (:229-357),
+ * the final cv::resize (:409).  Same numbers as the reference bit for bit, except match-image samples: bilinear with exact fp32
+ * weights where the CUDA texture quantises them.  Images: width * height floats, on the host or (flag) in HBM.
+ *   default_params  dense_mapping_parameters.cpp:3-11 (pi1 16, pi2 64, tau_so 8, sgm_q1 1, sgm_q2 1, var_scale 1, nSparseRatio 15)
+ *                   and DEP_SAMPLE = 1.0f / (0.11f * 460.95f) (dense_mapping_parameters.h:24,36-37)
+ *   create          StereoMapper::StereoMapper (sgm_stereo_mapper.cpp:11-18); width, height >= 2 at run time (the reference
+ *                   fixes 640 x 480); p == NULL: the defaults
+ *   set_reference   InitReference (:55-123): the undistorted reference image and its P2 weight map; measurement count = 0
+ *   update          Update (:125-199) -> ad_calc_cost (calc_cost.cu:20-233): count + 1, then the running mean of the AD cost.
+ *                   R = K2 R_m^T R_r K1^-1, t = K2 R_m^T (t_r - t_m) as floats, row-major (:179-182)
+ *   output          Output (:219-385): FuseSparseInfo (calc_cost.cu:684-736) with the sparse depth and distance maps
+ *                   (both NULL: no prior; the reference's all -1 map changes nothing), the SGM volume zeroed, sgm2 right,
+ *                   left, down, up (:365-546), filterCostKernel (:235-282) -> depth map (1000 where no minimum is accepted)
+ *   clear           ClearRawCost (:202-216): cost, SGM and depth zeroed; the measurement count is NOT reset (the reference's)
+ *   read            which = 0 cost volume f32, 1 SGM volume f32, 2 depth map f32, 3 depth map widened to f64
+ *                   (depth_estimator.cpp:283): the input of chisel_hip_depth_filter_update(..., reciprocal = 1, on_device = 1)
+ * Every call runs on the null stream: update / output return before the kernels finish and the next call (also a depth-filter
+ * call) is ordered after them; read waits. */
+typedef struct {
+    float pi1, pi2, tau_so, sgm_q1, sgm_q2, var_scale, sparse_ratio, dep_sample;
+} chisel_hip_stereo_params;
+typedef struct chisel_hip_stereo chisel_hip_stereo;
+void chisel_hip_stereo_default_params(chisel_hip_stereo_params *p);
+int chisel_hip_stereo_create(int width, int height, const chisel_hip_stereo_params *p, int device_id, chisel_hip_stereo **out);
+int chisel_hip_stereo_destroy(chisel_hip_stereo *s);
+int chisel_hip_stereo_set_reference(chisel_hip_stereo *s, const float *ref, const float *p2_weight, int on_device);
+int chisel_hip_stereo_update(chisel_hip_stereo *s, const float *match, const float R[9], const float t[3], int on_device);
+int chisel_hip_stereo_output(chisel_hip_stereo *s, const float *sparse_depth, const float *sparse_dist, int on_device);
+int chisel_hip_stereo_clear(chisel_hip_stereo *s);
+int chisel_hip_stereo_read(chisel_hip_stereo *s, int which, void *dst, int dst_on_device);
 
 /* Binary dump / restore of the whole map (the correct counterpart of chisel_ros FillChunkMessage,
  * Serialization.h:31-84, whose bit packing loses data; also checkpoint / resume).  File: 32-byte header
