@@ -75,6 +75,8 @@ EXPORTS = [
     "chisel_hip_depth_filter_create", "chisel_hip_depth_filter_destroy", "chisel_hip_depth_filter_update", "chisel_hip_depth_filter_read",
     "chisel_hip_stereo_default_params", "chisel_hip_stereo_create", "chisel_hip_stereo_destroy", "chisel_hip_stereo_set_reference",
     "chisel_hip_stereo_update", "chisel_hip_stereo_output", "chisel_hip_stereo_clear", "chisel_hip_stereo_read",
+    "chisel_hip_stereo_set_camera", "chisel_hip_stereo_set_reference_image", "chisel_hip_stereo_update_image",
+    "chisel_hip_stereo_bind_sparse_points", "chisel_hip_stereo_output_image", "chisel_hip_stereo_homography",
     "chisel_hip_get_counters", "chisel_hip_memory_statistics", "chisel_hip_topology_epoch", "chisel_hip_candidates", "chisel_hip_cloud_candidates", "chisel_hip_mesh_cube", "chisel_hip_write_mesh_ply", "chisel_hip_shade_vertices", "chisel_hip_generate_mesh", "chisel_hip_recompute_mesh", "chisel_hip_integrate_chunk", "chisel_hip_dirty_ids_device", "chisel_hip_mesh_shell_plan",
     "chisel_hip_shell_volume", "chisel_hip_export_shells", "chisel_hip_import_ghost_shells", "chisel_hip_set_profiling", "chisel_hip_get_profile", "chisel_hip_get_launch_stats", "chisel_hip_pool_info", "chisel_hip_mc_tables", "chisel_hip_mesh_cube_values", "chisel_hip_interpolate_vertex", "chisel_hip_raycast", "chisel_hip_chunk_owner", "chisel_hip_frustum", "chisel_hip_frustum_from_vectors", "chisel_hip_create_group",
 ]
@@ -82,7 +84,7 @@ EXPORTS = [
 SELFTEST_EXPORTS = [
     "chisel_hip_kat_truncation", "chisel_hip_kat_dist", "chisel_hip_kat_color", "chisel_hip_kat_color_fresh", "chisel_hip_kat_color_any",
     "chisel_hip_kat_reciprocal", "chisel_hip_kat_floor", "chisel_hip_kat_raycast", "chisel_hip_debug_cloud_stats",
-    "chisel_hip_debug_cull_space", "chisel_hip_debug_frustum_range",
+    "chisel_hip_debug_cull_space", "chisel_hip_debug_frustum_range", "chisel_hip_debug_stereo_prep",
 ]
 
 
@@ -177,6 +179,14 @@ def load_library():
     L.chisel_hip_stereo_output.argtypes = [vp, vp, vp, C.c_int]
     L.chisel_hip_stereo_clear.argtypes = [vp]
     L.chisel_hip_stereo_read.argtypes = [vp, C.c_int, vp, C.c_int]
+    f64p = C.POINTER(C.c_double)
+    L.chisel_hip_stereo_set_camera.argtypes = [vp, C.c_int, C.c_int, f64p, f64p, f64p, f64p]
+    L.chisel_hip_stereo_set_reference_image.argtypes = [vp, vp, C.c_int, C.c_int]
+    L.chisel_hip_stereo_update_image.argtypes = [vp, vp, C.c_int, f64p, f64p, f64p, f64p, C.c_int]
+    L.chisel_hip_stereo_bind_sparse_points.argtypes = [vp, vp, vp, C.c_int]
+    L.chisel_hip_stereo_output_image.argtypes = [vp]
+    L.chisel_hip_stereo_homography.argtypes = [f64p, f64p, f64p, f64p, f64p, f64p, f32p, f32p]
+    L.chisel_hip_debug_stereo_prep.argtypes = [vp, C.c_int, vp]
     L.chisel_hip_save_map.argtypes = [vp, C.c_char_p]
     L.chisel_hip_load_map.argtypes = [vp, C.c_char_p]
     L.chisel_hip_get_counters.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int]

@@ -699,11 +699,38 @@ def _float32_image(img, shape, what):
     return _image_pointer(img, np.float32)
 
 
+def _uint8_image(img, shape, what):
+    """-> (address, on_device, keepalive) of a uint8 (h, w) image, a numpy array or a torch tensor (CUDA: used in place)"""
+    assert tuple(img.shape) == shape, "%s: shape %s, expected %s" % (what, tuple(img.shape), shape)
+    if isinstance(img, np.ndarray):
+        assert img.dtype == np.uint8, "%s: a mono8 image must be uint8, not %s" % (what, img.dtype)
+    else:
+        import torch
+        assert img.dtype == torch.uint8, "%s: a mono8 image must be uint8, not %s" % (what, img.dtype)
+    return _image_pointer(img, np.uint8)
+
+
+def _doubles(a, n, what):
+    a = np.asarray(a, np.float64).reshape(-1)
+    assert a.size == n, "%s: %d values, expected %d" % (what, a.size, n)
+    return (C.c_double * n)(*a.tolist())
+
+
+def _intrinsics4(K):
+    """(fx, fy, cx, cy) from a 3 x 3 camera matrix or a 4-vector"""
+    K = np.asarray(K, np.float64)
+    return (K[0, 0], K[1, 1], K[0, 2], K[1, 2]) if K.shape == (3, 3) else tuple(K.reshape(4))
+
+
 class StereoMapper:
     """StereoMapper of the dense-mapping thread (server_pose_graph/src/dense_mapping/sgm_stereo_mapper.cpp) with its cost and SGM
-    volumes in HBM (chisel_hip_stereo_*).  Images are the caller's already resized and undistorted float32 (height, width) maps,
-    numpy arrays or torch CUDA tensors; the OpenCV steps around the device work stay with the caller."""
-    COST, SGM, DEPTH, DEPTH64 = range(4)
+    volumes in HBM (chisel_hip_stereo_*).  Two ways in: InitReference / Update / Output take the caller's already resized and
+    undistorted float32 (height, width) maps; InitIntrinsic then InitReferenceImage / UpdateImage / BindSparsePoints / OutputImage
+    take the camera's mono8 frames and do the resize, undistort, P2 map, gradient masks, sparse prior and final resize on the
+    device.  Images are numpy arrays or torch CUDA tensors."""
+    COST, SGM, DEPTH, DEPTH64, DEPTH_REAL, DEPTH_REAL64 = range(6)
+    # chisel_hip_debug_stereo_prep read-outs
+    PREP_REF, PREP_MATCH, PREP_P2W, PREP_MASK_X, PREP_MASK_Y, PREP_SPARSE_DEPTH, PREP_SPARSE_DIST = range(7)
     DEP_CNT = 128
 
     def __init__(self, width, height, params=None, device_id=-1):
@@ -761,15 +788,123 @@ class StereoMapper:
         check(self.L.chisel_hip_stereo_clear(self.h))
 
     def read(self, which, out=None):
-        """which = COST / SGM (float32 (h, w, 128)), DEPTH (float32 (h, w)), DEPTH64 (float64 (h, w)); `out`: a torch CUDA tensor
-        to fill in place (stays in HBM), default a new numpy array"""
+        """which = COST / SGM (float32 (h, w, 128)), DEPTH (float32 (h, w)), DEPTH64 (float64 (h, w)), DEPTH_REAL / DEPTH_REAL64
+        (the camera-size depth of the last OutputImage, float32 / float64); `out`: a torch CUDA tensor to fill in place (stays in
+        HBM), default a new numpy array"""
         if out is not None:
             check(self.L.chisel_hip_stereo_read(self.h, int(which), out.data_ptr(), 1))
             return out
         shape = self.shape + (self.DEP_CNT,) if which in (self.COST, self.SGM) else self.shape
-        a = np.empty(shape, np.float64 if which == self.DEPTH64 else np.float32)
+        if which in (self.DEPTH_REAL, self.DEPTH_REAL64):
+            assert getattr(self, "real_shape", None) is not None, "InitIntrinsic first"
+            shape = self.real_shape
+        a = np.empty(shape, np.float64 if which in (self.DEPTH64, self.DEPTH_REAL64) else np.float32)
         check(self.L.chisel_hip_stereo_read(self.h, int(which), a.ctypes.data, 0))
         return a
+
+    # ---- the raw-image path ----
+    def InitIntrinsic(self, K1, D1, K2, D2, real_size):
+        """InitIntrinsic (:20-52): K as a 3 x 3 matrix or (fx, fy, cx, cy) of the camera image, D = (k1, k2, p1, p2[, k3]);
+        real_size = (width, height) of the camera images the raw entries take"""
+        real_w, real_h = (int(v) for v in real_size)
+        pad = lambda D: list(np.asarray(D, np.float64).reshape(-1)) + [0.0] * (5 - np.asarray(D).size)
+        check(self.L.chisel_hip_stereo_set_camera(self.h, real_w, real_h, _doubles(_intrinsics4(K1), 4, "K1"), _doubles(pad(D1), 5, "D1"),
+                                                  _doubles(_intrinsics4(K2), 4, "K2"), _doubles(pad(D2), 5, "D2")))
+        self.real_shape = (real_h, real_w)
+
+    def _raw(self, img, what):
+        assert getattr(self, "real_shape", None) is not None, "%s before InitIntrinsic" % what
+        return _uint8_image(img, self.real_shape, what)
+
+    def InitReferenceImage(self, image):
+        """InitReference (:55-123) on the camera's mono8 image (uint8 (real_h, real_w)): resize, undistort, P2 map, gradient
+        masks on the device; the measurement count restarts"""
+        a, dev, k = self._raw(image, "InitReferenceImage")
+        check(self.L.chisel_hip_stereo_set_reference_image(self.h, a, self.real_shape[1], dev))
+        self._keep = [k]
+
+    def UpdateImage(self, image, ref_pose, match_pose):
+        """Update (:125-199) on a mono8 match image; poses are camera-to-world (R_wc, t_wc)"""
+        a, dev, k = self._raw(image, "UpdateImage")
+        Rr, tr = ref_pose
+        Rm, tm = match_pose
+        check(self.L.chisel_hip_stereo_update_image(self.h, a, self.real_shape[1], _doubles(Rr, 9, "ref R"), _doubles(tr, 3, "ref t"),
+                                                    _doubles(Rm, 9, "match R"), _doubles(tm, 3, "match t"), dev))
+        self._keep = [k]
+
+    def BindSparsePoints(self, depths, points):
+        """BindSparsePoints (sgm_stereo_mapper.h:60-66): depths (n,) and points (n, 2) x, y in camera-image pixels"""
+        d = np.ascontiguousarray(np.asarray(depths, np.float64).reshape(-1))
+        p = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 2))
+        assert len(d) == len(p), "%d depths for %d points" % (len(d), len(p))
+        check(self.L.chisel_hip_stereo_bind_sparse_points(self.h, d.ctypes.data if len(d) else None, p.ctypes.data if len(p) else None,
+                                                          len(d)))
+
+    def OutputImage(self, out=None):
+        """Output (:219-422) in full: sparse prior, FuseSparseInfo, SGM, WTA and the resize to the camera size.  Returns the
+        float32 (real_h, real_w) depth (numpy), or fills `out` (a torch CUDA tensor, float32 or float64) in place"""
+        assert getattr(self, "real_shape", None) is not None, "OutputImage before InitIntrinsic"
+        check(self.L.chisel_hip_stereo_output_image(self.h))
+        if out is not None:
+            assert tuple(out.shape) == self.real_shape
+            return self.read(self.DEPTH_REAL64 if str(out.dtype).endswith("float64") else self.DEPTH_REAL, out=out)
+        return self.read(self.DEPTH_REAL)
+
+    def debug_prep(self, which):
+        """the prepared inputs (chisel_hip_debug_stereo_prep): PREP_* -> numpy (h, w), float32 or uint8 for the masks"""
+        a = np.empty(self.shape, np.uint8 if which in (self.PREP_MASK_X, self.PREP_MASK_Y) else np.float32)
+        check(self.L.chisel_hip_debug_stereo_prep(self.h, int(which), a.ctypes.data))
+        return a
+
+
+class DepthEstimator:
+    """DepthEstimator (server_pose_graph/src/dense_mapping/depth_estimator.cpp) as ServerKeyFrame drives it: the constructor and
+    Initialize (:165-188, :503-599) make a StereoMapper of the work size for the keyframe's camera size (k3 = 0) and a DepthFilter
+    of the camera size; FuseNewFrame (:191-197) runs FuseNewFrameSGM -- UpdateImage, OutputImage into a float64 device map, the
+    filter update with 1 / depth and cov_all = (3 DEP_SAMPLE)^2 (:276-297) -- and ClearRawCost, all in HBM.  PropogateDepth,
+    Validate and RegularizeDepthMap are not built: their call sites are commented out in the reference."""
+
+    def __init__(self, ref_image, ref_pose_wc, fx, fy, cx, cy, d1, d2, d3, d4, width=640, height=480, params=None, device_id=-1):
+        import torch
+        self.ref_pose_wc = (np.asarray(ref_pose_wc[0], np.float64), np.asarray(ref_pose_wc[1], np.float64))
+        real_h, real_w = tuple(ref_image.shape)
+        self.params = params if params is not None else stereo_default_params()
+        self.mapper = StereoMapper(width, height, self.params, device_id)
+        K = (fx, fy, cx, cy)
+        D = (d1, d2, d3, d4, 0.0)                              # :588
+        self.mapper.InitIntrinsic(K, D, K, D, (real_w, real_h))
+        self.mapper.InitReferenceImage(ref_image)
+        self.filter = DepthFilter(real_h, real_w, device_id)   # :184
+        dev = device_id if device_id >= 0 else torch.cuda.current_device()
+        self._depth = torch.empty((real_h, real_w), dtype=torch.float64, device="cuda:%d" % dev)
+        ds = np.float32(self.params.dep_sample)
+        self.cov_all = float((np.float32(3) * ds) * (np.float32(3) * ds))   # float arithmetic, widened (:293)
+        self.observations = 0
+
+    def BindSparsePoints(self, depths, points):
+        """DepthEstimator::BindSparsePoints (depth_estimator.h:109-115)"""
+        self.mapper.BindSparsePoints(depths, points)
+
+    def FuseNewFrame(self, match_image, match_pose_wc):
+        """FuseNewFrame (:191-197) = FuseNewFrameSGM (:209-299) + ClearRawCost, device-resident"""
+        self.mapper.UpdateImage(match_image, self.ref_pose_wc, match_pose_wc)
+        self.mapper.OutputImage(out=self._depth)
+        self.filter.Update(self._depth, self.cov_all, reciprocal=True)
+        self.mapper.ClearRawCost()
+        self.observations += 1
+
+    def GetInvDepth(self):
+        return self.filter.GetInvDepth()
+
+    def GetRatio(self):
+        return self.filter.GetRatio()
+
+    def GetCov(self):
+        return self.filter.GetCov()
+
+    def read(self, which, out=None):
+        """the filter's maps (DepthFilter.read): DepthFilter.DEPTH is the depth map ServerKeyFrame integrates"""
+        return self.filter.read(which, out=out)
 
 
 def condition_depth(depth64, width=640, height=480, intrinsics=None):

@@ -37,6 +37,7 @@
 #include "kernels_cloud.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
+#include "kernels_stereo_prep.h"
 
 using namespace chisel_hip;
 
@@ -2115,6 +2116,24 @@ struct chisel_hip_stereo {
     float *ref = nullptr, *match = nullptr, *p2w = nullptr;
     float *stage_a = nullptr, *stage_b = nullptr;  // host sparse maps pass through these
     double *stage_out = nullptr;                   // read-out 3 to the host
+    // the raw-image path (chisel_hip_stereo_set_camera and after): allocated by the first set_camera
+    bool has_camera = false;
+    int real_w = 0, real_h = 0;
+    double K1[4] = {}, K2[4] = {};                   // fx, fy, cx, cy scaled to the work size (InitIntrinsic)
+    short2 *map_xy[2] = {};                          // undistort maps of camera 1 (reference) and 2 (match), CV_16SC2 + CV_16UC1
+    uint16_t *map_f[2] = {};
+    uint8_t *raw = nullptr;                          // real_w x real_h input staged contiguous
+    uint8_t *small = nullptr;                        // the W x H resize
+    int *sob_g = nullptr, *sob_x = nullptr, *sob_y = nullptr;
+    long long *sob_partials = nullptr;
+    StereoPrepStats *stats = nullptr;
+    uint8_t *mask_x = nullptr, *mask_y = nullptr;
+    float *sparse_depth = nullptr, *sparse_dist = nullptr;
+    double *pts_depth = nullptr, *pts_xy = nullptr;  // bound points (BindSparsePoints)
+    SparsePoint *pts = nullptr;
+    int n_points = 0, pts_cap = 0;
+    float *depth_real = nullptr;                     // Output's result at the camera size
+    double *stage_real = nullptr;                    // read-out 5 to the host
 };
 
 void chisel_hip_stereo_default_params(chisel_hip_stereo_params *p) {
@@ -2176,7 +2195,11 @@ int chisel_hip_stereo_destroy(chisel_hip_stereo *s) {
     if (!s) return CHISEL_HIP_OK;
     (void)hipSetDevice(s->device);
     (void)hipDeviceSynchronize();
-    void *ptrs[] = {s->ref, s->match, s->p2w, s->stage_a, s->stage_b, s->stage_out, s->view.cost, s->view.sgm, s->view.depth};
+    void *ptrs[] = {s->ref,       s->match,     s->p2w,      s->stage_a,      s->stage_b,   s->stage_out, s->view.cost,
+                    s->view.sgm,  s->view.depth, s->map_xy[0], s->map_xy[1],   s->map_f[0],  s->map_f[1],  s->raw,
+                    s->small,     s->sob_g,     s->sob_x,    s->sob_y,        s->sob_partials, s->stats,  s->mask_x,
+                    s->mask_y,    s->sparse_depth, s->sparse_dist, s->pts_depth, s->pts_xy,  s->pts,       s->depth_real,
+                    s->stage_real};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     delete s;
@@ -2201,36 +2224,35 @@ int chisel_hip_stereo_set_reference(chisel_hip_stereo *s, const float *ref, cons
     return CHISEL_HIP_OK;
 }
 
-int chisel_hip_stereo_update(chisel_hip_stereo *s, const float *match, const float R[9], const float t[3], int on_device) {
-    if (!s || !match || !R || !t) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
-    if (!s->has_reference) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_stereo_update before chisel_hip_stereo_set_reference");
-    HIP_TRY(hipSetDevice(s->device));
+// Update's cost pass (sgm_stereo_mapper.cpp:153, :184-195) on the match image already in s->match
+static int stereo_run_cost(chisel_hip_stereo *s, const float R[9], const float t[3]) {
     const size_t n = (size_t)s->width * s->height;
-    const int rc = stereo_upload(s->match, match, n, on_device);
-    if (rc != CHISEL_HIP_OK) return rc;
     StereoPose P;
     memcpy(P.r, R, sizeof(P.r));
     memcpy(P.t, t, sizeof(P.t));
     s->measurement_cnt++;
     hipLaunchKernelGGL(stereo_cost_kernel, dim3((unsigned)((n + 1) / 2)), dim3(256), 0, 0, s->view, P, s->measurement_cnt, s->prm.dep_sample);
     HIP_TRY(hipGetLastError());
+    return CHISEL_HIP_OK;
+}
+
+int chisel_hip_stereo_update(chisel_hip_stereo *s, const float *match, const float R[9], const float t[3], int on_device) {
+    if (!s || !match || !R || !t) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
+    if (!s->has_reference) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_stereo_update before chisel_hip_stereo_set_reference");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = (size_t)s->width * s->height;
+    int rc = stereo_upload(s->match, match, n, on_device);
+    if (rc == CHISEL_HIP_OK) rc = stereo_run_cost(s, R, t);
+    if (rc != CHISEL_HIP_OK) return rc;
     if (!on_device) HIP_TRY(hipStreamSynchronize(0));  // the host image may go once this returns
     return CHISEL_HIP_OK;  // stream 0: ordered against the next call; reads wait
 }
 
-int chisel_hip_stereo_output(chisel_hip_stereo *s, const float *sparse_depth, const float *sparse_dist, int on_device) {
-    if (!s || (!sparse_depth) != (!sparse_dist)) return fail(CHISEL_HIP_ERR_INVALID, "bad argument (sparse depth and distance go together)");
-    HIP_TRY(hipSetDevice(s->device));
+// Output's device half (sgm_stereo_mapper.cpp:366-382): FuseSparseInfo when given device sparse maps, then SGM and WTA
+static int stereo_run_output(chisel_hip_stereo *s, const float *dd, const float *ds) {
     const int W = s->width, H = s->height;
     const size_t n = (size_t)W * H, nv = n * STEREO_DEP_CNT;
-    if (sparse_depth) {  // FuseSparseInfo (sgm_stereo_mapper.cpp:366-368); without a prior every nDepth is -1 and it changes nothing
-        const float *dd = sparse_depth, *ds = sparse_dist;
-        if (!on_device) {
-            HIP_TRY(hipMemcpyAsync(s->stage_a, sparse_depth, n * sizeof(float), hipMemcpyHostToDevice, 0));
-            HIP_TRY(hipMemcpyAsync(s->stage_b, sparse_dist, n * sizeof(float), hipMemcpyHostToDevice, 0));
-            dd = s->stage_a;
-            ds = s->stage_b;
-        }
+    if (dd) {
         hipLaunchKernelGGL(stereo_fuse_sparse_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, 0, s->view, dd, ds,
                            s->prm.sparse_ratio, s->prm.dep_sample);
         HIP_TRY(hipGetLastError());
@@ -2251,6 +2273,23 @@ int chisel_hip_stereo_output(chisel_hip_stereo *s, const float *sparse_depth, co
     }
     hipLaunchKernelGGL(stereo_wta_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, 0, s->view, s->prm.var_scale, s->prm.dep_sample);
     HIP_TRY(hipGetLastError());
+    return CHISEL_HIP_OK;
+}
+
+int chisel_hip_stereo_output(chisel_hip_stereo *s, const float *sparse_depth, const float *sparse_dist, int on_device) {
+    if (!s || (!sparse_depth) != (!sparse_dist)) return fail(CHISEL_HIP_ERR_INVALID, "bad argument (sparse depth and distance go together)");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = (size_t)s->width * s->height;
+    // FuseSparseInfo (sgm_stereo_mapper.cpp:366-368); without a prior every nDepth is -1 and it changes nothing
+    const float *dd = sparse_depth, *ds = sparse_dist;
+    if (sparse_depth && !on_device) {
+        HIP_TRY(hipMemcpyAsync(s->stage_a, sparse_depth, n * sizeof(float), hipMemcpyHostToDevice, 0));
+        HIP_TRY(hipMemcpyAsync(s->stage_b, sparse_dist, n * sizeof(float), hipMemcpyHostToDevice, 0));
+        dd = s->stage_a;
+        ds = s->stage_b;
+    }
+    const int rc = stereo_run_output(s, dd, ds);
+    if (rc != CHISEL_HIP_OK) return rc;
     if (sparse_depth && !on_device) HIP_TRY(hipStreamSynchronize(0));
     return CHISEL_HIP_OK;
 }
@@ -2266,20 +2305,316 @@ int chisel_hip_stereo_clear(chisel_hip_stereo *s) {
 }
 
 int chisel_hip_stereo_read(chisel_hip_stereo *s, int which, void *dst, int dst_on_device) {
-    if (!s || !dst || which < 0 || which > 3) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
+    if (!s || !dst || which < 0 || which > 5) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
+    if (which >= 4 && !s->has_camera) return fail(CHISEL_HIP_ERR_INVALID, "read-outs 4 and 5 are at the camera size: chisel_hip_stereo_set_camera first");
     HIP_TRY(hipSetDevice(s->device));
-    const size_t n = (size_t)s->width * s->height;
+    const size_t n = (size_t)s->width * s->height, n_real = (size_t)s->real_w * s->real_h;
     const hipMemcpyKind kind = dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     if (which == 0) HIP_TRY(hipMemcpyAsync(dst, s->view.cost, n * STEREO_DEP_CNT * sizeof(float), kind, 0));
     else if (which == 1) HIP_TRY(hipMemcpyAsync(dst, s->view.sgm, n * STEREO_DEP_CNT * sizeof(float), kind, 0));
     else if (which == 2) HIP_TRY(hipMemcpyAsync(dst, s->view.depth, n * sizeof(float), kind, 0));
+    else if (which == 4) HIP_TRY(hipMemcpyAsync(dst, s->depth_real, n_real * sizeof(float), kind, 0));
     else {
-        double *d_out = dst_on_device ? static_cast<double *>(dst) : s->stage_out;
-        hipLaunchKernelGGL(stereo_widen_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, s->view.depth, d_out, (int)n);
+        const float *src = which == 3 ? s->view.depth : s->depth_real;
+        const size_t m = which == 3 ? n : n_real;
+        double *d_out = dst_on_device ? static_cast<double *>(dst) : (which == 3 ? s->stage_out : s->stage_real);
+        hipLaunchKernelGGL(stereo_widen_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, src, d_out, (int)m);
         HIP_TRY(hipGetLastError());
-        if (!dst_on_device) HIP_TRY(hipMemcpyAsync(dst, d_out, n * sizeof(double), hipMemcpyDeviceToHost, 0));
+        if (!dst_on_device) HIP_TRY(hipMemcpyAsync(dst, d_out, m * sizeof(double), hipMemcpyDeviceToHost, 0));
     }
     HIP_TRY(hipStreamSynchronize(0));
+    return CHISEL_HIP_OK;
+}
+
+// ---- the raw-image path: InitIntrinsic, InitReference, Update, BindSparsePoints, Output with their OpenCV work on the device ------
+// cv::invert(DECOMP_LU) of a 3 x 3 CV_64F matrix takes a closed form (core/src/lapack.cpp, cv::invert, n == 3): det3 expanded
+// along the first row, d = 1. / det, then every entry of the adjugate (2 x 2 cofactor differences) times d.  false: det == 0.
+static bool stereo_invert3(const double *m, double *o) {
+#define M_(i, j) m[(i) * 3 + (j)]
+    double d = M_(0, 0) * (M_(1, 1) * M_(2, 2) - M_(1, 2) * M_(2, 1)) - M_(0, 1) * (M_(1, 0) * M_(2, 2) - M_(1, 2) * M_(2, 0)) +
+               M_(0, 2) * (M_(1, 0) * M_(2, 1) - M_(1, 1) * M_(2, 0));
+    if (d == 0.) return false;
+    d = 1. / d;
+    o[0] = (M_(1, 1) * M_(2, 2) - M_(1, 2) * M_(2, 1)) * d;
+    o[1] = (M_(0, 2) * M_(2, 1) - M_(0, 1) * M_(2, 2)) * d;
+    o[2] = (M_(0, 1) * M_(1, 2) - M_(0, 2) * M_(1, 1)) * d;
+    o[3] = (M_(1, 2) * M_(2, 0) - M_(1, 0) * M_(2, 2)) * d;
+    o[4] = (M_(0, 0) * M_(2, 2) - M_(0, 2) * M_(2, 0)) * d;
+    o[5] = (M_(0, 2) * M_(1, 0) - M_(0, 0) * M_(1, 2)) * d;
+    o[6] = (M_(1, 0) * M_(2, 1) - M_(1, 1) * M_(2, 0)) * d;
+    o[7] = (M_(0, 1) * M_(2, 0) - M_(0, 0) * M_(2, 1)) * d;
+    o[8] = (M_(0, 0) * M_(1, 1) - M_(0, 1) * M_(1, 0)) * d;
+#undef M_
+    return true;
+}
+
+// 3 x 3 times 3 x cols (cols 3 or 1), every entry a0 b0 + a1 b1 + a2 b2 left to right; bt: b is 3 x 3 and used transposed
+static void stereo_mul3(const double *a, const double *b, int cols, bool bt, double *o) {
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < cols; ++j) {
+            const double b0 = bt ? b[j * 3 + 0] : b[0 * cols + j], b1 = bt ? b[j * 3 + 1] : b[1 * cols + j], b2 = bt ? b[j * 3 + 2] : b[2 * cols + j];
+            o[i * cols + j] = a[i * 3 + 0] * b0 + a[i * 3 + 1] * b1 + a[i * 3 + 2] * b2;
+        }
+}
+
+int chisel_hip_stereo_homography(const double K1[4], const double K2[4], const double Rr[9], const double tr[3], const double Rm[9],
+                                 const double tm[3], float R[9], float t[3]) {
+    if (!K1 || !K2 || !Rr || !tr || !Rm || !tm || !R || !t) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
+    const double k1[9] = {K1[0], 0.0, K1[2], 0.0, K1[1], K1[3], 0.0, 0.0, 1.0};
+    const double k2[9] = {K2[0], 0.0, K2[2], 0.0, K2[1], K2[3], 0.0, 0.0, 1.0};
+    double k1i[9], a[9], b[9], r[9], tt[3];
+    if (!stereo_invert3(k1, k1i)) return fail(CHISEL_HIP_ERR_INVALID, "K1 is singular");
+    stereo_mul3(k2, Rm, 3, true, a);  // K2 * Rm.t()
+    stereo_mul3(a, Rr, 3, false, b);  // * Rr
+    stereo_mul3(b, k1i, 3, false, r); // * K1.inv()
+    const double d[3] = {tr[0] - tm[0], tr[1] - tm[1], tr[2] - tm[2]};
+    stereo_mul3(a, d, 1, false, tt);  // K2 * Rm.t() * (tr - tm)
+    for (int k = 0; k < 9; ++k) R[k] = (float)r[k];
+    for (int k = 0; k < 3; ++k) t[k] = (float)tt[k];
+    return CHISEL_HIP_OK;
+}
+
+// cvRound as x86-64 computes it (cvtsd2si): round half to even; NaN and values outside int give INT_MIN
+static int stereo_cv_round(double v) {
+    return (v >= -2147483648.5 && v < 2147483647.5) ? (int)std::nearbyint(v) : INT32_MIN;
+}
+
+// cv::undistort(src, dst, K, D, K) of OpenCV 4 (imgproc/src/undistort.dispatch.cpp), its map restated from the scalar loop of
+// initUndistortRectifyMap with R = I and map type CV_16SC2: the rows go in stripes of min(max(1, 4096 / cols), rows); in each,
+// Ar(1,2) = v0 - y and ir = Ar^-1 (stereo_invert3; Ar * I is Ar bit for bit); per row i of the stripe _x, _y, _w start at
+// i * ir[1] + ir[2], i * ir[4] + ir[5], i * ir[7] + ir[8] and get += ir[0], ir[3], ir[6] column by column; w = 1. / _w,
+// x = _x * w, y = _y * w; kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2) with k4..k6 = 0;
+// xd = x kr + p1 2xy + p2 (r2 + 2 x2), yd = y kr + p1 (r2 + 2 y2) + p2 2xy (the thin-prism terms s1..s4 are 0 and the tilt is the
+// identity: they change at most the sign of a zero, which u = fx xd + u0 removes); u, v with fx, fy, u0, v0 of the unmodified
+// A; iu = cvRound(u * 32), iv = cvRound(v * 32); map (short)(iu >> 5), (short)(iv >> 5) and (iv & 31) * 32 + (iu & 31).
+static void stereo_undistort_map(int W, int H, const double K[4], const double D[5], short2 *xy, uint16_t *f) {
+    const double fx = K[0], fy = K[1], u0 = K[2], v0 = K[3];
+    const double k1 = D[0], k2 = D[1], p1 = D[2], p2 = D[3], k3 = D[4], k4 = 0.0, k5 = 0.0, k6 = 0.0;
+    const int stripe0 = std::min(std::max(1, 4096 / std::max(W, 1)), H);
+    for (int y = 0; y < H; y += stripe0) {
+        const int rows = std::min(stripe0, H - y);
+        const double Ar[9] = {fx, 0.0, u0, 0.0, fy, v0 - y, 0.0, 0.0, 1.0};
+        double ir[9];
+        if (!stereo_invert3(Ar, ir)) std::fill(ir, ir + 9, 0.0);  // cv::invert leaves a singular matrix's inverse zeroed
+        for (int i = 0; i < rows; ++i) {
+            double _x = i * ir[1] + ir[2], _y = i * ir[4] + ir[5], _w = i * ir[7] + ir[8];
+            for (int j = 0; j < W; ++j, _x += ir[0], _y += ir[3], _w += ir[6]) {
+                const double w = 1. / _w, x = _x * w, yy = _y * w;
+                const double x2 = x * x, y2 = yy * yy;
+                const double r2 = x2 + y2, _2xy = 2 * x * yy;
+                const double kr = (1 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2);
+                const double xd = x * kr + p1 * _2xy + p2 * (r2 + 2 * x2);
+                const double yd = yy * kr + p1 * (r2 + 2 * y2) + p2 * _2xy;
+                const double u = fx * xd + u0, v = fy * yd + v0;
+                const int iu = stereo_cv_round(u * 32), iv = stereo_cv_round(v * 32);
+                const size_t k = (size_t)(y + i) * W + j;
+                xy[k] = make_short2((short)(iu >> 5), (short)(iv >> 5));
+                f[k] = (uint16_t)((iv & 31) * 32 + (iu & 31));
+            }
+        }
+    }
+}
+
+static int stereo_alloc(void **p, size_t bytes, bool zero) {
+    if (*p) return CHISEL_HIP_OK;
+    HIP_TRY(hipMalloc(p, bytes));
+    if (zero) HIP_TRY(hipMemset(*p, 0, bytes));
+    return CHISEL_HIP_OK;
+}
+
+static void stereo_free(void **p) {
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+}
+
+int chisel_hip_stereo_set_camera(chisel_hip_stereo *s, int real_w, int real_h, const double K1[4], const double D1[5], const double K2[4],
+                                 const double D2[5]) {
+    if (!s || !K1 || !D1 || !K2 || !D2) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
+    if (real_w < 2 || real_h < 2 || real_w > 16384 || real_h > 16384 || (int64_t)real_w * real_h > (1 << 26))
+        return fail(CHISEL_HIP_ERR_INVALID, "bad camera image size");
+    const int W = s->width, H = s->height;
+    if (W < 9 || H < 9) return fail(CHISEL_HIP_ERR_INVALID, "the raw-image path needs a work size of at least 9 x 9 (the border of the 9-tap Sobel)");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());  // buffers below may be in use by queued work
+    const size_t n = (size_t)W * H, n_real = (size_t)real_w * real_h;
+    const size_t n_blocks = (size_t)((W + SOBEL_TILE - 1) / SOBEL_TILE) * ((H + SOBEL_TILE - 1) / SOBEL_TILE);
+    if (s->real_w != real_w || s->real_h != real_h) {
+        stereo_free((void **)&s->raw);
+        stereo_free((void **)&s->depth_real);
+        stereo_free((void **)&s->stage_real);
+    }
+    struct {
+        void **p;
+        size_t bytes;
+        bool zero;
+    } bufs[] = {
+        {(void **)&s->map_xy[0], n * sizeof(short2), false}, {(void **)&s->map_xy[1], n * sizeof(short2), false},
+        {(void **)&s->map_f[0], n * sizeof(uint16_t), false}, {(void **)&s->map_f[1], n * sizeof(uint16_t), false},
+        {(void **)&s->small, n, false},                        {(void **)&s->sob_g, n * sizeof(int), false},
+        {(void **)&s->sob_x, n * sizeof(int), false},           {(void **)&s->sob_y, n * sizeof(int), false},
+        {(void **)&s->sob_partials, n_blocks * SOBEL_N_STATS * sizeof(long long), false},
+        {(void **)&s->stats, sizeof(StereoPrepStats), true},    {(void **)&s->mask_x, n, true},
+        {(void **)&s->mask_y, n, true},                         {(void **)&s->sparse_depth, n * sizeof(float), false},
+        {(void **)&s->sparse_dist, n * sizeof(float), false},   {(void **)&s->raw, n_real, false},
+        {(void **)&s->depth_real, n_real * sizeof(float), true}, {(void **)&s->stage_real, n_real * sizeof(double), false},
+    };
+    for (const auto &b : bufs) {
+        const int rc = stereo_alloc(b.p, b.bytes, b.zero);
+        if (rc != CHISEL_HIP_OK) return rc;  // what was allocated stays with s (destroy frees it); the camera is not set
+    }
+    // InitIntrinsic (sgm_stereo_mapper.cpp:31-45): fx, cx / (real_w / W), fy, cy / (real_h / H)
+    const double sx = (double)real_w / (double)W, sy = (double)real_h / (double)H;
+    const double k1[4] = {K1[0] / sx, K1[1] / sy, K1[2] / sx, K1[3] / sy}, k2[4] = {K2[0] / sx, K2[1] / sy, K2[2] / sx, K2[3] / sy};
+    std::vector<short2> xy(n);
+    std::vector<uint16_t> f(n);
+    for (int c = 0; c < 2; ++c) {
+        stereo_undistort_map(W, H, c == 0 ? k1 : k2, c == 0 ? D1 : D2, xy.data(), f.data());
+        HIP_TRY(hipMemcpy(s->map_xy[c], xy.data(), n * sizeof(short2), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->map_f[c], f.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice));
+    }
+    memcpy(s->K1, k1, sizeof(k1));
+    memcpy(s->K2, k2, sizeof(k2));
+    s->real_w = real_w;
+    s->real_h = real_h;
+    s->has_camera = true;
+    return CHISEL_HIP_OK;
+}
+
+// cv::resize of the real_w x real_h mono8 image to W x H (condition_color_kernel), then cv::undistort with camera `cam` and
+// convertTo(CV_32F) into dst
+static int stereo_prepare(chisel_hip_stereo *s, const uint8_t *img, int step, int on_device, int cam, float *dst) {
+    const int W = s->width, H = s->height, w0 = s->real_w, h0 = s->real_h;
+    const uint8_t *src = img;
+    if (!on_device || step != w0) {
+        HIP_TRY(hipMemcpy2DAsync(s->raw, w0, img, step, w0, h0, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, 0));
+        src = s->raw;
+    }
+    hipLaunchKernelGGL(condition_color_kernel, dim3((W + 255) / 256, H), dim3(256), 0, 0, src, w0, h0, 1, s->small, W, H);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(stereo_remap_kernel, dim3((unsigned)(((size_t)W * H + 255) / 256)), dim3(256), 0, 0, s->small, W, H, s->map_xy[cam],
+                       s->map_f[cam], dst);
+    HIP_TRY(hipGetLastError());
+    return CHISEL_HIP_OK;
+}
+
+static int stereo_check_image(chisel_hip_stereo *s, const uint8_t *img, int step, const char *what) {
+    if (!s || !img) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
+    if (!s->has_camera) return fail(CHISEL_HIP_ERR_INVALID, std::string(what) + " before chisel_hip_stereo_set_camera");
+    if (step < s->real_w) return fail(CHISEL_HIP_ERR_INVALID, "row step shorter than the camera image");
+    return CHISEL_HIP_OK;
+}
+
+int chisel_hip_stereo_set_reference_image(chisel_hip_stereo *s, const uint8_t *img, int step, int on_device) {
+    int rc = stereo_check_image(s, img, step, "chisel_hip_stereo_set_reference_image");
+    if (rc != CHISEL_HIP_OK) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const int W = s->width, H = s->height, n = W * H;
+    rc = stereo_prepare(s, img, step, on_device, 0, s->ref);
+    if (rc != CHISEL_HIP_OK) return rc;
+    const dim3 tiles((W + SOBEL_TILE - 1) / SOBEL_TILE, (H + SOBEL_TILE - 1) / SOBEL_TILE);
+    hipLaunchKernelGGL(stereo_sobel_kernel, tiles, dim3(256), 0, 0, s->ref, W, H, s->sob_g, s->sob_x, s->sob_y, s->sob_partials);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(stereo_prep_stats_kernel, dim3(1), dim3(256), 0, 0, s->sob_partials, (int)(tiles.x * tiles.y), n, s->stats);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(stereo_prep_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, s->sob_g, s->sob_x, s->sob_y, s->stats, n, s->p2w,
+                       s->mask_x, s->mask_y);
+    HIP_TRY(hipGetLastError());
+    if (!on_device) HIP_TRY(hipStreamSynchronize(0));
+    s->measurement_cnt = 0;  // sgm_stereo_mapper.cpp:121
+    s->has_reference = true;
+    return CHISEL_HIP_OK;
+}
+
+int chisel_hip_stereo_update_image(chisel_hip_stereo *s, const uint8_t *img, int step, const double ref_R_wc[9], const double ref_t_wc[3],
+                                   const double match_R_wc[9], const double match_t_wc[3], int on_device) {
+    int rc = stereo_check_image(s, img, step, "chisel_hip_stereo_update_image");
+    if (rc != CHISEL_HIP_OK) return rc;
+    if (!ref_R_wc || !ref_t_wc || !match_R_wc || !match_t_wc) return fail(CHISEL_HIP_ERR_INVALID, "null pose");
+    if (!s->has_reference) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_stereo_update_image before a reference image");
+    float R[9], t[3];
+    rc = chisel_hip_stereo_homography(s->K1, s->K2, ref_R_wc, ref_t_wc, match_R_wc, match_t_wc, R, t);  // :179-182
+    if (rc != CHISEL_HIP_OK) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    rc = stereo_prepare(s, img, step, on_device, 1, s->match);
+    if (rc == CHISEL_HIP_OK) rc = stereo_run_cost(s, R, t);
+    if (rc != CHISEL_HIP_OK) return rc;
+    if (!on_device) HIP_TRY(hipStreamSynchronize(0));
+    return CHISEL_HIP_OK;
+}
+
+int chisel_hip_stereo_bind_sparse_points(chisel_hip_stereo *s, const double *depth, const double *xy, int n) {
+    if (!s || n < 0 || n > (1 << 24) || (n > 0 && (!depth || !xy))) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
+    if (!s->has_camera) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_stereo_bind_sparse_points before chisel_hip_stereo_set_camera");
+    HIP_TRY(hipSetDevice(s->device));
+    if (n > s->pts_cap) {
+        HIP_TRY(hipDeviceSynchronize());  // a queued Output may still read the old points
+        stereo_free((void **)&s->pts_depth);
+        stereo_free((void **)&s->pts_xy);
+        stereo_free((void **)&s->pts);
+        s->pts_cap = 0;
+        const int cap = std::max(n, 1024);
+        int rc = stereo_alloc((void **)&s->pts_depth, (size_t)cap * sizeof(double), false);
+        if (rc == CHISEL_HIP_OK) rc = stereo_alloc((void **)&s->pts_xy, (size_t)cap * 2 * sizeof(double), false);
+        if (rc == CHISEL_HIP_OK) rc = stereo_alloc((void **)&s->pts, (size_t)cap * sizeof(SparsePoint), false);
+        if (rc != CHISEL_HIP_OK) {
+            s->n_points = 0;
+            return rc;
+        }
+        s->pts_cap = cap;
+    }
+    if (n > 0) {  // hipMemcpy from pageable memory: ordered after queued work, done when it returns (BindSparsePoints copies)
+        HIP_TRY(hipMemcpy(s->pts_depth, depth, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(s->pts_xy, xy, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice));
+    }
+    s->n_points = n;
+    return CHISEL_HIP_OK;
+}
+
+static SparseRatios stereo_sparse_ratios() {
+    SparseRatios R;
+    for (int u = -SPARSE_WIN; u <= SPARSE_WIN; ++u)
+        for (int v = -SPARSE_WIN; v <= SPARSE_WIN; ++v) {
+            double r = (1.0 - (std::sqrt((double)(u * u + v * v)) / (SPARSE_WIN * 1.414)));  // sgm_stereo_mapper.cpp:346-347
+            r = r * r;
+            const int b = (u + SPARSE_WIN) * SPARSE_SIDE + (v + SPARSE_WIN);
+            R.ratio[b] = r;
+            R.stored[b] = (float)(r * r);  // :350
+        }
+    return R;
+}
+
+int chisel_hip_stereo_output_image(chisel_hip_stereo *s) {
+    if (!s) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
+    if (!s->has_camera) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_stereo_output_image before chisel_hip_stereo_set_camera");
+    HIP_TRY(hipSetDevice(s->device));
+    const int W = s->width, H = s->height, n = s->n_points;
+    static const SparseRatios ratios = stereo_sparse_ratios();
+    // 1. the sparse prior (:229-357): -1 / 0 where no point writes
+    if (n > 0) {
+        hipLaunchKernelGGL(stereo_sparse_points_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, s->pts_depth, s->pts_xy, n, W, H,
+                           (double)s->real_h / (double)H, (double)s->real_w / (double)W, s->mask_x, s->mask_y, s->pts);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(stereo_sparse_raster_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, 0, s->pts, n, W, H, ratios,
+                       s->sparse_depth, s->sparse_dist);
+    HIP_TRY(hipGetLastError());
+    // 2-4. FuseSparseInfo (all -1 without points: it changes nothing and is skipped), SGM, WTA
+    const int rc = stereo_run_output(s, n > 0 ? s->sparse_depth : nullptr, s->sparse_dist);
+    if (rc != CHISEL_HIP_OK) return rc;
+    // 5. cv::resize to the camera size (:409)
+    hipLaunchKernelGGL(stereo_resize_f32_kernel, dim3((s->real_w + 255) / 256, s->real_h), dim3(256), 0, 0, s->view.depth, W, H, s->depth_real,
+                       s->real_w, s->real_h);
+    HIP_TRY(hipGetLastError());
+    return CHISEL_HIP_OK;
+}
+
+int chisel_hip_debug_stereo_prep(chisel_hip_stereo *s, int which, void *dst) {
+    if (!s || !dst || which < 0 || which > 6) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
+    if (which >= 3 && !s->has_camera) return fail(CHISEL_HIP_ERR_INVALID, "no camera set");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t n = (size_t)s->width * s->height;
+    const void *src[7] = {s->ref, s->match, s->p2w, s->mask_x, s->mask_y, s->sparse_depth, s->sparse_dist};
+    HIP_TRY(hipMemcpy(dst, src[which], n * (which == 3 || which == 4 ? 1 : sizeof(float)), hipMemcpyDeviceToHost));
     return CHISEL_HIP_OK;
 }
 

@@ -315,11 +315,12 @@ int chisel_hip_depth_filter_read(chisel_hip_depth_filter *filter, int which, dou
 /* ---- the step before that: the stereo matcher (StereoMapper, the reference's only GPU code) --------------------------------
  * StereoMapper (server_pose_graph/src/dense_mapping/sgm_stereo_mapper.cpp, kernels calc_cost.cu): plane-sweep absolute-difference
  * cost over STEREO_DEP_CNT = 128 inverse depths i * dep_sample, four-path SGM, winner-takes-all with parabola sub-sample.  The cost
- * and SGM volumes ([height][width][128] floats, depth fastest: 314 MB at 640 x 480) and the depth map live in HBM.  What stays
- * with the caller, on the host as in the reference: cv::resize + cv::undistort of both images, the P2 weight map
- * 0.8 + 1.5 m^3 / (1 + |Sobel(5,5,9)|^3) (sgm_stereo_mapper.cpp:72-83), the sparse prior maps of Output's window loop (:229-357),
- * the final cv::resize (:409).  Same numbers as the reference bit for bit, except match-image samples: bilinear with exact fp32
- * weights where the CUDA texture quantises them.  Images: width * height floats, on the host or (flag) in HBM.
+ * and SGM volumes ([height][width][128] floats, depth fastest: 314 MB at 640 x 480) and the depth map live in HBM.  Two ways in:
+ * the float entries (set_reference / update / output) take images the caller has already resized and undistorted, with its own P2
+ * weight map and sparse maps; the raw-image entries (set_camera and after, below) take the camera's mono8 frames and do the
+ * reference's OpenCV work on the device too.  Same numbers as the reference bit for bit, except match-image samples: bilinear with
+ * exact fp32 weights where the CUDA texture quantises them.  Images: width * height floats, on the host or (flag)
+ * in HBM.
  *   default_params  dense_mapping_parameters.cpp:3-11 (pi1 16, pi2 64, tau_so 8, sgm_q1 1, sgm_q2 1, var_scale 1, nSparseRatio 15)
  *                   and DEP_SAMPLE = 1.0f / (0.11f * 460.95f) (dense_mapping_parameters.h:24,36-37)
  *   create          StereoMapper::StereoMapper (sgm_stereo_mapper.cpp:11-18); width, height >= 2 at run time (the reference
@@ -332,7 +333,9 @@ int chisel_hip_depth_filter_read(chisel_hip_depth_filter *filter, int which, dou
  *                   left, down, up (:365-546), filterCostKernel (:235-282) -> depth map (1000 where no minimum is accepted)
  *   clear           ClearRawCost (:202-216): cost, SGM and depth zeroed; the measurement count is NOT reset (the reference's)
  *   read            which = 0 cost volume f32, 1 SGM volume f32, 2 depth map f32, 3 depth map widened to f64
- *                   (depth_estimator.cpp:283): the input of chisel_hip_depth_filter_update(..., reciprocal = 1, on_device = 1)
+ *                   (depth_estimator.cpp:283): the input of chisel_hip_depth_filter_update(..., reciprocal = 1, on_device = 1);
+ *                   4 / 5 the camera-size depth of the last output_image as f32 / f64 (5: the filter's input when the filter has
+ *                   the camera size, as DepthEstimator's has, depth_estimator.cpp:276-297); both need set_camera
  * Every call runs on the null stream: update / output return before the kernels finish and the next call (also a depth-filter
  * call) is ordered after them; read waits. */
 typedef struct {
@@ -347,6 +350,45 @@ int chisel_hip_stereo_update(chisel_hip_stereo *s, const float *match, const flo
 int chisel_hip_stereo_output(chisel_hip_stereo *s, const float *sparse_depth, const float *sparse_dist, int on_device);
 int chisel_hip_stereo_clear(chisel_hip_stereo *s);
 int chisel_hip_stereo_read(chisel_hip_stereo *s, int which, void *dst, int dst_on_device);
+/* The raw-image path: StereoMapper's OpenCV steps, restated from OpenCV 4's published algorithms and run on the device.  Parity
+ * with the real OpenCV is unpinned (OpenCV is not a dependency; the restatement in tests/stereo_prep_restated.py fixes each rule).
+ *   set_camera             InitIntrinsic (sgm_stereo_mapper.cpp:20-52): K = (fx, fy, cx, cy) of the real_w x real_h camera, fx, cx
+ *                          divided by real_w / (double)width, fy, cy by real_h / (double)height; D = (k1, k2, p1, p2, k3) (the
+ *                          reference passes k3 = 0, depth_estimator.cpp:588).  Builds both cameras' cv::undistort maps once, on
+ *                          the host in double (they depend only on K, D and the size; the reference rebuilds them per call) and
+ *                          keeps them in HBM.  Needs width, height >= 9 (the border of the 9-tap Sobel).
+ *   set_reference_image    InitReference (:55-123) on a real_w x real_h mono8 image (ServerKeyFrame::m_mImage), row step `step`
+ *                          bytes, on the host or (flag) in HBM: cv::resize to width x height (8-bit INTER_LINEAR, the rules of
+ *                          chisel_hip_condition_color), cv::undistort (remap with the fixed-point bilinear table, BORDER_CONSTANT),
+ *                          the f32 reference image; the P2 weight map (float)(((1.5 m) m) m / (1 + g (g g)) * 1.0 + 0.8), g =
+ *                          |Sobel(5,5,9)|, m = mean g; the thresholded Sobel(3,0,7) / Sobel(0,3,7) maps as masks g >= mean +
+ *                          stddev && g > 0 (all Output reads of them); Sobel kernels of getSobelKernels, BORDER_REFLECT_101, exact
+ *                          in int32; mean and stddev from exact int64 sums.  Measurement count = 0.
+ *   update_image           Update (:125-199): the match image resized and undistorted with camera 2, R and t from the two
+ *                          camera-to-world poses (chisel_hip_stereo_homography with the scaled K), then the cost pass of update
+ *   bind_sparse_points     BindSparsePoints (sgm_stereo_mapper.h:60-66): n points, depth[n] and xy[2 n] (x, y in real-image
+ *                          pixels, as server_keyframe.cpp:936-960 builds them), host arrays, copied; n = 0 clears
+ *   output_image           Output in full (:219-422): the sparse depth / distance maps rasterised on the device with every quirk of
+ *                          the window loop (:229-357: swapped x / y scales, int truncation, bounds from the masks read at the flat
+ *                          index (nY + vs) * width + nX + us -- a read outside the map counts as 0, where the reference is
+ *                          undefined --, the outward propagation, the border skip, a write when dist < ratio that stores ratio^2;
+ *                          overlapping windows give the sequential loop's result), FuseSparseInfo, SGM, WTA, then the f32
+ *                          INTER_LINEAR cv::resize of the depth to real_w x real_h (float weights and products; 1000 is
+ *                          interpolated like any other value) for read-outs 4 and 5
+ *   homography             host arithmetic, no device: R = K2 Rm^T Rr K1^-1 and t = K2 Rm^T (tr - tm) (:179-182) in double, every
+ *                          3 x 3 product an entry at a time a0 b0 + a1 b1 + a2 b2 left to right, K1^-1 the closed form cv::invert
+ *                          (DECOMP_LU) takes for 3 x 3 (det3 along the first row, d = 1. / det, adjugate entries times d); narrowed
+ *                          to float.  K = (fx, fy, cx, cy), R row-major, poses camera-to-world.
+ * A raw entry before set_camera, a work size below 9 x 9, a step below real_w or n < 0 is CHISEL_HIP_ERR_INVALID, nothing launched. */
+int chisel_hip_stereo_set_camera(chisel_hip_stereo *s, int real_w, int real_h, const double K1[4], const double D1[5], const double K2[4],
+                                 const double D2[5]);
+int chisel_hip_stereo_set_reference_image(chisel_hip_stereo *s, const uint8_t *img, int step, int on_device);
+int chisel_hip_stereo_update_image(chisel_hip_stereo *s, const uint8_t *img, int step, const double ref_R_wc[9], const double ref_t_wc[3],
+                                   const double match_R_wc[9], const double match_t_wc[3], int on_device);
+int chisel_hip_stereo_bind_sparse_points(chisel_hip_stereo *s, const double *depth, const double *xy, int n);
+int chisel_hip_stereo_output_image(chisel_hip_stereo *s);
+int chisel_hip_stereo_homography(const double K1[4], const double K2[4], const double Rr[9], const double tr[3], const double Rm[9],
+                                 const double tm[3], float R[9], float t[3]);
 
 /* Binary dump / restore of the whole map (the correct counterpart of chisel_ros FillChunkMessage,
  * Serialization.h:31-84, whose bit packing loses data; also checkpoint / resume).  File: 32-byte header

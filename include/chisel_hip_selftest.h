@@ -31,6 +31,10 @@ int chisel_hip_debug_cull_space(const int range_min[3], const int range_dim[3], 
                                 int capacity, int *count);
 int chisel_hip_debug_frustum_range(const float *pose, float near_plane, float far_plane, float fy, float cy, int W, int H, int chunk_n,
                                    float res, int *range_min3, int *range_dim3, float *planes24, float *corners24);
+/* the stereo matcher's prepared inputs (chisel_hip_stereo_set_reference_image / update_image / output_image), to the host:
+ * which = 0 reference image, 1 match image, 2 P2 weight map (f32, width x height), 3 / 4 Sobel(3,0,7) / Sobel(0,3,7) masks
+ * (1 byte per pixel), 5 / 6 the rasterised sparse depth / distance maps (f32); 3-6 need chisel_hip_stereo_set_camera */
+int chisel_hip_debug_stereo_prep(chisel_hip_stereo *s, int which, void *dst);
 
 #ifdef __cplusplus
 }
