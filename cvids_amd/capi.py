@@ -7,7 +7,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CHISEL_HIP_LIB selects a diagnostic build (e.g. libchisel_hip_stamps.so); the default is the product library
 _LIB = os.path.join(_HERE, os.environ.get("CHISEL_HIP_LIB", "libchisel_hip.so"))
 
-ABI_VERSION = 2  # CHISEL_HIP_ABI_VERSION of include/chisel_hip.h this mirror was written against (tests/test_abi.py compares)
+ABI_VERSION = 3  # CHISEL_HIP_ABI_VERSION of include/chisel_hip.h this mirror was written against (tests/test_abi.py compares)
 NUM_COUNTERS = 9
 COUNTER_NAMES = ["sdf", "col", "col_sat", "probe", "carved", "work_chunks", "new_chunks", "updated_chunks", "frames"]
 NUM_KERNELS = 6
@@ -70,7 +70,7 @@ EXPORTS = [
     "chisel_hip_list_chunks", "chisel_hip_has_chunk", "chisel_hip_download_chunk", "chisel_hip_upload_chunk",
     "chisel_hip_meshes_to_update", "chisel_hip_meshes_to_update_since", "chisel_hip_meshes_to_update_prefetch", "chisel_hip_shell_plan_device", "chisel_hip_shell_segment_bytes", "chisel_hip_export_shells_packed", "chisel_hip_import_shells_packed", "chisel_hip_update_meshes_planned", "chisel_hip_shell_plan_queue", "chisel_hip_import_shells_fixed", "chisel_hip_shell_commit", "chisel_hip_num_meshes", "chisel_hip_list_meshes", "chisel_hip_mesh_size",
     "chisel_hip_download_mesh", "chisel_hip_get_sdf", "chisel_hip_get_sdf_and_gradient", "chisel_hip_save_ply",
-    "chisel_hip_save_map", "chisel_hip_load_map", "chisel_hip_export_chunks", "chisel_hip_import_ghost_chunks",
+    "chisel_hip_save_map", "chisel_hip_load_map",
     "chisel_hip_drop_ghost_chunks", "chisel_hip_update_meshes_of", "chisel_hip_condition_depth", "chisel_hip_condition_color", "chisel_hip_publish_cloud",
     "chisel_hip_depth_filter_create", "chisel_hip_depth_filter_destroy", "chisel_hip_depth_filter_update", "chisel_hip_depth_filter_read",
     "chisel_hip_stereo_default_params", "chisel_hip_stereo_create", "chisel_hip_stereo_destroy", "chisel_hip_stereo_set_reference",
@@ -78,7 +78,7 @@ EXPORTS = [
     "chisel_hip_stereo_set_camera", "chisel_hip_stereo_set_reference_image", "chisel_hip_stereo_update_image",
     "chisel_hip_stereo_bind_sparse_points", "chisel_hip_stereo_output_image", "chisel_hip_stereo_homography",
     "chisel_hip_get_counters", "chisel_hip_memory_statistics", "chisel_hip_topology_epoch", "chisel_hip_candidates", "chisel_hip_cloud_candidates", "chisel_hip_mesh_cube", "chisel_hip_write_mesh_ply", "chisel_hip_shade_vertices", "chisel_hip_generate_mesh", "chisel_hip_recompute_mesh", "chisel_hip_integrate_chunk", "chisel_hip_dirty_ids_device", "chisel_hip_mesh_shell_plan",
-    "chisel_hip_shell_volume", "chisel_hip_export_shells", "chisel_hip_import_ghost_shells", "chisel_hip_set_profiling", "chisel_hip_get_profile", "chisel_hip_get_launch_stats", "chisel_hip_pool_info", "chisel_hip_mc_tables", "chisel_hip_mesh_cube_values", "chisel_hip_interpolate_vertex", "chisel_hip_raycast", "chisel_hip_chunk_owner", "chisel_hip_frustum", "chisel_hip_frustum_from_vectors", "chisel_hip_create_group",
+    "chisel_hip_shell_volume", "chisel_hip_set_profiling", "chisel_hip_get_profile", "chisel_hip_get_launch_stats", "chisel_hip_pool_info", "chisel_hip_mc_tables", "chisel_hip_mesh_cube_values", "chisel_hip_interpolate_vertex", "chisel_hip_raycast", "chisel_hip_chunk_owner", "chisel_hip_frustum", "chisel_hip_frustum_from_vectors", "chisel_hip_create_group",
 ]
 # the device self-tests and debug read-outs include/chisel_hip_selftest.h declares
 SELFTEST_EXPORTS = [
@@ -159,8 +159,6 @@ def load_library():
     L.chisel_hip_get_sdf.argtypes = [vp, f32p, C.POINTER(C.c_double), i32p]
     L.chisel_hip_get_sdf_and_gradient.argtypes = [vp, f32p, C.POINTER(C.c_double), f32p, i32p]
     L.chisel_hip_save_ply.argtypes = [vp, C.c_char_p]
-    L.chisel_hip_export_chunks.argtypes = [vp, i32p, C.c_int, vp, vp, vp, i32p, C.c_int]
-    L.chisel_hip_import_ghost_chunks.argtypes = [vp, i32p, C.c_int, vp, vp, vp, i32p, C.c_int]
     L.chisel_hip_drop_ghost_chunks.argtypes = [vp]
     L.chisel_hip_condition_depth.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), vp]
     L.chisel_hip_condition_color.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp]
@@ -213,8 +211,6 @@ def load_library():
         L.chisel_hip_mesh_shell_plan.argtypes = [i32p, C.c_int64, C.c_int, C.c_int, C.c_int, i32p, C.c_int64, i64p, i32p, C.c_int64, i64p]
         L.chisel_hip_shell_volume.argtypes = [C.c_int, C.c_int]
         L.chisel_hip_shell_volume.restype = C.c_int64
-        L.chisel_hip_export_shells.argtypes = [vp, i32p, C.c_int, vp, vp, vp, vp, C.c_int]
-        L.chisel_hip_import_ghost_shells.argtypes = [vp, i32p, C.c_int, vp, vp, vp, vp, C.c_int]
         L.chisel_hip_generate_mesh.argtypes = [vp, i32p, C.c_int, C.c_int64, C.c_int64, f32p, f32p, f32p, f32p, i64p, i64p]
     if hasattr(L, "chisel_hip_memory_statistics"):
         L.chisel_hip_memory_statistics.argtypes = [vp, C.POINTER(Statistics)]

@@ -248,51 +248,6 @@ class Chisel:
     def Reset(self):
         check(self.L.chisel_hip_reset(self.h))
 
-    # ---- meshing a sharded map: halo chunks (chisel_hip.h "meshing a sharded map") ------------------------------
-    def ExportChunks(self, ids, device=False):
-        """-> (sdf [n, V] float32, weight [n, V] float32, rgbw [n, V, 4] uint8 or None, found [n] int32) of the listed chunks;
-        device=True: the three payload arrays are torch CUDA tensors (they never visit the host), `found` stays a numpy array"""
-        ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1, 3))
-        n = len(ids)
-        found = np.zeros(n, np.int32)
-        if device:
-            import torch
-            dev = torch.device("cuda", torch.cuda.current_device())
-            sdf = torch.empty((n, self.V), dtype=torch.float32, device=dev)
-            wgt = torch.empty((n, self.V), dtype=torch.float32, device=dev)
-            col = torch.empty((n, self.V, 4), dtype=torch.uint8, device=dev) if self.use_color else None
-            ptr = lambda t: t.data_ptr() if t is not None else None
-        else:
-            sdf = np.empty((n, self.V), np.float32)
-            wgt = np.empty((n, self.V), np.float32)
-            col = np.empty((n, self.V, 4), np.uint8) if self.use_color else None
-            ptr = lambda a: a.ctypes.data if a is not None else None
-        if n:
-            check(self.L.chisel_hip_export_chunks(self.h, ids.ctypes.data_as(C.POINTER(C.c_int)), n, ptr(sdf), ptr(wgt), ptr(col),
-                                                  found.ctypes.data_as(C.POINTER(C.c_int)), int(bool(device))))
-        return sdf, wgt, col, found
-
-    def ImportGhostChunks(self, ids, sdf, wgt, col=None, found=None):
-        """payload: numpy arrays, or torch CUDA tensors (used in place)"""
-        ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1, 3))
-        n = len(ids)
-        if not n:
-            return
-        on_device = not isinstance(sdf, np.ndarray) and getattr(sdf, "is_cuda", False)
-        if on_device:
-            sdf, wgt = sdf.contiguous(), wgt.contiguous()
-            col = col.contiguous() if col is not None else None
-            ptr = lambda t: t.data_ptr() if t is not None else None
-        else:
-            sdf = np.ascontiguousarray(sdf, np.float32)
-            wgt = np.ascontiguousarray(wgt, np.float32)
-            col = np.ascontiguousarray(col, np.uint8) if col is not None else None
-            ptr = lambda a: a.ctypes.data if a is not None else None
-        found = np.ascontiguousarray(found, np.int32) if found is not None else None
-        check(self.L.chisel_hip_import_ghost_chunks(self.h, ids.ctypes.data_as(C.POINTER(C.c_int)), n, ptr(sdf), ptr(wgt), ptr(col),
-                                                    found.ctypes.data_as(C.POINTER(C.c_int)) if found is not None else None, int(on_device)))
-        self._keep = [sdf, wgt, col]
-
     # ---- meshing a sharded map with shells (chisel_hip.h "meshing a sharded map with shells") --------------------
     def DirtyIdsDevice(self, out):
         """out: torch int32 CUDA tensor of 1 + 4 * capacity elements -> [n, (x, y, z, flag) * n] (filled on the map's stream: no wait)"""
@@ -311,53 +266,6 @@ class Chisel:
             if h[0] <= cap:
                 return h[1:1 + 4 * int(h[0])].reshape(-1, 4).copy()
             cap = 2 * int(h[0])
-
-    def ExportShells(self, items, device=False):
-        """items: (n, 4) int32 (x, y, z, box) -> (sdf [vox], weight [vox], rgbw [vox, 4] or None, found [n]) packed box after box;
-        device=True: torch CUDA tensors, nothing has been waited for (record_event orders the consumer)"""
-        items = np.ascontiguousarray(np.asarray(items, np.int32).reshape(-1, 4))
-        n = len(items)
-        edge = self.chunk_size[0]
-        vox = int(shell_volumes(items[:, 3], edge).sum()) if n else 0
-        if device:
-            import torch
-            dev = torch.device("cuda", torch.cuda.current_device())
-            sdf = torch.empty((vox,), dtype=torch.float32, device=dev)
-            wgt = torch.empty((vox,), dtype=torch.float32, device=dev)
-            col = torch.empty((vox, 4), dtype=torch.uint8, device=dev) if self.use_color else None
-            found = torch.empty((n,), dtype=torch.int32, device=dev)  # (every entry is written by the kernel)
-            ptr = lambda t: t.data_ptr() if t is not None else None
-        else:
-            sdf, wgt = np.empty(vox, np.float32), np.empty(vox, np.float32)
-            col = np.empty((vox, 4), np.uint8) if self.use_color else None
-            found = np.zeros(n, np.int32)
-            ptr = lambda a: a.ctypes.data if a is not None else None
-        if n:
-            check(self.L.chisel_hip_export_shells(self.h, items.ctypes.data_as(C.POINTER(C.c_int)), n, ptr(sdf), ptr(wgt), ptr(col), ptr(found),
-                                                  int(bool(device))))
-        self._keep = [items]
-        return sdf, wgt, col, found
-
-    def ImportGhostShells(self, items, sdf, wgt, col, found):
-        """payload as ExportShells returns it (numpy arrays, or torch CUDA tensors used in place behind wait_event)"""
-        items = np.ascontiguousarray(np.asarray(items, np.int32).reshape(-1, 4))
-        n = len(items)
-        if not n:
-            return
-        on_device = not isinstance(sdf, np.ndarray) and getattr(sdf, "is_cuda", False)
-        if on_device:
-            ptr = lambda t: t.data_ptr() if t is not None else None
-        else:
-            sdf, wgt = np.ascontiguousarray(sdf, np.float32), np.ascontiguousarray(wgt, np.float32)
-            col = np.ascontiguousarray(col, np.uint8) if col is not None else None
-            found = np.ascontiguousarray(found, np.int32)
-            ptr = lambda a: a.ctypes.data if a is not None else None
-        check(self.L.chisel_hip_import_ghost_shells(self.h, items.ctypes.data_as(C.POINTER(C.c_int)), n, ptr(sdf), ptr(wgt), ptr(col), ptr(found),
-                                                    int(on_device)))
-        # the import is only queued (device payloads are read in place, nothing is waited for): the payload must outlive it.  Kept until
-        # DropGhostChunks, which returns after the recompute behind the imports has started (it looks at that recompute's totals).
-        self._ghost_keep = getattr(self, "_ghost_keep", []) + [(items, sdf, wgt, col, found)]
-        self._imports_fenced = False  # (only a recompute queued BEHIND this import tells the host that it has read its payload)
 
     # ---- the sharded recompute planned on the device (chisel_hip.h: chisel_hip_shell_plan_device ...) -------------------------------
     def PlanShellsDevice(self, gathered, world, cap):
@@ -401,22 +309,13 @@ class Chisel:
 
     def UpdateMeshesPlanned(self):
         check(self.L.chisel_hip_update_meshes_planned(self.h))
-        self._imports_fenced = True
 
     def DropGhostChunks(self):
         check(self.L.chisel_hip_drop_ghost_chunks(self.h))
-        if getattr(self, "_ghost_keep", None):
-            # a recompute queued behind the imports (UpdateMeshesOf): the call above has looked at its totals, which the device publishes
-            # after everything in front of it -- the imports have read their payload.  Without one nothing has told the host so: wait.
-            if not getattr(self, "_imports_fenced", False):
-                self.synchronize()
-            self._ghost_keep = []
-        self._imports_fenced = False
 
     def UpdateMeshesOf(self, ids):
         ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1, 3))
         check(self.L.chisel_hip_update_meshes_of(self.h, ids.ctypes.data_as(C.POINTER(C.c_int)), len(ids)))
-        self._imports_fenced = True
 
     def SaveMap(self, filename):
         """binary dump of every resident chunk (chisel_hip_save_map): checkpoint"""
@@ -964,15 +863,3 @@ def mesh_shell_plan(entries, n_shards, rank, shard_block=2):
 
 def shell_volume(box, chunk_edge):
     return int(capi.load_library().chisel_hip_shell_volume(int(box), int(chunk_edge)))
-
-
-_SHELL_VOLUMES = {}
-
-
-def shell_volumes(boxes, chunk_edge):
-    """voxels in the payload of every box code of an array (a table of the 64 codes per chunk edge: one library call per code and
-    edge, not one per item -- a recompute lists thousands of items)"""
-    table = _SHELL_VOLUMES.get(int(chunk_edge))
-    if table is None:
-        table = _SHELL_VOLUMES[int(chunk_edge)] = np.array([shell_volume(b, chunk_edge) for b in range(64)], np.int64)
-    return table[np.asarray(boxes, np.int64)]

@@ -306,7 +306,6 @@ struct chisel_hip_map {
     int mesh_seq = 0;                                                  // recomputes queued so far
     JobInfo *mesh_info_host = nullptr;                                 // pinned: its first MESH_INFO_PREFETCH per-job records
     hipStream_t copy_stream = nullptr;                                 // small device->host copies that must not wait for queued batches
-    std::vector<int> ghost_ids;                                        // chunks of other shards imported for meshing (x, y, z triples)
     // the plan of a sharded recompute, made on the device (kernels_map.h: ShellPlan; chisel_hip_shell_plan_device ...)
     ShellPlan shell_plan{};
     int *shell_plan_host = nullptr, *shell_plan_host_dev = nullptr;    // pinned: where the plan's figures reach the host (the one wait of a sharded recompute)
@@ -332,11 +331,6 @@ struct chisel_hip_map {
     int *dirty_tail_host = nullptr, *dirty_tail_dev = nullptr;         // pinned: where list_dirty_tail_kernel leaves the new entries of the dirty list
     int batch_frames = KMAX;                                           // frames per launch set in chisel_hip_integrate_batch
     uint64_t ghost_bytes = 0;                                          // group handle: ghost voxel bytes its recomputes have moved between shards
-    int *shell_items_dev = nullptr;                                    // staging of the items / offsets of chisel_hip_export_shells / import_ghost_shells
-    long long *shell_offs_dev = nullptr;
-    int shell_capacity = 0;
-    int *shell_first_dev = nullptr;                                    // chisel_hip_import_ghost_shells: first item of every distinct ghost
-    int shell_first_capacity = 0;
     bool single_chunk = false;                                         // chisel_hip_integrate_chunk: the next integrate call sees this id only
     int single_id[3] = {0, 0, 0};
     bool mesh_mark_needed = false;                                     // slots were dirtied by something other than integrate_kernel (point clouds), or the kept job list was given up: the next recompute runs mesh_mark_kernel
@@ -1600,7 +1594,7 @@ int chisel_hip_destroy(chisel_hip_map *m) {
         v.sdf = nullptr; v.wgt = nullptr; v.rgbw = nullptr;
     }
     void *ptrs[] = {v.sdf, v.wgt, v.rgbw, v.hash_keys, v.hash_vals, v.slot_key, v.slot_dirty, v.free_list, v.free_top,
-                    v.counters, v.block_counters, m->view_dev, m->scratch_i, m->shell_items_dev, m->shell_offs_dev, m->shell_first_dev, v.mesh_jobs};
+                    v.counters, v.block_counters, m->view_dev, m->scratch_i, v.mesh_jobs};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     for (auto &bs : m->sets) {
@@ -1919,19 +1913,6 @@ int chisel_hip_download_chunk(chisel_hip_map *m, const int id[3], float *sdf, fl
     }
     return CHISEL_HIP_OK;
 }
-
-namespace {
-// device staging for the batched chunk transfers: ids, flags and (host callers) the voxel rows
-struct ChunkStage {
-    int *ids = nullptr, *flags = nullptr;
-    float *sdf = nullptr, *wgt = nullptr;
-    uchar4 *col = nullptr;
-    ~ChunkStage() {
-        for (void *p : {(void *)ids, (void *)flags, (void *)sdf, (void *)wgt, (void *)col})
-            if (p) (void)hipFree(p);
-    }
-};
-}  // namespace
 
 int chisel_hip_condition_depth(const double *src, int w0, int h0, int src_on_device, float *dst, int w, int h, int dst_on_device, double K[4],
                                void *hip_stream) {
@@ -2618,82 +2599,6 @@ int chisel_hip_debug_stereo_prep(chisel_hip_stereo *s, int which, void *dst) {
     return CHISEL_HIP_OK;
 }
 
-int chisel_hip_export_chunks(chisel_hip_map *m, const int *ids, int n, float *sdf, float *weight, uint8_t *rgbw, int *found, int on_device) {
-    SETTLE(m);
-    if (m && m->is_group) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "chisel_hip_export_chunks is a call between the shards of a map: a group makes it itself (chisel_hip_update_meshes)");
-    if (!m || n < 0 || (n > 0 && (!ids || !sdf || !weight || !found))) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
-    if (n == 0) return CHISEL_HIP_OK;
-    HIP_TRY(hipSetDevice(m->device));
-    const size_t V = (size_t)m->V, rows = (size_t)n * V;
-    const bool color = m->view.rgbw && rgbw;
-    ChunkStage st;
-    HIP_TRY(hipMalloc(&st.ids, (size_t)n * 3 * sizeof(int)));
-    HIP_TRY(hipMalloc(&st.flags, (size_t)n * sizeof(int)));
-    HIP_TRY(hipMemcpyAsync(st.ids, ids, (size_t)n * 3 * sizeof(int), hipMemcpyHostToDevice, m->stream));
-    float *d_s = sdf, *d_w = weight;
-    uchar4 *d_c = reinterpret_cast<uchar4 *>(rgbw);
-    if (!on_device) {
-        HIP_TRY(hipMalloc(&st.sdf, rows * sizeof(float)));
-        HIP_TRY(hipMalloc(&st.wgt, rows * sizeof(float)));
-        if (color) HIP_TRY(hipMalloc(&st.col, rows * sizeof(uchar4)));
-        d_s = st.sdf; d_w = st.wgt; d_c = st.col;
-    }
-    hipLaunchKernelGGL(export_chunks_kernel, dim3(n), dim3(256), 0, m->stream, m->view, st.ids, m->V, d_s, d_w, color ? d_c : nullptr, st.flags);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(found, st.flags, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-    if (!on_device) {
-        HIP_TRY(hipMemcpyAsync(sdf, st.sdf, rows * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-        HIP_TRY(hipMemcpyAsync(weight, st.wgt, rows * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-        if (color) HIP_TRY(hipMemcpyAsync(rgbw, st.col, rows * sizeof(uchar4), hipMemcpyDeviceToHost, m->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    return CHISEL_HIP_OK;
-}
-
-int chisel_hip_import_ghost_chunks(chisel_hip_map *m, const int *ids, int n, const float *sdf, const float *weight, const uint8_t *rgbw,
-                                   const int *found, int on_device) {
-    SETTLE(m);
-    if (m && m->is_group) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "chisel_hip_import_ghost_chunks is a call between the shards of a map: a group makes it itself (chisel_hip_update_meshes)");
-    if (!m || n < 0 || (n > 0 && (!ids || !sdf || !weight))) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
-    if (n == 0) return CHISEL_HIP_OK;
-    HIP_TRY(hipSetDevice(m->device));
-    { m->topology_epoch++; m->dirty_tail_queued = false; }
-    int rc = check_mesh_totals(m);
-    if (rc) return rc;
-    rc = maybe_grow(m, n);  // (ghosts take slots of this shard's pool until they are dropped again)
-    if (rc) return rc;
-    for (int j = 0; j < n; j++)
-        if ((!found || found[j]) && chunk_owner(ids[3 * j], ids[3 * j + 1], ids[3 * j + 2], m->cfg.n_shards, m->cfg.shard_block) == m->cfg.shard_rank)
-            return fail(CHISEL_HIP_ERR_INVALID, "a ghost chunk must belong to another shard");
-    const size_t V = (size_t)m->V, rows = (size_t)n * V;
-    ChunkStage st;
-    HIP_TRY(hipMalloc(&st.ids, (size_t)n * 3 * sizeof(int)));
-    HIP_TRY(hipMemcpyAsync(st.ids, ids, (size_t)n * 3 * sizeof(int), hipMemcpyHostToDevice, m->stream));
-    if (found) {
-        HIP_TRY(hipMalloc(&st.flags, (size_t)n * sizeof(int)));
-        HIP_TRY(hipMemcpyAsync(st.flags, found, (size_t)n * sizeof(int), hipMemcpyHostToDevice, m->stream));
-    }
-    const float *d_s = sdf, *d_w = weight;
-    const uchar4 *d_c = reinterpret_cast<const uchar4 *>(rgbw);
-    if (!on_device) {
-        HIP_TRY(hipMalloc(&st.sdf, rows * sizeof(float)));
-        HIP_TRY(hipMalloc(&st.wgt, rows * sizeof(float)));
-        HIP_TRY(hipMemcpyAsync(st.sdf, sdf, rows * sizeof(float), hipMemcpyHostToDevice, m->stream));
-        HIP_TRY(hipMemcpyAsync(st.wgt, weight, rows * sizeof(float), hipMemcpyHostToDevice, m->stream));
-        if (rgbw) {
-            HIP_TRY(hipMalloc(&st.col, rows * sizeof(uchar4)));
-            HIP_TRY(hipMemcpyAsync(st.col, rgbw, rows * sizeof(uchar4), hipMemcpyHostToDevice, m->stream));
-        }
-        d_s = st.sdf; d_w = st.wgt; d_c = st.col;
-    }
-    hipLaunchKernelGGL(import_chunks_kernel, dim3(n), dim3(256), 0, m->stream, m->view, st.ids, found ? st.flags : nullptr, m->V, d_s, d_w, d_c);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    for (int j = 0; j < n; j++)
-        if (!found || found[j]) m->ghost_ids.insert(m->ghost_ids.end(), ids + 3 * j, ids + 3 * j + 3);
-    return check_device_error(m);
-}
-
 int chisel_hip_drop_ghost_chunks(chisel_hip_map *m) {
     SETTLE(m);
     if (m && m->is_group) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "chisel_hip_drop_ghost_chunks is a call between the shards of a map: a group makes it itself (chisel_hip_update_meshes)");
@@ -2726,53 +2631,8 @@ int chisel_hip_drop_ghost_chunks(chisel_hip_map *m) {
         m->ghost_packed = nullptr;
         m->ghost_packed_items = 0;
     }
-    if (m->ghost_ids.empty()) return CHISEL_HIP_OK;
-    HIP_TRY(hipSetDevice(m->device));
-    { m->topology_epoch++; m->dirty_tail_queued = false; }
-    int rc = check_mesh_totals(m);  // a recompute in flight may still read them
-    if (rc) return rc;
-    const int n = (int)(m->ghost_ids.size() / 3);
-    rc = ensure_scratch(m, (size_t)n * 3 + 16);
-    if (rc) return rc;
-    int *d_cnt = m->scratch_i, *d_ids = m->scratch_i + 16;
-    HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(int), m->stream));
-    HIP_TRY(hipMemcpyAsync(d_ids, m->ghost_ids.data(), (size_t)n * 3 * sizeof(int), hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(remove_chunks_kernel, dim3(n), dim3(256), 0, m->stream, m->view, d_ids, n, d_cnt, m->V);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(note_map_mutation(m));  // (stream-ordered; the next batch's front half waits for it -- nothing is waited for here)
-    m->ghost_ids.clear();
     return CHISEL_HIP_OK;
 }
-
-
-// ---- meshing a sharded map: shells (kernels_map.h) -------------------------------------------------------------------------------
-namespace {
-// items (x, y, z, box) and their payload offsets onto the device (the map's stream; staging buffers kept by the map)
-int stage_shell_items(chisel_hip_map *m, const int *items, int n, long long *total) {
-    if (n > m->shell_capacity) {
-        HIP_TRY(hipStreamSynchronize(m->stream));
-        if (m->shell_items_dev) HIP_TRY(hipFree(m->shell_items_dev));
-        if (m->shell_offs_dev) HIP_TRY(hipFree(m->shell_offs_dev));
-        m->shell_items_dev = nullptr;
-        m->shell_offs_dev = nullptr;
-        const int cap = std::max(4096, 2 * n);
-        HIP_TRY(hipMalloc(&m->shell_items_dev, (size_t)cap * 4 * sizeof(int)));
-        HIP_TRY(hipMalloc(&m->shell_offs_dev, (size_t)cap * sizeof(long long)));
-        m->shell_capacity = cap;
-    }
-    std::vector<long long> offs((size_t)n);
-    long long t = 0;
-    for (int j = 0; j < n; j++) {
-        if (items[4 * j + 3] < 0 || items[4 * j + 3] > 63) return fail(CHISEL_HIP_ERR_INVALID, "bad shell box code");
-        offs[(size_t)j] = t;
-        t += shell_volume(items[4 * j + 3], m->N);
-    }
-    *total = t;
-    HIP_TRY(hipMemcpyAsync(m->shell_items_dev, items, (size_t)n * 4 * sizeof(int), hipMemcpyHostToDevice, m->stream));
-    HIP_TRY(hipMemcpyAsync(m->shell_offs_dev, offs.data(), (size_t)n * sizeof(long long), hipMemcpyHostToDevice, m->stream));
-    return CHISEL_HIP_OK;
-}
-}  // namespace
 
 int chisel_hip_dirty_ids_device(chisel_hip_map *m, int *out_dev, int capacity) {
     SETTLE(m);
@@ -2801,114 +2661,6 @@ int chisel_hip_dirty_ids_device(chisel_hip_map *m, int *out_dev, int capacity) {
     else HIP_TRY(hipMemcpyAsync(out_dev, head.data(), head.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(list_dirty_ids_kernel, dim3(256), dim3(256), 0, m->stream, m->view, out_dev, capacity);
     HIP_TRY(hipGetLastError());
-    return CHISEL_HIP_OK;
-}
-
-int chisel_hip_export_shells(chisel_hip_map *m, const int *items, int n, float *sdf, float *weight, uint8_t *rgbw, int *found, int on_device) {
-    SETTLE(m);
-    if (m && m->is_group) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "a call between the shards of a map");
-    if (!m || n < 0 || (n > 0 && (!items || !sdf || !weight || !found))) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
-    if (n == 0) return CHISEL_HIP_OK;
-    HIP_TRY(hipSetDevice(m->device));
-    {
-        int rc_m = check_mesh_totals(m);
-        if (rc_m) return rc_m;
-    }
-    if (m->input_event) {  // chisel_hip_wait_event: the output buffers may be used from here on
-        HIP_TRY(hipStreamWaitEvent(m->stream, m->input_event, 0));
-        m->input_event = nullptr;
-    }
-    long long total = 0;
-    int rc = stage_shell_items(m, items, n, &total);
-    if (rc) return rc;
-    const bool color = m->view.rgbw && rgbw;
-    ChunkStage st;
-    float *d_s = sdf, *d_w = weight;
-    uchar4 *d_c = reinterpret_cast<uchar4 *>(rgbw);
-    int *d_f = found;
-    if (!on_device) {
-        HIP_TRY(hipMalloc(&st.sdf, (size_t)total * sizeof(float)));
-        HIP_TRY(hipMalloc(&st.wgt, (size_t)total * sizeof(float)));
-        if (color) HIP_TRY(hipMalloc(&st.col, (size_t)total * sizeof(uchar4)));
-        HIP_TRY(hipMalloc(&st.flags, (size_t)n * sizeof(int)));
-        d_s = st.sdf; d_w = st.wgt; d_c = st.col; d_f = st.flags;
-    }
-    hipLaunchKernelGGL(export_shells_kernel, dim3(n), dim3(256), 0, m->stream, m->view, m->shell_items_dev, m->shell_offs_dev, m->N, d_s, d_w, color ? d_c : nullptr, d_f);
-    HIP_TRY(hipGetLastError());
-    if (!on_device) {
-        HIP_TRY(hipMemcpyAsync(sdf, st.sdf, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-        HIP_TRY(hipMemcpyAsync(weight, st.wgt, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, m->stream));
-        if (color) HIP_TRY(hipMemcpyAsync(rgbw, st.col, (size_t)total * sizeof(uchar4), hipMemcpyDeviceToHost, m->stream));
-        HIP_TRY(hipMemcpyAsync(found, st.flags, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, m->stream));
-        HIP_TRY(hipStreamSynchronize(m->stream));
-    }
-    return CHISEL_HIP_OK;  // on_device: nothing has been waited for (chisel_hip_record_event orders the consumer)
-}
-
-int chisel_hip_import_ghost_shells(chisel_hip_map *m, const int *items, int n, const float *sdf, const float *weight, const uint8_t *rgbw,
-                                   const int *found, int on_device) {
-    SETTLE(m);
-    if (m && m->is_group) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "a call between the shards of a map");
-    if (!m || n < 0 || (n > 0 && (!items || !sdf || !weight || !found))) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
-    if (n == 0) return CHISEL_HIP_OK;
-    HIP_TRY(hipSetDevice(m->device));
-    { m->topology_epoch++; m->dirty_tail_queued = false; }
-    int rc = check_mesh_totals(m);
-    if (rc) return rc;
-    rc = maybe_grow(m, n);  // (ghosts take slots of this shard's pool until they are dropped again)
-    if (rc) return rc;
-    // the distinct ghosts (several boxes may belong to one), each with the item whose `found` decides whether it is created
-    std::unordered_set<uint64_t, IdHash> seen;
-    std::vector<int> first;
-    for (int j = 0; j < n; j++) {
-        if (chunk_owner(items[4 * j], items[4 * j + 1], items[4 * j + 2], m->cfg.n_shards, m->cfg.shard_block) == m->cfg.shard_rank)
-            return fail(CHISEL_HIP_ERR_INVALID, "a ghost chunk must belong to another shard");
-        if (seen.insert(pack_id(items[4 * j], items[4 * j + 1], items[4 * j + 2])).second) first.push_back(j);
-    }
-    if (m->input_event) {  // chisel_hip_wait_event: the payload arrives on another stream (the collective's)
-        HIP_TRY(hipStreamWaitEvent(m->stream, m->input_event, 0));
-        m->input_event = nullptr;
-    }
-    long long total = 0;
-    rc = stage_shell_items(m, items, n, &total);
-    if (rc) return rc;
-    ChunkStage st;
-    const float *d_s = sdf, *d_w = weight;
-    const uchar4 *d_c = reinterpret_cast<const uchar4 *>(rgbw);
-    const int *d_f = found;
-    if (!on_device) {
-        HIP_TRY(hipMalloc(&st.sdf, (size_t)total * sizeof(float)));
-        HIP_TRY(hipMalloc(&st.wgt, (size_t)total * sizeof(float)));
-        HIP_TRY(hipMalloc(&st.flags, (size_t)n * sizeof(int)));
-        HIP_TRY(hipMemcpyAsync(st.sdf, sdf, (size_t)total * sizeof(float), hipMemcpyHostToDevice, m->stream));
-        HIP_TRY(hipMemcpyAsync(st.wgt, weight, (size_t)total * sizeof(float), hipMemcpyHostToDevice, m->stream));
-        HIP_TRY(hipMemcpyAsync(st.flags, found, (size_t)n * sizeof(int), hipMemcpyHostToDevice, m->stream));
-        if (rgbw) {
-            HIP_TRY(hipMalloc(&st.col, (size_t)total * sizeof(uchar4)));
-            HIP_TRY(hipMemcpyAsync(st.col, rgbw, (size_t)total * sizeof(uchar4), hipMemcpyHostToDevice, m->stream));
-        }
-        d_s = st.sdf; d_w = st.wgt; d_c = st.col; d_f = st.flags;
-    }
-    // phase 1: one thread block per distinct ghost creates the chunk (distinct ids never collide); phase 2: every box is written.
-    // The list of first items travels through a staging buffer the map keeps (stream-ordered like the item list): nothing is
-    // allocated, freed or waited for here when the payload is already on the device.
-    if ((int)first.size() > m->shell_first_capacity) {
-        HIP_TRY(hipStreamSynchronize(m->stream));
-        if (m->shell_first_dev) HIP_TRY(hipFree(m->shell_first_dev));
-        m->shell_first_dev = nullptr;
-        const int cap = std::max(4096, 2 * (int)first.size());
-        HIP_TRY(hipMalloc(&m->shell_first_dev, (size_t)cap * sizeof(int)));
-        m->shell_first_capacity = cap;
-    }
-    HIP_TRY(hipMemcpyAsync(m->shell_first_dev, first.data(), first.size() * sizeof(int), hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL(ensure_ghosts_kernel, dim3((unsigned)first.size()), dim3(64), 0, m->stream, m->view, m->shell_items_dev, m->shell_first_dev, d_f);
-    hipLaunchKernelGGL(import_shells_kernel, dim3(n), dim3(256), 0, m->stream, m->view, m->shell_items_dev, m->shell_offs_dev, d_f, m->N, d_s, d_w, d_c);
-    HIP_TRY(hipGetLastError());
-    // every item may have become a ghost (which of them were resident at their owner is known on the device only): all are dropped
-    // again by chisel_hip_drop_ghost_chunks (removing an absent id does nothing)
-    for (int j = 0; j < n; j++) m->ghost_ids.insert(m->ghost_ids.end(), items + 4 * j, items + 4 * j + 3);
-    if (!on_device) HIP_TRY(hipStreamSynchronize(m->stream));  // (the staging buffers above are freed on return)
-    HIP_TRY(note_map_mutation(m));
     return CHISEL_HIP_OK;
 }
 

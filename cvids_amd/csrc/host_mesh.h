@@ -536,8 +536,8 @@ int chisel_hip_update_meshes(chisel_hip_map *m, int force) {
     if (!m) return fail(CHISEL_HIP_ERR_INVALID, "null map");
     if (m->cfg.n_shards > 1)
         return fail(CHISEL_HIP_ERR_UNSUPPORTED,
-                    "a shard cannot mesh on its own (its chunks' neighbours live on other shards): exchange them with chisel_hip_export_chunks / "
-                    "import_ghost_chunks and call chisel_hip_update_meshes_of (cvids_amd/sharded.py: ShardedChisel.UpdateMeshes)");
+                    "a shard cannot mesh on its own (its chunks' neighbours live on other shards): exchange them with chisel_hip_shell_plan_device / "
+                    "_export_shells_packed / _import_shells_packed and call chisel_hip_update_meshes_planned (cvids_amd/sharded.py: ShardedChisel.UpdateMeshes)");
     HIP_TRY(hipSetDevice(m->device));
     // Chisel.cpp:53-58: "static int cnt = 0; if (cnt++ % 10 == 0)" -- the recompute runs on every 10th call
     if (!force && (m->update_meshes_calls++ % 10) != 0) return CHISEL_HIP_OK;

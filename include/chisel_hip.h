@@ -43,8 +43,9 @@ extern "C" {
  *   2  round 5-6: chisel_hip_mesh_shell_plan_all removed, CHISEL_HIP_NUM_LAUNCH_STATS 8 -> 10, the device-plan and incremental
  *      meshesToUpdate entries added; later additions within 2 (nothing removed or re-typed): chisel_hip_pool_info,
  *      chisel_hip_frustum_from_vectors, chisel_hip_order_stream_after_map / _map_after_stream, the wait-free sharded recompute
- *      (chisel_hip_shell_plan_queue, _import_shells_fixed, _shell_commit), the stereo matcher (chisel_hip_stereo_*) */
-#define CHISEL_HIP_ABI_VERSION 2
+ *      (chisel_hip_shell_plan_queue, _import_shells_fixed, _shell_commit), the stereo matcher (chisel_hip_stereo_*)
+ *   3  chisel_hip_export_chunks, _import_ghost_chunks, _export_shells, _import_ghost_shells removed */
+#define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
 
@@ -250,20 +251,15 @@ int chisel_hip_write_mesh_ply(const char *path, const float *vertices, const flo
 
 /* ---- meshing a sharded map (SURVEY.md 8e "meshing across shards") -------------------------------------------------
  * A chunk's mesh reads its 26 neighbours (cube corners: ChunkManager.cpp:316-357; gradient normals and colours of border
- * vertices: :449-499, :588-607), most of which belong to other shards.  The owners export those chunks, the mesher
- * imports them as "ghost" chunks -- resident, never integrated (cull_kernel only takes chunks this shard owns) --
- * recomputes the meshes of its own chunks and drops the ghosts again.  cvids_amd/sharded.py orchestrates the exchange
- * (ShardedChisel.UpdateMeshes).  ids must not repeat within a call.  Buffers: [n][V] floats / [n][V][4] bytes, on the
- * host or (on_device != 0) in HBM on the map's device.
- *   export_chunks        voxels of n chunks (found[j] = 0 and default voxels for a chunk that is not resident)
- *   import_ghost_chunks  install the chunks with found[j] != 0 (found may be NULL = all) as ghosts
- *   drop_ghost_chunks    remove every ghost imported since the last drop
+ * vertices: :449-499, :588-607), most of which belong to other shards.  The owners send the parts of those chunks that
+ * are read, the mesher installs them as "ghost" chunks -- resident, never integrated (cull_kernel only takes chunks this
+ * shard owns) -- recomputes the meshes of its own chunks and drops the ghosts again.  cvids_amd/sharded.py orchestrates
+ * the exchange (ShardedChisel.UpdateMeshes) with the device plan and its wait-free form further down
+ * (chisel_hip_shell_plan_device, chisel_hip_shell_plan_queue).
+ *   drop_ghost_chunks    remove the ghosts of the latest chisel_hip_import_shells_packed / _import_shells_fixed (named by
+ *                        the items of the received segments, which must stay untouched until then)
  *   update_meshes_of     RecomputeMeshes (ChunkManager.cpp:130-169) for exactly these chunk ids -- the shard's share of
  *                        the union of all shards' meshesToUpdate -- then meshesToUpdate.clear() (Chisel.cpp:57) */
-int chisel_hip_export_chunks(chisel_hip_map *map, const int *ids_xyz, int n, float *sdf, float *weight, uint8_t *rgbw,
-                             int *found, int on_device);
-int chisel_hip_import_ghost_chunks(chisel_hip_map *map, const int *ids_xyz, int n, const float *sdf, const float *weight,
-                                   const uint8_t *rgbw, const int *found, int on_device);
 int chisel_hip_drop_ghost_chunks(chisel_hip_map *map);
 int chisel_hip_update_meshes_of(chisel_hip_map *map, const int *ids_xyz, int n);
 
@@ -432,20 +428,15 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
  * What a chunk's mesh reads of a neighbour chunk is a shell one or two voxels thick (cube corners, gradients around the vertices, the
  * nearest voxel's colour: SURVEY.md 8e's "faces"), not the whole chunk.  A "box code" names the part of a ghost chunk that travels:
  * two bits per axis (x: bits 0-1, y: 2-3, z: 4-5), 0 = every coordinate, 1 = {0, 1}, 2 = {N - 1}, 3 = {0, 1, N - 1}; chisel_hip_shell_volume gives its
- * number of voxels; the payload of a list of items (x, y, z, box) is the concatenation of their boxes in z, y, x order.
+ * number of voxels; the payload of an item (x, y, z, box) is its box in z, y, x order.
  *   chisel_hip_dirty_ids_device  the chunks updated since the last recompute as a DEVICE int array: out[0] = n, then n entries
  *                                (x, y, z, flag) -- flag 0: the chunk was updated (its 27-neighbourhood is meshesToUpdate, Chisel.h:175-189),
  *                                flag 1: an entry of meshesToUpdate kept on the host; nothing is waited for (record_event orders the
  *                                collective that gathers the ranks' arrays)
- *   chisel_hip_mesh_shell_plan   host arithmetic, identical on every rank: from the gathered entries the ids `rank` meshes (jobs) and
- *                                the ghosts it needs as items (owner, x, y, z, box) -- one or more boxes per ghost, ascending by owner, id, box;
- *                                chisel_hip_import_ghost_shells creates a ghost once, from its first item --,
- *                                every rank can evaluate it for every other rank, so the request lists need no exchange
- *   chisel_hip_export_shells     the boxes of the listed chunks of this shard, packed (device pointers with on_device: no wait);
- *                                found[j] = 0 and default voxels for a chunk that is not resident
- *   chisel_hip_import_ghost_shells  installs them as ghost chunks (only the box is written; honours chisel_hip_wait_event; with
- *                                on_device nothing is allocated or waited for: queued on the map's stream);
- *                                chisel_hip_drop_ghost_chunks removes them again (queued as well) */
+ *   chisel_hip_mesh_shell_plan   the host planner of rounds 3-4, kept as the independent check of the device plan below (tests/
+ *                                test_sharded_cpu.py); no entry point consumes its items.  Host arithmetic, identical on every rank:
+ *                                from the gathered entries the ids `rank` meshes (jobs) and the ghosts it needs as items
+ *                                (owner, x, y, z, box) -- one or more boxes per ghost, ascending by owner, id, box */
 int chisel_hip_dirty_ids_device(chisel_hip_map *map, int *out_dev, int capacity);
 int chisel_hip_mesh_shell_plan(const int *entries, int64_t n_entries, int n_shards, int rank, int shard_block, int *jobs, int64_t max_jobs,
                                int64_t *n_jobs, int *items, int64_t max_items, int64_t *n_items);
@@ -484,9 +475,6 @@ int chisel_hip_shell_plan_queue(chisel_hip_map *map, const int *gathered_dev, in
 int chisel_hip_import_shells_fixed(chisel_hip_map *map, const void *in_dev, int64_t seg_stride, const int *status_dev, int jobs_hint, int items_hint);
 int chisel_hip_shell_commit(chisel_hip_map *map, int aborted);
 int64_t chisel_hip_shell_volume(int box, int chunk_edge);
-int chisel_hip_export_shells(chisel_hip_map *map, const int *items, int n, float *sdf, float *weight, uint8_t *rgbw, int *found, int on_device);
-int chisel_hip_import_ghost_shells(chisel_hip_map *map, const int *items, int n, const float *sdf, const float *weight, const uint8_t *rgbw,
-                                   const int *found, int on_device);
 
 /* ---- measurement ------------------------------------------------------------------------------------ */
 /* accumulated since creation / last reset_counters; out has CHISEL_HIP_NUM_COUNTERS entries */

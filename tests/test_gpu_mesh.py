@@ -74,8 +74,9 @@ def test_mesh_chunk_sizes(oracle_mod, N, res, W, H):
 @pytest.mark.parametrize("wait_free", [False, True])
 @pytest.mark.parametrize("n_shards", [2, 4, 8])
 def test_sharded_map_meshes_equal_the_unsharded_map(oracle_mod, n_shards, wait_free):
-    """SURVEY.md 8e "meshing across shards": every shard meshes the chunks it owns with its neighbours' chunks imported as
-    ghosts (export_chunks / import_ghost_chunks / update_meshes_of / drop_ghost_chunks, cvids_amd/sharded.py).  The union
+    """SURVEY.md 8e "meshing across shards": every shard meshes the chunks it owns with the shells of its neighbours' chunks
+    installed as ghosts (the device plan and its wait-free form: shell_plan_device / export_shells_packed / import_shells_packed or
+    shell_plan_queue / import_shells_fixed, then update_meshes_planned / drop_ghost_chunks, cvids_amd/sharded.py).  The union
     of the shards' meshes equals the oracle's meshes of the whole map element for element, two recomputes in a row, and
     the ghosts leave no trace in the shards' chunk lists."""
     from cvids_amd import chisel as ch
