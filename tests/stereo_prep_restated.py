@@ -28,6 +28,7 @@ from oracle import publish_dense as pd
 f32 = np.float32
 WINDOW = 4                     # nWindowSize, sgm_stereo_mapper.cpp:240
 INT_MIN = -2 ** 31
+FIT_LIMIT = 2.0 ** 30          # kernels_stereo_prep.h: a point at or beyond it (or at NaN) does not fit an int and writes nothing
 
 
 def sobel_kernel(order, ksize):
@@ -200,7 +201,9 @@ def _ratio(u, v):
 def sparse_maps(depths, points, mask_x, mask_y, W, H, real_w, real_h):
     """Output's window loop (sgm_stereo_mapper.cpp:229-357), literally: -> (sparse depth, sparse distance) float32 (H, W).
     The masks are read at the flat index of the continuous map; outside [0, W * H) a read counts as 0 (the reference reads out of
-    its buffer there: undefined)."""
+    its buffer there: undefined).  A point whose position does not fit an int -- NaN, +-inf or |.| >= 2^30, before or after the
+    scale -- writes nothing: the reference's (int) of such a double is undefined, and the library's stated rule
+    (kernels_stereo_prep.h, the sparse prior's header comment) is the contract."""
     nScaleX = float(real_h) / float(H)     # sic: the x scale is the height ratio (:226-227)
     nScaleY = float(real_w) / float(W)
     mSparseDepth = np.full((H, W), -1.0, np.float32)
@@ -213,8 +216,13 @@ def sparse_maps(depths, points, mask_x, mask_y, W, H, real_w, real_h):
 
     for i in range(len(depths)):
         nDepth = float(depths[i])
-        nX = int(float(points[i][0]))
-        nY = int(float(points[i][1]))
+        fX, fY = float(points[i][0]), float(points[i][1])
+        if not (abs(fX) < FIT_LIMIT and abs(fY) < FIT_LIMIT):      # (false for NaN too)
+            continue
+        nX = int(fX)
+        nY = int(fY)
+        if not (abs(nX / nScaleX) < FIT_LIMIT and abs(nY / nScaleY) < FIT_LIMIT):
+            continue
         nX = int(nX / nScaleX)
         nY = int(nY / nScaleY)
         n = WINDOW
@@ -271,8 +279,13 @@ def sparse_maps_vectorised(depths, points, mask_x, mask_y, W, H, real_w, real_h)
     sd, sdist = np.full((H, W), -1.0, np.float32), np.zeros((H, W), np.float32)
     if len(depths) == 0:
         return sd, sdist
-    nX = np.trunc(np.trunc(pts[:, 0]) / (float(real_h) / float(H))).astype(np.int64)
-    nY = np.trunc(np.trunc(pts[:, 1]) / (float(real_w) / float(W))).astype(np.int64)
+    # the does-not-fit-an-int rule, before any cast: such a point is parked at the origin here and skipped in the replay below
+    fits = (np.abs(pts[:, 0]) < FIT_LIMIT) & (np.abs(pts[:, 1]) < FIT_LIMIT)      # (false for NaN too)
+    pts = np.where(fits[:, None], pts, 0.0)
+    qx, qy = np.trunc(pts[:, 0]) / (float(real_h) / float(H)), np.trunc(pts[:, 1]) / (float(real_w) / float(W))
+    fits &= (np.abs(qx) < FIT_LIMIT) & (np.abs(qy) < FIT_LIMIT)
+    nX = np.trunc(np.where(fits, qx, 0.0)).astype(np.int64)
+    nY = np.trunc(np.where(fits, qy, 0.0)).astype(np.int64)
     off = np.arange(-n, n + 1)
     # masks at [point, us, vs]
     k = (nY[:, None, None] + off[None, None, :]) * W + (nX[:, None, None] + off[None, :, None])
@@ -300,7 +313,7 @@ def sparse_maps_vectorised(depths, points, mask_x, mask_y, W, H, real_w, real_h)
     U, V = np.meshgrid(off, off, indexing="ij")                    # [u, v]
     ratio = np.array([[_ratio(int(u), int(v)) for v in off] for u in off])
     stored = (ratio * ratio).astype(np.float32)
-    for i in range(len(depths)):
+    for i in np.flatnonzero(fits):
         px, py = nX[i] + U, nY[i] + V
         allowed = ((py < H - 1) & (py >= 1) & (px < W - 1) & (px >= 1) & (U >= left[i][V + n]) & (U <= right[i][V + n]) &
                    (V >= bottom[i][U + n]) & (V <= up[i][U + n]))
