@@ -62,6 +62,12 @@ class StereoParams(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("pi1", "pi2", "tau_so", "sgm_q1", "sgm_q2", "var_scale", "sparse_ratio", "dep_sample")]
 
 
+class View(C.Structure):
+    """chisel_hip_view (include/chisel_hip.h): the camera of chisel_hip_render_view"""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("pose", C.c_float * 12), ("fx", C.c_float), ("fy", C.c_float),
+                ("cx", C.c_float), ("cy", C.c_float), ("near_plane", C.c_float), ("far_plane", C.c_float), ("step", C.c_float)]
+
+
 EXPORTS = [
     "chisel_hip_abi_version", "chisel_hip_last_error", "chisel_hip_device_count", "chisel_hip_host_alloc", "chisel_hip_host_free", "chisel_hip_create",
     "chisel_hip_destroy", "chisel_hip_reset", "chisel_hip_set_integrator", "chisel_hip_set_stream",
@@ -78,7 +84,7 @@ EXPORTS = [
     "chisel_hip_stereo_set_camera", "chisel_hip_stereo_set_reference_image", "chisel_hip_stereo_update_image",
     "chisel_hip_stereo_bind_sparse_points", "chisel_hip_stereo_output_image", "chisel_hip_stereo_homography",
     "chisel_hip_get_counters", "chisel_hip_memory_statistics", "chisel_hip_topology_epoch", "chisel_hip_candidates", "chisel_hip_cloud_candidates", "chisel_hip_mesh_cube", "chisel_hip_write_mesh_ply", "chisel_hip_shade_vertices", "chisel_hip_generate_mesh", "chisel_hip_recompute_mesh", "chisel_hip_integrate_chunk", "chisel_hip_dirty_ids_device", "chisel_hip_mesh_shell_plan",
-    "chisel_hip_shell_volume", "chisel_hip_set_profiling", "chisel_hip_get_profile", "chisel_hip_get_launch_stats", "chisel_hip_pool_info", "chisel_hip_mc_tables", "chisel_hip_mesh_cube_values", "chisel_hip_interpolate_vertex", "chisel_hip_raycast", "chisel_hip_chunk_owner", "chisel_hip_frustum", "chisel_hip_frustum_from_vectors", "chisel_hip_create_group",
+    "chisel_hip_shell_volume", "chisel_hip_set_profiling", "chisel_hip_get_profile", "chisel_hip_get_launch_stats", "chisel_hip_pool_info", "chisel_hip_mc_tables", "chisel_hip_mesh_cube_values", "chisel_hip_interpolate_vertex", "chisel_hip_raycast", "chisel_hip_chunk_owner", "chisel_hip_frustum", "chisel_hip_frustum_from_vectors", "chisel_hip_create_group", "chisel_hip_render_view",
 ]
 # the device self-tests and debug read-outs include/chisel_hip_selftest.h declares
 SELFTEST_EXPORTS = [
@@ -214,6 +220,7 @@ def load_library():
         L.chisel_hip_generate_mesh.argtypes = [vp, i32p, C.c_int, C.c_int64, C.c_int64, f32p, f32p, f32p, f32p, i64p, i64p]
     if hasattr(L, "chisel_hip_memory_statistics"):
         L.chisel_hip_memory_statistics.argtypes = [vp, C.POINTER(Statistics)]
+    L.chisel_hip_render_view.argtypes = [vp, C.POINTER(View), vp, vp, vp, C.c_int]
     L.chisel_hip_get_profile.argtypes = [vp, C.POINTER(C.c_double), i64p, C.c_int]
     L.chisel_hip_get_launch_stats.argtypes = [vp, i64p, C.c_int]
     L.chisel_hip_pool_info.argtypes = [vp, i64p]

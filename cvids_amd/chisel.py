@@ -459,6 +459,31 @@ class Chisel:
         check(self.L.chisel_hip_get_sdf_and_gradient(self.h, p, C.byref(d), g, C.byref(found)))
         return bool(found.value), d.value, np.array(list(g), np.float32)
 
+    def RenderView(self, extrinsic, camera, step=0.0, normals=False, colors=False, out=None):
+        """chisel_hip_render_view: what the map holds as `camera` at the camera->world pose `extrinsic` sees it (the pair
+        IntegrateDepthScan takes); step: z-distance between two samples of a ray, <= 0 = the voxel resolution.
+        -> {"depth": (H, W), "normals": (H, W, 3) or None, "colors": (H, W, 3) or None}, float32 numpy arrays with NaN where
+        the ray hits nothing.  `out`: a dict of float32 torch CUDA tensors of those shapes ("depth" required) to fill in place on
+        the map's stream, nothing waited for; it is returned."""
+        H, W = camera.height, camera.width
+        v = capi.View(W, H, _pose12(extrinsic), camera.fx, camera.fy, camera.cx, camera.cy, camera.near_plane, camera.far_plane,
+                      float(step))
+        if out is not None:
+            import torch
+            for name, t in out.items():
+                want = (H, W) if name == "depth" else (H, W, 3)
+                assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == want), \
+                    "out[%r]: a contiguous float32 CUDA tensor of shape %s" % (name, want)
+            ptr = lambda t: t.data_ptr() if t is not None else None
+            check(self.L.chisel_hip_render_view(self.h, C.byref(v), ptr(out["depth"]), ptr(out.get("normals")), ptr(out.get("colors")), 1))
+            self._keep = [out]
+            return out
+        res = {"depth": np.empty((H, W), np.float32), "normals": np.empty((H, W, 3), np.float32) if normals else None,
+               "colors": np.empty((H, W, 3), np.float32) if colors else None}
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        check(self.L.chisel_hip_render_view(self.h, C.byref(v), ptr(res["depth"]), ptr(res["normals"]), ptr(res["colors"]), 0))
+        return res
+
     def MemoryStatistics(self):
         """ChunkManager::PrintMemoryStatistics (ChunkManager.cpp:641-678) as numbers: the voxel census of Chunk::ComputeStatistics over
         the resident chunks, the weight sum, the bounds of the chunk boxes and the two memory figures the reference prints (it

@@ -34,6 +34,7 @@
 #include "kernels_integrate.h"
 #include "kernels_map.h"
 #include "kernels_mesh.h"
+#include "kernels_render.h"
 #include "kernels_cloud.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
@@ -3543,6 +3544,55 @@ int chisel_hip_shade_vertices(chisel_hip_map *m, const float *vertices, int64_t 
     if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
     (void)hipFree(d);
     if (e != hipSuccess) return fail(CHISEL_HIP_ERR_HIP, std::string("chisel_hip_shade_vertices: ") + hipGetErrorString(e));
+    return CHISEL_HIP_OK;
+}
+
+// One ray march per pixel over the voxels as they are (kernels_render.h; DESIGN.md "Rendering a view"): the map is only read.
+int chisel_hip_render_view(chisel_hip_map *m, const chisel_hip_view *view, float *depth, float *normals, float *colors, int on_device) {
+    SETTLE(m);
+    if (m && m->is_group) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "chisel_hip_render_view marches every ray through the voxels of all owners: a group's shards hold a part each (render a map of one shard)");
+    if (!m || !view || !depth) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
+    if (m->cfg.n_shards > 1) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "chisel_hip_render_view marches every ray through the voxels of all owners: this map is one shard of several");
+    if (view->width < 1 || view->height < 1) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_render_view: non-positive image size");
+    if (colors && !m->view.rgbw) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_render_view: colours asked of a map without colour voxels");
+    RenderCamera cam;
+    memcpy(cam.pose, view->pose, sizeof(cam.pose));
+    cam.fx = view->fx; cam.fy = view->fy; cam.cx = view->cx; cam.cy = view->cy;
+    cam.near_plane = view->near_plane;
+    cam.step = view->step > 0.0f ? view->step : m->cfg.voxel_resolution;
+    cam.width = view->width; cam.height = view->height;
+    const float last = floorf((view->far_plane - view->near_plane) / cam.step);  // K = (int)floorf((far - near) / step) + 1
+    if (!(last >= 0.0f) || last > (float)(RENDER_MAX_SAMPLES - 1)) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_render_view: (far - near) / step gives less than 1 or more than 65536 samples per ray");
+    cam.n_samples = (int)last + 1;
+    HIP_TRY(hipSetDevice(m->device));
+    {
+        int rc_m = check_mesh_totals(m);
+        if (rc_m) return rc_m;
+    }
+    const size_t px = (size_t)view->width * view->height;
+    float *d = nullptr, *dd = depth, *dn = normals, *dc = colors;
+    if (!on_device) {
+        HIP_TRY(hipMalloc(&d, 7 * px * sizeof(float)));
+        dd = d;
+        dn = normals ? d + px : nullptr;
+        dc = colors ? d + 4 * px : nullptr;
+    }
+    const MeshParams P = mesh_params(m);
+    const dim3 grid((unsigned)((view->width + 15) / 16), (unsigned)((view->height + 15) / 16));
+    switch (m->N) {
+        case 8: hipLaunchKernelGGL(render_view_kernel<8>, grid, dim3(256), 0, m->stream, m->view, P, cam, dd, dn, dc); break;
+        case 16: hipLaunchKernelGGL(render_view_kernel<16>, grid, dim3(256), 0, m->stream, m->view, P, cam, dd, dn, dc); break;
+        case 32: hipLaunchKernelGGL(render_view_kernel<32>, grid, dim3(256), 0, m->stream, m->view, P, cam, dd, dn, dc); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (!on_device) {  // (device outputs are left on the map's stream: nothing is waited for)
+        if (e == hipSuccess) e = hipMemcpyAsync(depth, dd, px * sizeof(float), hipMemcpyDeviceToHost, m->stream);
+        if (e == hipSuccess && normals) e = hipMemcpyAsync(normals, dn, 3 * px * sizeof(float), hipMemcpyDeviceToHost, m->stream);
+        if (e == hipSuccess && colors) e = hipMemcpyAsync(colors, dc, 3 * px * sizeof(float), hipMemcpyDeviceToHost, m->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+        (void)hipFree(d);
+    }
+    if (e != hipSuccess) return fail(CHISEL_HIP_ERR_HIP, std::string("chisel_hip_render_view: ") + hipGetErrorString(e));
     return CHISEL_HIP_OK;
 }
 

@@ -44,7 +44,8 @@ extern "C" {
  *      meshesToUpdate entries added; later additions within 2 (nothing removed or re-typed): chisel_hip_pool_info,
  *      chisel_hip_frustum_from_vectors, chisel_hip_order_stream_after_map / _map_after_stream, the wait-free sharded recompute
  *      (chisel_hip_shell_plan_queue, _import_shells_fixed, _shell_commit), the stereo matcher (chisel_hip_stereo_*)
- *   3  chisel_hip_export_chunks, _import_ghost_chunks, _export_shells, _import_ghost_shells removed */
+ *   3  chisel_hip_export_chunks, _import_ghost_chunks, _export_shells, _import_ghost_shells removed; later additions within 3 (nothing
+ *      removed or re-typed): chisel_hip_render_view */
 #define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -511,6 +512,26 @@ int chisel_hip_cloud_candidates(chisel_hip_map *map, const chisel_hip_pointcloud
  * lookup of its vertex succeeds, kept otherwise) and ChunkManager::ColorizeMesh / InterpolateColor (:628-639, :501-573; stages bit 1)
  * for a caller's own vertex list (host arrays of 3 n floats). */
 int chisel_hip_shade_vertices(chisel_hip_map *map, const float *vertices, int64_t n, float *normals, float *colors, int stages);
+/* A camera for chisel_hip_render_view: pose and intrinsics as in chisel_hip_depth_frame, and the spacing of the samples along the
+ * optical axis. */
+typedef struct {
+    int width, height;
+    float pose[12];          /* camera -> world, row-major 3 x 4                                         */
+    float fx, fy, cx, cy;
+    float near_plane, far_plane;
+    float step;              /* z-distance between two samples of a ray [m]; <= 0: the map's voxel resolution */
+} chisel_hip_view;          /* 84 bytes */
+/* Not in the reference: what the map holds as a camera at `view` sees it.  Pixel (col, row) looks along the ray through (col + 0.5,
+ * row + 0.5) and takes K = floor((far - near) / step) + 1 samples ChunkManager::GetSDF (nearest voxel) at the z-depths near + k step;
+ * its depth is where the distance changes from positive to <= 0 between two consecutive observed samples, interpolated linearly, as
+ * z-depth along the optical axis (what DepthImage holds: the image can go straight into chisel_hip_integrate_depth of another map).
+ * normals / colors (each 3 floats per pixel, or NULL): ChunkManager::ComputeNormalsFromGradients' normal and InterpolateColor's colour
+ * at the hit point, as chisel_hip_shade_vertices gives them.  A pixel without a hit -- nothing observed along the ray, or the ray comes
+ * up behind a surface -- is NaN in all three; so is the normal where the gradient lookup fails.  DESIGN.md "Rendering a view" has the
+ * definition to the bit.  The map is only read.  on_device: the outputs are device pointers, filled on the map's stream without a wait;
+ * otherwise host arrays, complete on return.  CHISEL_HIP_ERR_INVALID: colors on a map without colour voxels, K < 1 or K > 65536, a
+ * non-positive size; CHISEL_HIP_ERR_UNSUPPORTED: a group or one shard of several (a ray needs every owner's voxels). */
+int chisel_hip_render_view(chisel_hip_map *map, const chisel_hip_view *view, float *depth, float *normals, float *colors, int on_device);
 /* ProjectionIntegrator::Integrate<DataType>(depthImage, camera, cameraPose, chunk) / IntegrateColor (ProjectionIntegrator.h:51-52,
  * :101-102): ONE frame into ONE resident chunk -- whether or not the frustum's id range holds it, as the reference's per-chunk call
  * knows nothing of frusta --; color may be NULL (the depth-only update rule).  *updated = the call's return value there ("some voxel

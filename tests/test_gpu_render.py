@@ -1,0 +1,305 @@
+"""chisel_hip_render_view on the GPU against its definition (DESIGN.md "Rendering a view").
+
+Depth is compared BIT FOR BIT, every pixel, with tests/render_restated.py run over the map as GetChunkIDs / GetChunk read it back:
+the kernel's chunk-slot cache, its jumps over absent chunks and its batched loads must not show.  Normals and colours are held to
+chisel_hip_shade_vertices at the hit points.  The rest: the map is only read, host and device outputs agree, a rendered depth image
+is a valid input of IntegrateDepthScan, and the error codes."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from cvids_amd import synth
+from tests import render_restated as rr
+from tests.common import compare_fields
+
+pytestmark = pytest.mark.gpu
+W, H = 160, 120
+NEAR, FAR = 0.05, 5.0
+KINDS = {"constant": 0, "inverse": 1, "quadratic": 2}
+
+
+def camera(w=W, h=H, near=NEAR, far=FAR):
+    from cvids_amd.chisel import PinholeCamera
+    return PinholeCamera(*synth.intrinsics(w, h), w, h, near, far)
+
+
+def integrator(trunc, carving=True):
+    from cvids_amd import chisel as ch
+    cls = {"constant": ch.ConstantTruncator, "inverse": ch.InverseTruncator, "quadratic": ch.QuadraticTruncator}[trunc[0]]
+    return ch.ProjectionIntegrator(cls(trunc[1]), ch.ConstantWeighter(1.0), 0.05, carving)
+
+
+def gpu_map(scene, N, res, trunc, n_frames, carving=True, color=False, nan_fraction=0.0, max_chunks=8192):
+    from cvids_amd import chisel as ch
+    gm = ch.Chisel((N, N, N), res, color, max_chunks=max_chunks)
+    integ, cam = integrator(trunc, carving), camera()
+    img = synth.render_color(W, H, 3)
+    for depth, pose in synth.stream(scene, n_frames, W, H, nan_fraction=nan_fraction):
+        if color:
+            gm.IntegrateDepthScanColor(integ, depth, pose, cam, img, pose, cam)
+        else:
+            gm.IntegrateDepthScan(integ, depth, pose, cam)
+    return gm
+
+
+def same_bits(got, want, what):
+    """NaN masks equal, uint32 views equal elsewhere, no pixel left out"""
+    assert got.shape == want.shape and got.dtype == want.dtype == np.float32
+    gn, wn = np.isnan(got), np.isnan(want)
+    assert np.array_equal(gn, wn), "%s: NaN masks differ at %d places" % (what, int((gn != wn).sum()))
+    g, w = got.view(np.uint32)[~gn], want.view(np.uint32)[~wn]
+    assert np.array_equal(g, w), "%s: %d of %d values differ in their bits (max |d| %g)" % (
+        what, int((g != w).sum()), g.size, float(np.abs(got[~gn].astype(np.float64) - want[~wn].astype(np.float64)).max()))
+
+
+def check_depth(gm, index, pose, cam, step, what):
+    got = gm.RenderView(pose, cam, step=step)["depth"]
+    want = rr.render_depth(index, pose, (cam.fx, cam.fy, cam.cx, cam.cy), cam.width, cam.height, cam.near_plane, cam.far_plane, step)
+    same_bits(got, want, what)
+    return got
+
+
+def index_of(gm):
+    return rr.VoxelIndex(gm.fields(), gm.chunk_size[0], gm.voxel_resolution)
+
+
+# scene, chunk edge, resolution, truncator, frames, carving, colour voxels, pose rendered
+MAPS = [
+    ("sphere_room", 16, 0.02, ("inverse", 2.0), 8, True, False, 4),
+    ("sphere_room", 8, 0.03, ("quadratic", 1.0), 6, False, True, 3),
+    ("box_room", 8, 0.03, ("constant", 0.1), 6, True, True, 3),
+    ("box_room", 32, 0.02, ("inverse", 2.0), 7, False, False, 4),
+    ("wall", 32, 0.01, ("quadratic", 1.0), 6, True, True, 4),
+    ("wall", 16, 0.03, ("constant", 0.1), 8, False, False, 3),
+]
+
+
+@pytest.mark.parametrize("scene,N,res,trunc,n_frames,carving,color,pose_k", MAPS)
+def test_depth_bit_for_bit(scene, N, res, trunc, n_frames, carving, color, pose_k):
+    """a step of one voxel and of half a voxel, the full image and one whose tiles hang over it (77 x 53), the view the map was built
+    from and pose 20, which looks past what was observed"""
+    gm = gpu_map(scene, N, res, trunc, n_frames, carving, color)
+    index = index_of(gm)
+    pose = synth.trajectory_pose(pose_k)
+    d = check_depth(gm, index, pose, camera(), 0.0, "one voxel")
+    assert np.isfinite(d).mean() >= 0.99
+    check_depth(gm, index, pose, camera(), res / 2, "half a voxel")
+    check_depth(gm, index, pose, camera(77, 53), 0.0, "77 x 53")
+    d = check_depth(gm, index, synth.trajectory_pose(20), camera(), 0.0, "pose 20")
+    assert 0.3 < np.isfinite(d).mean() < 1.0  # partly outside what the frames observed
+
+
+def test_depth_bit_for_bit_640x480():
+    gm = gpu_map("sphere_room", 16, 0.02, ("inverse", 2.0), 8)
+    d = check_depth(gm, index_of(gm), synth.trajectory_pose(4), camera(640, 480), 0.0, "640 x 480")
+    assert np.isfinite(d).mean() >= 0.99
+
+
+def test_views_without_a_hit():
+    gm = gpu_map("sphere_room", 16, 0.02, ("inverse", 2.0), 8)
+    index = index_of(gm)
+    for name, (pose, far) in rr.no_hit_views().items():
+        for step in (0.0, 0.01):
+            d = check_depth(gm, index, pose, camera(far=far), step, name)
+            assert np.isnan(d).all(), name
+
+
+def test_depth_after_garbage_collect_reset_and_nan_frames():
+    trunc = ("inverse", 2.0)
+    pose, cam = synth.trajectory_pose(4), camera()
+    # every third chunk removed: absent chunks in front of, between and behind resident ones
+    gm = gpu_map("sphere_room", 16, 0.02, trunc, 8)
+    ids = gm.GetChunkIDs()
+    ids = ids[np.lexsort((ids[:, 2], ids[:, 1], ids[:, 0]))]
+    gm.GarbageCollect(ids[::3])
+    assert gm.NumChunks() == len(ids) - len(ids[::3])
+    for step in (0.0, 0.01):
+        d = check_depth(gm, index_of(gm), pose, cam, step, "after GarbageCollect")
+        assert 0.05 < np.isfinite(d).mean() < 0.99
+    check_depth(gm, index_of(gm), synth.trajectory_pose(20), cam, 0.0, "after GarbageCollect, pose 20")
+    # Reset: an empty map renders nothing; three frames later it renders them
+    gm.Reset()
+    assert np.isnan(gm.RenderView(pose, cam)["depth"]).all()
+    integ = integrator(trunc)
+    for depth, p in synth.stream("sphere_room", 3, W, H, start=2):
+        gm.IntegrateDepthScan(integ, depth, p, cam)
+    d = check_depth(gm, index_of(gm), pose, cam, 0.0, "after Reset")
+    assert np.isfinite(d).mean() > 0.9
+    # frames with 2 % invalid pixels
+    gm = gpu_map("box_room", 8, 0.03, ("constant", 0.1), 6, nan_fraction=0.02)
+    check_depth(gm, index_of(gm), synth.trajectory_pose(3), cam, 0.0, "2 % NaN")
+
+
+def shade(gm, points, normals_in):
+    """chisel_hip_shade_vertices (both stages) at `points`; normals prefilled with `normals_in`"""
+    from cvids_amd import capi
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    v = np.ascontiguousarray(points, np.float32)
+    n = np.ascontiguousarray(normals_in, np.float32).copy()
+    c = np.full_like(v, np.nan)
+    capi.check(gm.L.chisel_hip_shade_vertices(gm.h, fp(v), len(v), fp(n), fp(c) if gm.use_color else None, 3 if gm.use_color else 1))
+    return n, c
+
+
+@pytest.mark.parametrize("scene,N,res,trunc,n_frames,carving,color,pose_k", [m for m in MAPS if m[6]] + [MAPS[0]])
+def test_normals_and_colours_equal_shade_vertices_at_the_hit_points(scene, N, res, trunc, n_frames, carving, color, pose_k):
+    gm = gpu_map(scene, N, res, trunc, n_frames, carving, color)
+    cam = camera()
+    for k in (pose_k, 20):
+        pose = synth.trajectory_pose(k)
+        out = gm.RenderView(pose, cam, normals=True, colors=color)
+        depth = out["depth"]
+        same_bits(depth, gm.RenderView(pose, cam)["depth"], "depth with and without shading")
+        hit = np.isfinite(depth).reshape(-1)
+        assert hit.any() and (k != 20 or not hit.all())
+        p = rr.hit_points(pose, (cam.fx, cam.fy, cam.cx, cam.cy), depth)
+        want_n = np.full((W * H, 3), np.nan, np.float32)
+        want_c = np.full((W * H, 3), np.nan, np.float32)
+        n, c = shade(gm, p[hit], want_n[hit])
+        want_n[hit] = n
+        want_c[hit] = c
+        same_bits(out["normals"].reshape(-1, 3), want_n, "normals")
+        assert np.isfinite(out["normals"].reshape(-1, 3)[hit]).all(axis=1).mean() > 0.9
+        if color:
+            same_bits(out["colors"].reshape(-1, 3), want_c, "colours")
+            assert np.isfinite(out["colors"].reshape(-1, 3)[hit]).all()
+        else:
+            assert out["colors"] is None
+
+
+def mesh_state(gm):
+    return {tuple(int(v) for v in cid): gm.GetMesh(cid) for cid in gm.GetMeshIDs()}
+
+
+def test_rendering_only_reads_the_map():
+    """two maps fed the same frames, one of them rendered from in between: voxels, counters, meshesToUpdate and the meshes of a
+    later UpdateMeshes are identical"""
+    import torch
+    args = ("sphere_room", 16, 0.03, ("inverse", 2.0), 6, True, True)
+    a, b = gpu_map(*args), gpu_map(*args)
+    cam = camera()
+    dev = torch.device("cuda:0")
+    out = {"depth": torch.empty((H, W), dtype=torch.float32, device=dev), "normals": torch.empty((H, W, 3), dtype=torch.float32, device=dev),
+           "colors": torch.empty((H, W, 3), dtype=torch.float32, device=dev)}
+    for k in (4, 20):
+        a.RenderView(synth.trajectory_pose(k), cam, normals=True, colors=True)
+        a.RenderView(synth.trajectory_pose(k), cam, step=0.01, out=out)
+    for name, (pose, far) in rr.no_hit_views().items():
+        a.RenderView(pose, camera(far=far))
+    a.synchronize()
+    assert a.counters() == b.counters()
+    assert sorted(map(tuple, a.GetMeshesToUpdate().tolist())) == sorted(map(tuple, b.GetMeshesToUpdate().tolist()))
+    assert a.NumChunks() == b.NumChunks()
+    compare_fields(b.fields(), a.fields(), a.V, True)
+    a.UpdateMeshes()
+    b.UpdateMeshes()
+    a.RenderView(synth.trajectory_pose(4), cam)
+    ma, mb = mesh_state(a), mesh_state(b)
+    assert set(ma) == set(mb) and len(ma) > 10
+    for cid in ma:
+        for key in ("vertices", "normals", "colors", "grids"):
+            assert ma[cid][key].tobytes() == mb[cid][key].tobytes(), (cid, key)
+    assert a.GetMeshesToUpdate().tolist() == b.GetMeshesToUpdate().tolist()
+
+
+def test_render_between_two_launch_sets_of_a_pipelined_stream():
+    """device frames, nothing waited for: IntegrateBatch, RenderView into device tensors, IntegrateBatch.  The image is the one of the
+    map after the first batch, and the final map is the one of the same stream without the rendering."""
+    import torch
+    from cvids_amd import chisel as ch
+    N, res, trunc = 16, 0.03, ("inverse", 2.0)
+    cam, integ = camera(), integrator(trunc)
+    frames = list(synth.stream("sphere_room", 8, W, H))
+    dev = torch.device("cuda:0")
+    d_dev = [torch.from_numpy(d).to(dev) for d, _ in frames]
+    torch.cuda.synchronize()
+    pose = synth.trajectory_pose(4)
+    out = {"depth": torch.full((H, W), 7.0, dtype=torch.float32, device=dev)}
+    torch.cuda.synchronize()
+    a, b, c = (ch.Chisel((N, N, N), res, False, max_chunks=8192) for _ in range(3))
+    a.IntegrateBatch(integ, [(d_dev[i], frames[i][1], cam) for i in range(4)])
+    a.RenderView(pose, cam, out=out)
+    a.IntegrateBatch(integ, [(d_dev[i], frames[i][1], cam) for i in range(4, 8)])
+    b.IntegrateBatch(integ, [(d_dev[i], frames[i][1], cam) for i in range(4)])
+    b.IntegrateBatch(integ, [(d_dev[i], frames[i][1], cam) for i in range(4, 8)])
+    c.IntegrateBatch(integ, [(d_dev[i], frames[i][1], cam) for i in range(4)])
+    a.synchronize()
+    mid = out["depth"].cpu().numpy()
+    same_bits(mid, c.RenderView(pose, cam)["depth"], "the image between the launch sets")
+    same_bits(mid, rr.render_depth(index_of(c), pose, (cam.fx, cam.fy, cam.cx, cam.cy), W, H, NEAR, FAR), "... against the restatement")
+    assert np.isfinite(mid).mean() > 0.9
+    assert a.NumChunks() == b.NumChunks()
+    compare_fields(b.fields(), a.fields(), a.V, False)
+    assert a.counters() == b.counters()
+
+
+def test_host_and_device_outputs_are_equal():
+    import torch
+    gm = gpu_map("box_room", 8, 0.03, ("constant", 0.1), 6, True, True)
+    cam, pose = camera(77, 53), synth.trajectory_pose(20)
+    host = gm.RenderView(pose, cam, normals=True, colors=True)
+    dev = torch.device("cuda:0")
+    out = {"depth": torch.zeros((53, 77), dtype=torch.float32, device=dev), "normals": torch.zeros((53, 77, 3), dtype=torch.float32, device=dev),
+           "colors": torch.zeros((53, 77, 3), dtype=torch.float32, device=dev)}
+    torch.cuda.synchronize()
+    assert gm.RenderView(pose, cam, out=out) is out
+    gm.synchronize()
+    for key in ("depth", "normals", "colors"):
+        same_bits(out[key].cpu().numpy(), host[key], key)
+    # depth alone into a device tensor: the other two are left out
+    only = {"depth": torch.zeros((53, 77), dtype=torch.float32, device=dev)}
+    torch.cuda.synchronize()
+    gm.RenderView(pose, cam, out=only)
+    gm.synchronize()
+    same_bits(only["depth"].cpu().numpy(), host["depth"], "depth alone")
+
+
+def test_round_trip_into_integrate_depth_scan(oracle_mod):
+    """a rendered depth image (z-depth, NaN = invalid: what DepthImage holds) integrated into a fresh map gives the voxels the oracle
+    gives for the same array"""
+    from cvids_amd import chisel as ch
+    gm = gpu_map("sphere_room", 16, 0.02, ("inverse", 2.0), 8)
+    cam, intr = camera(), synth.intrinsics(W, H)
+    N, res = 16, 0.04
+    om = oracle_mod.OracleMap(N, res, False)
+    om.set_integrator(KINDS["inverse"], 2.0, 1.0, True, 0.05)
+    fresh = ch.Chisel((N, N, N), res, False, max_chunks=8192)
+    integ = integrator(("inverse", 2.0))
+    for k in (4, 20):
+        pose = synth.trajectory_pose(k)
+        depth = gm.RenderView(pose, cam)["depth"]
+        assert np.isfinite(depth).any() and (k != 20 or np.isnan(depth).any())
+        om.integrate_depth(depth, pose, intr, NEAR, FAR)
+        fresh.IntegrateDepthScan(integ, depth, pose, cam)
+    assert om.num_chunks() == fresh.NumChunks() > 10
+    compare_fields(om.fields(), fresh.fields(), om.V, False)
+
+
+def test_errors():
+    from cvids_amd import capi
+    from cvids_amd import chisel as ch
+    L = capi.load_library()
+    cam, pose = camera(), synth.trajectory_pose(0)
+
+    def refused(gm, code, *args, **kw):
+        with pytest.raises(capi.ChiselHipError) as e:
+            gm.RenderView(*args, **kw)
+        assert e.value.code == code, e.value
+        msg = L.chisel_hip_last_error().decode()
+        assert msg and msg in str(e.value)
+        return msg
+
+    plain = gpu_map("sphere_room", 16, 0.04, ("inverse", 2.0), 2)
+    assert "colour" in refused(plain, 1, pose, cam, colors=True)                   # no colour voxels
+    assert "samples" in refused(plain, 1, pose, cam, step=1e-5)                     # K > 65536
+    assert "samples" in refused(plain, 1, pose, camera(near=2.0, far=1.0))          # K < 1
+    refused(plain, 1, pose, camera(0, 10))                                          # a non-positive size
+    v = capi.View(W, H, ch._pose12(pose), cam.fx, cam.fy, cam.cx, cam.cy, NEAR, FAR, 0.0)
+    assert L.chisel_hip_render_view(plain.h, C.byref(v), None, None, None, 0) == 1  # null depth
+    assert L.chisel_hip_render_view(plain.h, None, None, None, None, 0) == 1        # null view
+    assert plain.RenderView(pose, cam)["depth"].shape == (H, W)                     # ... and the map still renders
+    group = ch.Chisel((16, 16, 16), 0.04, False, max_chunks=4096, devices=[0, 0])
+    assert "group" in refused(group, 5, pose, cam)
+    shard = ch.Chisel((16, 16, 16), 0.04, False, max_chunks=4096, n_shards=2, shard_rank=0)
+    assert "shard" in refused(shard, 5, pose, cam)
