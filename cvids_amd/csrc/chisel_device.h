@@ -53,16 +53,29 @@ __host__ __device__ inline int chunk_owner(int x, int y, int z, int n_shards, in
     return h < 0 ? h + n_shards : h;
 }
 
-// The map's error flags live in pinned host memory (the device addresses them through MapView::error_flag): two words, so
-// that neither kind of report can overwrite the other (a third word, [2], is not an error: the number of work items of the
-// latest integration launch, from which the host sizes a later launch's grid).
-//   [0] chunk pool (1) or chunk hash (2) exhausted: the map is incomplete from here on; stays set until chisel_hip_reset
-//   [1] a property of ONE point cloud (kernels_cloud.h: 3 = too many chunks / pairs, 4 = ray out of range): reported once, cleared
-// Plain stores: every writer of a word stores a nonzero code; the host reads them after a wait, without a copy.
-// Words [2], [3]: the work items / (item, frame) pairs of the latest integration launch (grid sizing hints).  Words [4], [5]: progress of the
-// map's stream -- [4] the number of the latest integration launch that has STARTED (its first thread), [5] the number of the latest launch
-// known to be OVER (stored by the count kernel of the recompute queued behind it) -- which the host reads instead of querying events.
-__device__ inline void raise_error(int *flag, int code) { reinterpret_cast<volatile int *>(flag)[code >= 3 ? 1 : 0] = code; }
+// The map's status block: ST_INTS words in pinned host memory through which the kernels report to the host (the device addresses them
+// through MapView::error_flag, the host reads them without a copy).  Two error words, so that neither kind of report can overwrite the other:
+//   ST_POOL_ERROR   chunk pool (1) or chunk hash (2) exhausted: the map is incomplete from here on; stays set until chisel_hip_reset
+//   ST_CLOUD_ERROR  a property of ONE point cloud (kernels_cloud.h: 3 = too many chunks / pairs, 4 = ray out of range): reported once, cleared
+// (plain stores: every writer of a word stores a nonzero code; the host reads them after a wait), and what is not an error:
+//   ST_ITEMS, ST_PAIRS  the work items / (item, frame) pairs of the latest integration launch, from which the host sizes a later launch's grid
+//   ST_STARTED      progress of the map's stream, which the host reads instead of querying events: the number of the latest integration
+//                   launch that has STARTED (its first thread) ...
+//   ST_DONE         ... and of the latest launch known to be OVER (stored by the count kernel of the recompute queued behind it)
+//   ST_USED         committed - free slots as the latest integration launch found them when it started (a growable pool's host looks at it)
+constexpr int ST_POOL_ERROR = 0, ST_CLOUD_ERROR = 1, ST_ITEMS = 2, ST_PAIRS = 3, ST_STARTED = 4, ST_DONE = 5, ST_USED = 7, ST_INTS = 16;
+__device__ inline void raise_error(int *flag, int code) { reinterpret_cast<volatile int *>(flag)[code >= 3 ? ST_CLOUD_ERROR : ST_POOL_ERROR] = code; }
+
+// The block a mesh recompute reports through (chisel_hip_map::mesh_totals_host: MH_INTS words in pinned host memory, written by
+// mesh_triangle_kernel unless noted):
+//   MH_TRIS, MH_GRIDS, MH_JOBS, MH_SEQ  the recompute's totals -- triangles, grids, jobs | record-list overflow << 31 -- and its sequence
+//                   number: ONE 16-byte store
+//   MH_UNFIT        the recompute did not fit its triangle list or its arena (what MC_LATCH was set by)
+//   MH_PUBLISHED    the sequence number again, behind a system-scope fence: what the host polls (the four totals are complete)
+//   MH_INFO_SEQ     the sequence number once the per-job records have reached mesh_info_host
+//   MH_ERROR_CHECK  reserved for check_device_error
+//   MH_STAGE        host only: staging of a small value that is copied to the device asynchronously
+constexpr int MH_TRIS = 0, MH_GRIDS = 1, MH_JOBS = 2, MH_SEQ = 3, MH_UNFIT = 4, MH_PUBLISHED = 5, MH_INFO_SEQ = 6, MH_ERROR_CHECK = 7, MH_STAGE = 8, MH_INTS = 16;
 
 struct MapView {
     float *sdf;
@@ -79,7 +92,7 @@ struct MapView {
     int *free_top;
     unsigned long long *counters;  // CHISEL_HIP_NUM_COUNTERS (filled by reduce_counters_kernel)
     unsigned long long *block_counters;  // [INTEGRATE_MAX_GRID][16] per-workgroup partial sums
-    int *error_flag;         // two words in pinned host memory, see raise_error
+    int *error_flag;         // the status block (ST_*) in pinned host memory
     int max_chunks;          // slots the per-slot arrays and the hash are laid out for (fixed at creation: the pool's upper limit)
     int committed;           // slots whose voxel payload has memory behind it, <= max_chunks: only these are ever on the free list (a growable
                              // pool commits more as it fills up, chisel_hip.hip: grow_pool; a fixed one has committed == max_chunks)
@@ -87,15 +100,20 @@ struct MapView {
     // a slot appends the resident chunks of its 27-neighbourhood (Chisel.h:175-189), so that a recompute starts with its count kernel
     unsigned *mesh_flag;     // [max_chunks] "this slot is in the job list"
     int *mesh_jobs;          // [mesh_jobs_capacity][3] chunk ids
-    int *mesh_ctl;           // [0..3] totals of the recompute in flight (triangles, grids, overflow, jobs), [4] entries of the job list
+    int *mesh_ctl;           // MC_INTS words (MC_*): totals of the recompute in flight, entries of the job list, latch, cursors, box of created ids
     int mesh_jobs_capacity;
 };
 
+// MapView::mesh_ctl / MeshBuffers::totals (ints): the recompute's totals -- MC_TRIS and MC_GRIDS are ONE 64-bit word for the last
+// arrivers' atomic --, MC_OVERFLOW of the record lists, MC_JOBS; MC_KEPT: entries of the job list the integration kernels keep; from
+// MC_CURSORS on MESH_PARTS (kernels_mesh.h) 64-bit cursors (triangles | cubes << 32).  The first three and the cursors start every
+// recompute at zero.
+constexpr int MC_TRIS = 0, MC_GRIDS = 1, MC_OVERFLOW = 2, MC_JOBS = 3, MC_KEPT = 4, MC_CURSORS = 8;
 // The bounding box of the ids of every chunk created since the last reset (never shrinks: removals leave it as it is), kept in
 // mesh_ctl[MC_BBOX .. +5] = min x, y, z, max x, y, z by everything that creates a chunk.  A superset of what is resident, and an exact
 // "absent" verdict for ids outside it: ChunkManager::InterpolateColor's eight look-ups (ChunkManager.cpp:506-520) take integer VOXEL
 // indices for metric positions and land hundreds of chunks away, where one compare answers what was a hash probe per vertex.
-constexpr int MC_BBOX = 136;
+constexpr int MC_BBOX = 136, MC_INTS = MC_BBOX + 8;
 // mesh_ctl[MC_LATCH] != 0: the recompute in front did not fit its triangle list or its arena and will be emitted again from the voxels AS THEY
 // ARE -- set by mesh_triangle_kernel, read by integrate_kernel (every wave leaves at once: the map stays as the recompute saw it), cleared by
 // the host when it emits again and then replays the launches that left (host_mesh.h: check_mesh_totals)

@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "chisel_device.h"
+#include "host_buffer.h"
 #include "host_frustum.h"
 #include "kernels_cull.h"
 #include "kernels_integrate.h"
@@ -170,6 +171,12 @@ struct ProfEvent {
 #ifndef CHISEL_FRONT_STREAMS
 #define CHISEL_FRONT_STREAMS 2
 #endif
+// chisel_hip_map::launch_stats (chisel_hip_get_launch_stats), in the order of Chisel.LAUNCH_STATS (cvids_amd/chisel.py): integration launches at
+// 2 voxels per lane, at 4, at 4 with a 2-voxel tail; cull launches with four waves per workgroup, with a wave per frame; all cull launches
+// ("unordered_worklists": launch sets without an order kernel); launch sets in the short single-stream form; launch sets in all; launch sets
+// queued behind a recompute whose totals the host had not seen, and the ones of them that were replayed
+enum LaunchStat { LS_VPL2, LS_VPL4, LS_VPL4_SPLIT, LS_CULL_NARROW, LS_CULL_WIDE, LS_CULL, LS_INLINE, LS_INTEGRATE, LS_DEFERRED, LS_REPLAYED, LS_COUNT };
+static_assert(LS_COUNT == CHISEL_HIP_NUM_LAUNCH_STATS, "launch_stats: one name per word of chisel_hip_get_launch_stats");
 static_assert(CHISEL_FRONT_SETS >= 3 && (CHISEL_PENDING_RING & (CHISEL_PENDING_RING - 1)) == 0 && CHISEL_PENDING_RING >= 4, "front-half rings");
 struct chisel_hip_map {
     // a group handle (chisel_hip_create_group, host_group.h): no device state of its own, one shard map per GPU
@@ -184,8 +191,14 @@ struct chisel_hip_map {
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
+    // The views the kernels take by value (MapView, MeshBuffers, CloudView, ShellPlan) hold raw pointers; what they point at is owned here,
+    // by the map (view_mem, mesh_mem, cloud, shell_mem), and freed with it.
     MapView view{};
-    MapView *view_dev = nullptr;  // device-resident copy of `view` (cold fields are read from here by the kernels)
+    struct ViewMemory {           // (sdf, wgt, rgbw: a fixed pool's; a growable pool's are mapped ranges, pool_mem)
+        DeviceBuffer<float> sdf, wgt; DeviceBuffer<uchar4> rgbw; DeviceBuffer<uint64_t> hash_keys, slot_key; DeviceBuffer<uint32_t> slot_dirty;
+        DeviceBuffer<int> hash_vals, free_list, free_top, mesh_jobs, mesh_ctl; DeviceBuffer<unsigned long long> counters, block_counters; DeviceBuffer<unsigned> mesh_flag;
+    } view_mem;
+    DeviceBuffer<MapView> view_dev;  // device-resident copy of `view` (cold fields are read from here by the kernels)
     uint64_t hash_capacity = 0;
     chisel_hip_integrator integ{CHISEL_HIP_TRUNC_INVERSE, 8.0f, 1.0f, 1, 0.05f};  // ChiselNode.cpp:54-64 defaults
     // A batch (up to KMAX frames) is handled by one launch set in two halves:
@@ -198,15 +211,15 @@ struct chisel_hip_map {
     // The pending sets (chunks a batch may create) rotate over CHISEL_PENDING_RING buffers of their own: batch b reads those of b-1
     // and b-2 while later batches fill theirs; a batch's pyramid kernel clears the one it is about to use.
     struct BatchSet {
-        float2 *pyr_data = nullptr;      // [KMAX][pyr_stride]
-        PixelRec *rec_data = nullptr;    // [KMAX][2 + W*H]: per frame two all-NaN records, then the image
-        float *depth_stage = nullptr;    // [KMAX][depth_stage_elems]: host frames are copied here
-        uint8_t *color_stage = nullptr;  // [KMAX][color_stage_bytes]
-        FrameBox *boxes = nullptr;       // [items_capacity][KMAX]: the cull kernel's flags of every (work item, frame), in work-list order
-        unsigned short *brick_masks = nullptr;  // [items_capacity][bricks per chunk]: the frames that can touch each brick of a work item (cull_kernel's brick phase)
-        int *cand_count = nullptr;       // [COUNT_INTS] device counters of the batch (COUNT_* in kernels_cull.h)
-        WorkItem *items = nullptr;       // [items_capacity]: the work-list
-        ItemSync *sync = nullptr;        // [items_capacity]: chunk-level state of the work items while the integration kernel runs
+        DeviceBuffer<float2> pyr_data;       // [KMAX][pyr_stride]
+        DeviceBuffer<PixelRec> rec_data;     // [KMAX][2 + W*H]: per frame two all-NaN records, then the image
+        DeviceBuffer<float> depth_stage;     // [KMAX][depth_stage_elems]: host frames are copied here
+        DeviceBuffer<uint8_t> color_stage;   // [KMAX][color_stage_bytes]
+        DeviceBuffer<FrameBox> boxes;        // [items_capacity][KMAX]: the cull kernel's flags of every (work item, frame), in work-list order
+        DeviceBuffer<unsigned short> brick_masks;  // [items_capacity][bricks per chunk]: the frames that can touch each brick of a work item (cull_kernel's brick phase)
+        DeviceBuffer<int> cand_count;        // [COUNT_INTS] device counters of the batch (COUNT_* in kernels_cull.h)
+        DeviceBuffer<WorkItem> items;        // [items_capacity]: the work-list
+        DeviceBuffer<ItemSync> sync;         // [items_capacity]: chunk-level state of the work items while the integration kernel runs
         uint64_t *pending = nullptr;     // chunks this batch may create: one of pending_ring (assigned per batch)
         hipStream_t front_stream = nullptr;  // where this batch's front half runs: aux, or the map's stream when nothing is in flight
         hipEvent_t front_done = nullptr;  // recorded on the front stream after the set's front half (work-list, brick masks) is complete
@@ -222,7 +235,7 @@ struct chisel_hip_map {
         bool front_inline = false;       // the set's front half ran on the map's stream, in front of its integration: no front_done event
     } sets[CHISEL_FRONT_SETS];
     int deferred_set = -1;               // the set whose integration was queued behind a recompute the host has not sized yet (launch_back), or -1
-    uint64_t *pending_ring[CHISEL_PENDING_RING] = {};  // [PENDING_CAPACITY + 1] each: the set, then its overflow flag
+    DeviceBuffer<uint64_t> pending_ring[CHISEL_PENDING_RING];  // [PENDING_CAPACITY + 1] each: the set, then its overflow flag
     hipStream_t aux = nullptr, aux2 = nullptr, aux3 = nullptr;  // the front halves of consecutive batches take them in turn (aux3: CHISEL_FRONT_SETS >= 4 only)
     hipEvent_t call_event = nullptr;     // caller-provided stream: orders the front after the caller's producers
     hipEvent_t mutation_event = nullptr; // map changed outside the integration path (reset, upload): the next front waits
@@ -260,16 +273,16 @@ struct chisel_hip_map {
     unsigned batch_seq = 0;              // batches issued so far: batch b uses sets[b % CHISEL_FRONT_SETS] and pending_ring[b % CHISEL_PENDING_RING]
     // How far the map's stream has come, WITHOUT events on it: a kernel that carries an event (or an event record, or a wait packet) holds the
     // kernel behind it back by 5-6 us (rocprofv3 timelines of the driver's window with and without them: 309 -> 294 us).  Every integration
-    // launch has a number (launch_seq, from 1); its first thread stores it into pinned word [4] (PROGRESS_STARTED: this launch has started, so
+    // launch has a number (launch_seq, from 1); its first thread stores it into the status block (ST_STARTED: this launch has started, so
     // everything queued before it on the stream is complete -- its own front half when that ran on the map's stream, and the launch before it),
-    // the count kernel of a recompute stores the number of the launch in front of it into word [5] (PROGRESS_DONE).  complete_seq: what the
+    // the count kernel of a recompute stores the number of the launch in front of it into ST_DONE.  complete_seq: what the
     // host itself has seen complete (a wait for the stream).
     unsigned launch_seq = 0, complete_seq = 0;
     // A pool that grows with the scene, as the reference's unordered_map of heap chunks does (ChunkManager.h:40-55, ChunkManager.cpp:171-174).
     // The voxel arrays are address ranges reserved for view.max_chunks slots (hipMemAddressReserve) of which view.committed have physical
     // memory mapped (hipMemCreate / hipMemMap, in steps of the allocation granularity); the per-slot arrays and the hash (76 bytes per slot
     // against 48 KiB of voxels) are allocated for max_chunks at once, so nothing is ever moved or rehashed.  When the free slots fall under a
-    // low-water mark -- checked at launch-set boundaries from the count the integration kernels report in pinned word [7] -- grow_pool() maps
+    // low-water mark -- checked at launch-set boundaries from the count the integration kernels report in ST_USED -- grow_pool() maps
     // more memory and two small kernels on the map's stream give the new slots default voxels and push them onto the free list.
     bool growable = false;
     struct PoolArray {
@@ -286,7 +299,7 @@ struct chisel_hip_map {
     size_t depth_stage_elems = 0;
     size_t color_stage_bytes = 0;
     // scratch for queries
-    int *scratch_i = nullptr;   // device ints
+    DeviceBuffer<int> scratch_i;
     size_t scratch_i_elems = 0;
     // meshing state
     int update_meshes_calls = 0;                                       // Chisel.cpp:53 "static int cnt"
@@ -300,16 +313,15 @@ struct chisel_hip_map {
         int n = 0;                                                     // jobs
         int arena = -1;
     } pending_meshes;
-    int *mesh_totals_host = nullptr;                                   // pinned: [0-3] totals of the recompute in flight and its sequence number (one 16-byte store of the device), [6] sequence number of the job records, [7] check_device_error
-    int *mesh_totals_dev = nullptr;                                    // the same memory as the device addresses it
-    int *error_flag_host = nullptr;                                    // pinned: the map's error flag (view.error_flag is its device address)
-    int *mesh_info_dev = nullptr;                                      // mesh_info_host as the device addresses it
+    PinnedBuffer<int> mesh_totals_host;                                // [MH_INTS] what the recompute in flight reports (MH_* in chisel_device.h)
+    PinnedBuffer<int> error_flag_host;                                 // [ST_INTS] the map's status block (ST_* in chisel_device.h; view.error_flag is its device address)
     int mesh_seq = 0;                                                  // recomputes queued so far
-    JobInfo *mesh_info_host = nullptr;                                 // pinned: its first MESH_INFO_PREFETCH per-job records
+    PinnedBuffer<JobInfo> mesh_info_host;                              // its first MESH_INFO_PREFETCH per-job records
     hipStream_t copy_stream = nullptr;                                 // small device->host copies that must not wait for queued batches
     // the plan of a sharded recompute, made on the device (kernels_map.h: ShellPlan; chisel_hip_shell_plan_device ...)
     ShellPlan shell_plan{};
-    int *shell_plan_host = nullptr, *shell_plan_host_dev = nullptr;    // pinned: where the plan's figures reach the host (the one wait of a sharded recompute)
+    struct ShellMemory { DeviceBuffer<unsigned long long> jobset; DeviceBuffer<int> my_jobs, ctl, send_items; } shell_mem;
+    PinnedBuffer<int> shell_plan_host;                                 // where the plan's figures reach the host (the one wait of a sharded recompute)
     int64_t shell_send[SHELL_MAX_SHARDS][2] = {}, shell_recv[SHELL_MAX_SHARDS][2] = {};  // (items, voxels) per peer of the latest plan
     int shell_jobs = 0, shell_send_items = 0;
     const unsigned char *ghost_packed = nullptr;                       // the received segments the current ghosts came from (chisel_hip_import_shells_packed): dropped from there
@@ -329,7 +341,7 @@ struct chisel_hip_map {
     bool dirty_tail_queued = false;                                    // chisel_hip_meshes_to_update_prefetch: the listing kernel is queued (or done) for ...
     uint64_t dirty_tail_cursor = 0;                                    // ... this cursor word and ...
     unsigned dirty_tail_batch = 0;                                     // ... this many batches issued
-    int *dirty_tail_host = nullptr, *dirty_tail_dev = nullptr;         // pinned: where list_dirty_tail_kernel leaves the new entries of the dirty list
+    PinnedBuffer<int> dirty_tail_host;                                 // where list_dirty_tail_kernel leaves the new entries of the dirty list
     int batch_frames = KMAX;                                           // frames per launch set in chisel_hip_integrate_batch
     uint64_t ghost_bytes = 0;                                          // group handle: ghost voxel bytes its recomputes have moved between shards
     bool single_chunk = false;                                         // chisel_hip_integrate_chunk: the next integrate call sees this id only
@@ -341,12 +353,18 @@ struct chisel_hip_map {
     int mesh_stages = 3;                                               // MeshParams::stages of the next recompute (chisel_hip_generate_mesh lowers it)
     bool mesh_detached = false;                                        // the next recompute leaves meshesToUpdate alone (chisel_hip_generate_mesh)
     uint64_t topology_epoch = 0;                                       // bumped by everything but integration that adds or removes chunks (chisel_hip_topology_epoch)
-    MeshBuffers mesh_buf{};
+    MeshBuffers mesh_buf{};                                            // (flags and totals: view_mem.mesh_flag and view_mem.mesh_ctl)
+    struct MeshMemory {
+        DeviceBuffer<MeshJob> jobs; DeviceBuffer<int> ids; DeviceBuffer<JobInfo> info; DeviceBuffer<TriRec> tris; DeviceBuffer<CubeCorners> corners;
+        DeviceBuffer<unsigned> cnt; DeviceBuffer<unsigned long long> job_acc; DeviceBuffer<double> query; DeviceBuffer<float> cube;
+    } mesh_mem;
     struct CloudBuffers {                                              // point-cloud fusion mode (host_cloud.h), allocated on first use
-        float *points = nullptr, *colors = nullptr;                    // staging of host clouds
+        DeviceBuffer<float> points, colors;                            // staging of host clouds
         int64_t capacity = 0;                                          // points
-        size_t zeroed_bytes = 0;                                       // table keys | control | counts | cursors: one allocation, one memset per cloud
-        CloudView view{};
+        DeviceBuffer<char> zeroed;                                     // table keys | control | counts | cursors: one allocation, one memset per cloud
+        size_t zeroed_bytes = 0;
+        CloudView view{};                                              // (what follows: what it points at)
+        DeviceBuffer<CloudRay> rays; DeviceBuffer<unsigned> rgb; DeviceBuffer<int> tile_prefix, table_vals, pairs, sorted; DeviceBuffer<uint64_t> listed;
     } cloud;
     // profiling
     bool profiling = false;
@@ -371,15 +389,14 @@ int sync_all(chisel_hip_map *m) {
 }
 
 // ---- progress of the map's stream (chisel_hip_map::launch_seq) ---------------------------------------------------------------------------
-constexpr int PROGRESS_STARTED = 4, PROGRESS_DONE = 5;  // words of the pinned error-flag block (chisel_device.h)
 inline void note_stream_idle(chisel_hip_map *m) { m->complete_seq = m->launch_seq; }  // the host has just waited for the map's stream
 // has integration launch L started / ended?  (pinned words the kernels store into; no runtime call, nothing queued)
 // (launch numbers are compared through their signed difference: a map that lives through 2^32 launches keeps working)
 inline bool seq_le(unsigned a, unsigned b) { return (int)(a - b) <= 0; }
 inline bool integrate_started(chisel_hip_map *m, unsigned L) {
     if (seq_le(L, m->complete_seq)) return true;
-    volatile int *w = reinterpret_cast<volatile int *>(m->error_flag_host);
-    const unsigned started = (unsigned)w[PROGRESS_STARTED], done = (unsigned)w[PROGRESS_DONE];
+    volatile int *w = reinterpret_cast<volatile int *>(m->error_flag_host.get());
+    const unsigned started = (unsigned)w[ST_STARTED], done = (unsigned)w[ST_DONE];
     // (a word counts only if it names a launch of this map that is not already known to be over: they start at zero)
     if (seq_le(started, m->launch_seq) && !seq_le(started - 1u, m->complete_seq)) m->complete_seq = started - 1u;
     if (seq_le(done, m->launch_seq) && !seq_le(done, m->complete_seq)) m->complete_seq = done;
@@ -409,7 +426,6 @@ int wait_integrate(chisel_hip_map *m, unsigned L, bool until_done) {
 }
 
 // ---- growable pool (chisel_hip_map::growable) ---------------------------------------------------------------------------------------------
-constexpr int PROGRESS_USED = 7;  // pinned word: committed - free slots as the latest integration launch found them when it started
 // physical memory behind the first `bytes` of a reserved array
 int pool_map_upto(chisel_hip_map *m, chisel_hip_map::PoolArray &A, size_t bytes) {
     bytes = (bytes + m->vmm_granularity - 1) / m->vmm_granularity * m->vmm_granularity;
@@ -466,7 +482,7 @@ int grow_pool(chisel_hip_map *m, int64_t want) {
     hipLaunchKernelGGL(grow_commit_kernel, dim3(1), dim3(1), 0, m->stream, m->view, n);
     HIP_TRY(hipGetLastError());
     v.committed = (int)target;
-    HIP_TRY(hipMemcpyAsync(&m->view_dev->committed, &v.committed, sizeof(int), hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipMemcpyAsync(&m->view_dev.get()->committed, &v.committed, sizeof(int), hipMemcpyHostToDevice, m->stream));
     m->grow_events++;
     return CHISEL_HIP_OK;
 }
@@ -474,9 +490,9 @@ int grow_pool(chisel_hip_map *m, int64_t want) {
 // less what the launches queued since may have taken -- is less than a quarter of the pool, or than `expect_new` with room to spare.
 int maybe_grow(chisel_hip_map *m, int64_t expect_new) {
     if (!m->growable || m->view.committed >= m->view.max_chunks) return CHISEL_HIP_OK;
-    volatile int *w = reinterpret_cast<volatile int *>(m->error_flag_host);
-    const int64_t used = w[PROGRESS_USED];
-    const unsigned started = (unsigned)w[PROGRESS_STARTED];
+    volatile int *w = reinterpret_cast<volatile int *>(m->error_flag_host.get());
+    const int64_t used = w[ST_USED];
+    const unsigned started = (unsigned)w[ST_STARTED];
     const int64_t in_flight = (int64_t)((int)(m->launch_seq - started) > 0 ? (int)(m->launch_seq - started) : 0) + 1;  // launches whose allocations the report does not hold
     const int64_t free_est = (int64_t)m->view.committed - used - in_flight * expect_new;
     if (free_est >= (int64_t)m->view.committed / 4 && free_est >= 2 * expect_new) return CHISEL_HIP_OK;
@@ -502,13 +518,20 @@ hipError_t note_map_mutation(chisel_hip_map *m) {
     return hipEventRecord(m->mutation_event, m->stream);
 }
 
+// n elements for an array the map owns (`buf`) and one of its views points at (`p`: the copy of buf.get() the kernels are given)
+template <class T>
+hipError_t alloc_viewed(DeviceBuffer<T> &buf, T *&p, size_t n) {
+    const hipError_t e = buf.alloc(n);
+    p = buf.get();
+    return e;
+}
+
 int ensure_scratch(chisel_hip_map *m, size_t elems) {
     if (elems <= m->scratch_i_elems) return CHISEL_HIP_OK;
     HIP_TRY(hipStreamSynchronize(m->stream));
-    if (m->scratch_i) HIP_TRY(hipFree(m->scratch_i));
-    m->scratch_i = nullptr;
+    m->scratch_i_elems = 0;
     size_t n = std::max<size_t>(elems, 1024);
-    HIP_TRY(hipMalloc(&m->scratch_i, n * sizeof(int)));
+    HIP_TRY(m->scratch_i.alloc(n));
     m->scratch_i_elems = n;
     return CHISEL_HIP_OK;
 }
@@ -559,6 +582,31 @@ int drain_profile(chisel_hip_map *m) {
     return CHISEL_HIP_OK;
 }
 
+// Device selection of the three *_create calls: device_id < 0 is the current device; the device must exist and be a gfx950 (there is
+// no CPU path and no other code object); it is made current.
+int open_device(int device_id, int *out) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(CHISEL_HIP_ERR_HIP, "no HIP device visible: libchisel_hip has no CPU path");
+    if (device_id < 0) HIP_TRY(hipGetDevice(&device_id));
+    if (device_id >= ndev) return fail(CHISEL_HIP_ERR_INVALID, "device_id out of range");
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, device_id));
+    if (!strstr(prop.gcnArchName, "gfx950"))
+        return fail(CHISEL_HIP_ERR_HIP, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 (MI355X) only");
+    HIP_TRY(hipSetDevice(device_id));
+    *out = device_id;
+    return CHISEL_HIP_OK;
+}
+
+// chisel_hip_wait_event: what the caller hands over next (a buffer, a cloud) is ready behind its event, which lives on a stream of the
+// caller's: `stream` waits for it, once
+int wait_for_input(chisel_hip_map *m, hipStream_t stream) {
+    if (!m->input_event) return CHISEL_HIP_OK;
+    HIP_TRY(hipStreamWaitEvent(stream, m->input_event, 0));
+    m->input_event = nullptr;
+    return CHISEL_HIP_OK;
+}
+
 // Wait for the stream by polling: the wake-up of a blocking wait costs more than the kernels being waited for.
 hipError_t wait_stream_spinning(hipStream_t st) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -575,16 +623,16 @@ int check_device_error(chisel_hip_map *m) {
     HIP_TRY(wait_stream_spinning(m->stream));
     note_stream_idle(m);
     std::atomic_thread_fence(std::memory_order_acquire);
-    volatile int *flags = m->error_flag_host;  // written by the device (raise_error): no copy
-    const int cloud = flags[1];
+    volatile int *flags = m->error_flag_host.get();  // written by the device (raise_error): no copy
+    const int cloud = flags[ST_CLOUD_ERROR];
     if (cloud != 0) {  // a property of one cloud, not of the map: reported once
-        flags[1] = 0;
-        if (flags[0] == 0)
+        flags[ST_CLOUD_ERROR] = 0;
+        if (flags[ST_POOL_ERROR] == 0)
             return fail(CHISEL_HIP_ERR_UNSUPPORTED, cloud == CLOUD_ERR_CAPACITY ? "point cloud: too many chunks or (chunk, point) pairs for one call"
                                                                                 : "point cloud: a ray leaves the supported chunk-id range or is too long");
     }
-    if (flags[0] != 0)  // the map is incomplete: every wait reports it until chisel_hip_reset
-        return fail(CHISEL_HIP_ERR_POOL_FULL, flags[0] == 1 ? "chunk pool exhausted: raise chisel_hip_config.max_chunks"
+    if (flags[ST_POOL_ERROR] != 0)  // the map is incomplete: every wait reports it until chisel_hip_reset
+        return fail(CHISEL_HIP_ERR_POOL_FULL, flags[ST_POOL_ERROR] == 1 ? "chunk pool exhausted: raise chisel_hip_config.max_chunks"
                                                             : "chunk hash table exhausted: raise chisel_hip_config.max_chunks");
     return CHISEL_HIP_OK;
 }
@@ -598,7 +646,7 @@ void fill_camera(CameraParams &c, const float *pose, float fx, float fy, float c
 }
 
 int ensure_pyramid(chisel_hip_map *m, int W, int H) {
-    if (m->sets[0].pyr_data && m->pyr_w == W && m->pyr_h == H) return CHISEL_HIP_OK;
+    if (m->sets[0].pyr_data.get() && m->pyr_w == W && m->pyr_h == H) return CHISEL_HIP_OK;
     int rc = sync_all(m);
     if (rc) return rc;
     int off = 0;
@@ -611,16 +659,12 @@ int ensure_pyramid(chisel_hip_map *m, int W, int H) {
     }
     m->pyr_stride = off;
     for (auto &bs : m->sets) {
-        if (bs.pyr_data) HIP_TRY(hipFree(bs.pyr_data));
-        if (bs.rec_data) HIP_TRY(hipFree(bs.rec_data));
-        bs.pyr_data = nullptr;
-        bs.rec_data = nullptr;
-        HIP_TRY(hipMalloc(&bs.pyr_data, (size_t)off * KMAX * sizeof(float2)));
+        HIP_TRY(bs.pyr_data.alloc((size_t)off * KMAX));
         // two records of padding in front of every frame's image, NaN once and for all (only pixels are ever written): the
         // integration kernel points voxels that are off the image at record -1
         const size_t rec_floats = ((size_t)W * H + 2) * KMAX * (sizeof(PixelRec) / sizeof(float));
-        HIP_TRY(hipMalloc(&bs.rec_data, rec_floats * sizeof(float)));
-        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(bs.rec_data), 0x7fc00000, rec_floats, m->stream));
+        HIP_TRY(bs.rec_data.alloc(rec_floats / (sizeof(PixelRec) / sizeof(float))));
+        HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(bs.rec_data.get()), 0x7fc00000, rec_floats, m->stream));
     }
     HIP_TRY(hipStreamSynchronize(m->stream));  // the padding is in place before a front half (possibly on the other stream) writes pixels
     m->pyr.data = nullptr;
@@ -709,25 +753,25 @@ int launch_back(chisel_hip_map *m, chisel_hip_map::BatchSet &bs, const Integrate
             bs.replay_color = color;
             bs.replay_total = total;
             bs.replay_inline = inline_resolve;
-            m->launch_stats[8]++;
+            m->launch_stats[LS_DEFERRED]++;
         } else {
             int rc_m = check_mesh_totals(m);
             if (rc_m) return rc_m;
         }
     }
-    int *wc = bs.cand_count + COUNT_ITEMS;
+    int *wc = bs.cand_count.get() + COUNT_ITEMS;
     {
         ProfScope ps(m, CHISEL_HIP_KERNEL_INTEGRATE);
         // Grid.  One unit per wave and the hardware's in-order workgroup dispatch over the cost-ordered work-list is the
         // schedule that works best (the SIMDs issue from their oldest wave first: a persistent wave that pulls a second unit keeps
         // its age and starves the younger waves' first units).  The number of work items is only known on the device, so the grid
-        // is sized from the count a recent launch of this map reported (pinned word [2] beside the error flags, written by the
+        // is sized from the count a recent launch of this map reported (ST_ITEMS of the status block, written by the
         // integration kernel; it lags by the launches in flight) plus 1/8; surplus workgroups find no unit and leave, a shortfall
         // is pulled from the queue heads by the workgroups as they finish.  Without a report yet: what the chip holds at once.
         // The same figure picks the granularity: 2 voxels per lane for launches of several frames below INTEGRATE_FINE_BELOW items
         // (about three rounds of the chip at 4 voxels per lane), 4 otherwise (kernels_integrate.h).
-        const long long hint = (long long)reinterpret_cast<volatile int *>(m->error_flag_host)[2];
-        const long long pairs = (long long)reinterpret_cast<volatile int *>(m->error_flag_host)[3];  // (item, frame) pairs of that launch, 0 = unknown
+        const long long hint = (long long)reinterpret_cast<volatile int *>(m->error_flag_host.get())[ST_ITEMS];
+        const long long pairs = (long long)reinterpret_cast<volatile int *>(m->error_flag_host.get())[ST_PAIRS];  // (item, frame) pairs of that launch, 0 = unknown
         int vpl = (IP.n_frames >= 4 && hint > 0 && hint * (long long)(N * N * N) < (long long)m->tune.fine_below * 4096 &&
                    (pairs == 0 || pairs >= (long long)m->tune.fine_min_frames_per_item * hint)) ? 2 : 4;
         if (m->tune.force_vpl) vpl = m->tune.force_vpl;
@@ -755,18 +799,18 @@ int launch_back(chisel_hip_map *m, chisel_hip_map::BatchSet &bs, const Integrate
         }
         blocks = std::min<long long>(blocks, (long long)INTEGRATE_GRID_CAP);
         const int grid = (int)std::max<long long>(step, (blocks + step - 1) / step * step);
-        m->launch_stats[vpl == 2 ? 0 : (split >= 0 ? 2 : 1)]++;
-        m->launch_stats[7]++;
-        if (inline_resolve) m->launch_stats[6]++;
-        int *queues = bs.cand_count + COUNT_QUEUE0;
+        m->launch_stats[vpl == 2 ? LS_VPL2 : (split >= 0 ? LS_VPL4_SPLIT : LS_VPL4)]++;
+        m->launch_stats[LS_INTEGRATE]++;
+        if (inline_resolve) m->launch_stats[LS_INLINE]++;
+        int *queues = bs.cand_count.get() + COUNT_QUEUE0;
         bool same_cam = color;
         for (int k = 0; k < IP.n_frames; k++) same_cam = same_cam && IP.f[k].same_cam;
         if (++m->launch_seq == 0u) { m->launch_seq = 1u; m->complete_seq = 0u; }  // (0 means "never launched"; the wait in integrate_group for a buffer set's last launch has long passed)
         bs.lseq = m->launch_seq;
         const int lseq = (int)bs.lseq;
 #define CHISEL_LAUNCH_INTEGRATE(COLOR, SAMECAM, VPL)                                                                                 \
-    hipLaunchKernelGGL((integrate_kernel<N, COLOR, SAMECAM, VPL>), dim3(grid), dim3(64 * WPB), 0, m->stream, IP, m->view, m->view_dev, bs.items, \
-                       bs.boxes, bs.sync, wc, queues, m->items_capacity, split, lseq, bs.brick_masks)
+    hipLaunchKernelGGL((integrate_kernel<N, COLOR, SAMECAM, VPL>), dim3(grid), dim3(64 * WPB), 0, m->stream, IP, m->view, m->view_dev.get(), bs.items.get(), \
+                       bs.boxes.get(), bs.sync.get(), wc, queues, m->items_capacity, split, lseq, bs.brick_masks.get())
         if (color && same_cam) {  // CVIDS: depth and colour share one camera (sample.launch:19-20)
             if (vpl == 2) CHISEL_LAUNCH_INTEGRATE(true, true, 2);
             else CHISEL_LAUNCH_INTEGRATE(true, true, 4);
@@ -797,7 +841,7 @@ int launch_group(chisel_hip_map *m, chisel_hip_map::BatchSet &bs, const PyramidP
     const int total = CullSpace(CP).total;  // candidate slots: every id of the union range, or the owned ones of a sharded map
     g_host_timer.lap(2);
     PyramidView pyr = m->pyr;
-    pyr.data = bs.pyr_data;
+    pyr.data = bs.pyr_data.get();
     // Nothing in flight (the previous batch has been integrated, e.g. a caller that waits after every frame): no second
     // stream to run beside, so the short form -- pyramid, cull with the lookup inline, integrate -- on the map's stream.
     // `front` was decided in integrate_group (it also routes the staging copies).
@@ -811,7 +855,7 @@ int launch_group(chisel_hip_map *m, chisel_hip_map::BatchSet &bs, const PyramidP
     {
         ProfScope ps(m, CHISEL_HIP_KERNEL_PYRAMID, front);
         dim3 grid((PP.W + 63) / 64, (PP.H + 63) / 64, IP.n_frames);
-        hipLaunchKernelGGL(depth_pyramid_kernel, grid, dim3(256), 0, front, PP, pyr, bs.cand_count, bs.pending);
+        hipLaunchKernelGGL(depth_pyramid_kernel, grid, dim3(256), 0, front, PP, pyr, bs.cand_count.get(), bs.pending);
     }
     g_host_timer.lap(3);
     // the chunks the batches in flight may create: the pending sets of the previous two (complete once the previous batch's cull kernel
@@ -819,8 +863,8 @@ int launch_group(chisel_hip_map *m, chisel_hip_map::BatchSet &bs, const PyramidP
     const unsigned b = m->batch_seq;
     const uint64_t *prev_pending = nullptr, *prev2_pending = nullptr;
     if (!inline_resolve) {
-        prev_pending = (b >= 1 || m->force_uncertain) ? m->pending_ring[(b + CHISEL_PENDING_RING - 1u) & (CHISEL_PENDING_RING - 1u)] : nullptr;
-        prev2_pending = b >= 2 ? m->pending_ring[(b + CHISEL_PENDING_RING - 2u) & (CHISEL_PENDING_RING - 1u)] : nullptr;
+        prev_pending = (b >= 1 || m->force_uncertain) ? m->pending_ring[(b + CHISEL_PENDING_RING - 1u) & (CHISEL_PENDING_RING - 1u)].get() : nullptr;
+        prev2_pending = b >= 2 ? m->pending_ring[(b + CHISEL_PENDING_RING - 2u) & (CHISEL_PENDING_RING - 1u)].get() : nullptr;
         if (b >= 1) {
             int rc_w = wait_for_front_of(m, m->sets[(b + CHISEL_FRONT_SETS - 1u) % CHISEL_FRONT_SETS], front);
             if (rc_w) return rc_w;
@@ -838,7 +882,7 @@ int launch_group(chisel_hip_map *m, chisel_hip_map::BatchSet &bs, const PyramidP
             for (int k2 = 0; k2 < CP.n_frames; k2++) vmax = std::max(vmax, (double)CP.f[k2].range_dim[0] * CP.f[k2].range_dim[1] * CP.f[k2].range_dim[2]);
             narrow_cull = m->cfg.n_shards <= m->tune.narrow_cull_max_shards && (double)CP.range_dim[0] * CP.range_dim[1] * CP.range_dim[2] > m->tune.narrow_cull_ratio * vmax;
             if (m->tune.force_cull_waves) narrow_cull = m->tune.force_cull_waves != 16;
-            m->launch_stats[(narrow_cull && IP.n_frames > 4) ? 3 : 4]++;
+            m->launch_stats[(narrow_cull && IP.n_frames > 4) ? LS_CULL_NARROW : LS_CULL_WIDE]++;
         }
         // a wave of the four-wave form takes several frames: the ones that share least (kernels_cull.h).  Frames 0 and 1 against frames 0
         // and `waves` by the ids their ranges have in common: interleaved agents share less with their neighbour in the launch
@@ -859,20 +903,20 @@ int launch_group(chisel_hip_map *m, chisel_hip_map::BatchSet &bs, const PyramidP
             cull_contig = common(CP.f[0], CP.f[1]) < common(CP.f[0], CP.f[far]) ? 1 : 0;
             if (m->tune.force_cull_contig >= 0) cull_contig = m->tune.force_cull_contig;
         }
-        const int *force_flag = m->force_uncertain ? m->sets[0].cand_count + COUNT_ONE : nullptr;
+        const int *force_flag = m->force_uncertain ? m->sets[0].cand_count.get() + COUNT_ONE : nullptr;
         front_recorded = false;
         // (pipelined form: the cull kernel's completion is the set's cull_done event -- what the next batch's cull kernel waits for)
         const bool cull_recorded = m->tune.ext_events && !m->profiling && !bs.staged && !inline_resolve;
 #define CHISEL_LAUNCH_CULL_W(KLV, WV)                                                                                                          \
     do {                                                                                                                                       \
         if (cull_recorded)                                                                                                                     \
-            hipExtLaunchKernelGGL((cull_kernel<N, KLV, WV>), cgrid, dim3(64 * CullGeom<KLV, WV>::WAVES), 0, front, nullptr, bs.cull_done, 0, CP, pyr, bs.items, \
-                                  bs.boxes, bs.cand_count, m->items_capacity, m->view, prev_pending, prev2_pending, force_flag, bs.pending, bs.sync, \
-                                  cull_contig, skip_bricks ? bs.brick_masks : nullptr);                                                        \
+            hipExtLaunchKernelGGL((cull_kernel<N, KLV, WV>), cgrid, dim3(64 * CullGeom<KLV, WV>::WAVES), 0, front, nullptr, bs.cull_done, 0, CP, pyr, bs.items.get(), \
+                                  bs.boxes.get(), bs.cand_count.get(), m->items_capacity, m->view, prev_pending, prev2_pending, force_flag, bs.pending, bs.sync.get(), \
+                                  cull_contig, skip_bricks ? bs.brick_masks.get() : nullptr);                                                        \
         else                                                                                                                                   \
-            hipLaunchKernelGGL((cull_kernel<N, KLV, WV>), cgrid, dim3(64 * CullGeom<KLV, WV>::WAVES), 0, front, CP, pyr, bs.items, bs.boxes, bs.cand_count, \
-                               m->items_capacity, m->view, prev_pending, prev2_pending, force_flag, bs.pending, bs.sync, cull_contig,        \
-                               skip_bricks ? bs.brick_masks : nullptr);                                                                       \
+            hipLaunchKernelGGL((cull_kernel<N, KLV, WV>), cgrid, dim3(64 * CullGeom<KLV, WV>::WAVES), 0, front, CP, pyr, bs.items.get(), bs.boxes.get(), bs.cand_count.get(), \
+                               m->items_capacity, m->view, prev_pending, prev2_pending, force_flag, bs.pending, bs.sync.get(), cull_contig,        \
+                               skip_bricks ? bs.brick_masks.get() : nullptr);                                                                       \
     } while (0)
 #define CHISEL_LAUNCH_CULL(KLV) do { if (narrow_cull && cull_one_wave) CHISEL_LAUNCH_CULL_W(KLV, 1); else if (narrow_cull) CHISEL_LAUNCH_CULL_W(KLV, 4); else CHISEL_LAUNCH_CULL_W(KLV, 16); } while (0)
         if (IP.n_frames <= 1) CHISEL_LAUNCH_CULL_W(1, 16);
@@ -882,7 +926,7 @@ int launch_group(chisel_hip_map *m, chisel_hip_map::BatchSet &bs, const PyramidP
         else CHISEL_LAUNCH_CULL(16);
 #undef CHISEL_LAUNCH_CULL_W
 #undef CHISEL_LAUNCH_CULL
-        m->launch_stats[5]++;
+        m->launch_stats[LS_CULL]++;
         narrow_cull_set = narrow_cull;
     }
     if (!inline_resolve && !(m->tune.ext_events && !m->profiling && !bs.staged)) HIP_TRY(hipEventRecord(bs.cull_done, front));  // the set's pending set is complete (wait_for_front_of)
@@ -890,7 +934,7 @@ int launch_group(chisel_hip_map *m, chisel_hip_map::BatchSet &bs, const PyramidP
         // per work item: which frames can touch which of its bricks (the cull test again at the scale of what a wave of the integration kernel
         // owns, kernels_cull.h).  One wave per item; their number is only known on the device: a persistent grid sized from a recent launch.
         ProfScope ps(m, CHISEL_HIP_KERNEL_RESOLVE, front);
-        const int items_hint = reinterpret_cast<volatile int *>(m->error_flag_host)[2];
+        const int items_hint = reinterpret_cast<volatile int *>(m->error_flag_host.get())[ST_ITEMS];
         // Shape.  Beside an integration kernel (80 registers, six single-wave workgroups per SIMD, every slot refilled the moment it frees up)
         // a workgroup of four waves waits for four free slots on ONE CU, i.e. for that kernel to drain (tools/micro/beside.hip: 145 us
         // instead of 17); single-wave workgroups get in at once -- and take the slots from the integration kernel for as long as they run.
@@ -903,11 +947,11 @@ int launch_group(chisel_hip_map *m, chisel_hip_map::BatchSet &bs, const PyramidP
         // behind it); the short form has no event at all (launch_seq).
         front_recorded = m->tune.ext_events && !m->profiling && !bs.staged && !inline_resolve;
         if (front_recorded)
-            hipExtLaunchKernelGGL((brick_kernel<N>), dim3(rgrid), dim3(rblock), 0, front, nullptr, bs.front_done, 0, IP, pyr, m->pyr_stride, (const WorkItem *)bs.items,
-                                  (const int *)(bs.cand_count + COUNT_ITEMS), m->items_capacity, bs.brick_masks, m->refine_off ? 1 : 0);
+            hipExtLaunchKernelGGL((brick_kernel<N>), dim3(rgrid), dim3(rblock), 0, front, nullptr, bs.front_done, 0, IP, pyr, m->pyr_stride, (const WorkItem *)bs.items.get(),
+                                  (const int *)(bs.cand_count.get() + COUNT_ITEMS), m->items_capacity, bs.brick_masks.get(), m->refine_off ? 1 : 0);
         else
-            hipLaunchKernelGGL((brick_kernel<N>), dim3(rgrid), dim3(rblock), 0, front, IP, pyr, m->pyr_stride, bs.items, bs.cand_count + COUNT_ITEMS, m->items_capacity,
-                               bs.brick_masks, m->refine_off ? 1 : 0);
+            hipLaunchKernelGGL((brick_kernel<N>), dim3(rgrid), dim3(rblock), 0, front, IP, pyr, m->pyr_stride, bs.items.get(), bs.cand_count.get() + COUNT_ITEMS, m->items_capacity,
+                               bs.brick_masks.get(), m->refine_off ? 1 : 0);
     }
     // The short form has no event: its kernels sit in front of the set's integration on the map's stream, and a later batch's front half on
     // another stream learns that they are over from the progress words (wait_for_front_of) -- an event carried by (or recorded behind) the
@@ -929,7 +973,7 @@ void launch_fixed_drop(chisel_hip_map *m, const int *latch) {
 // the integration of a set that was queued behind a recompute which then did not fit: its kernel left at once (MC_LATCH), here it is again
 int replay_deferred_set(chisel_hip_map *m, int set) {
     chisel_hip_map::BatchSet &bs = m->sets[set];
-    m->launch_stats[9]++;
+    m->launch_stats[LS_REPLAYED]++;
     switch (m->N) {
         case 8: return launch_back<8>(m, bs, bs.replay_ip, bs.replay_color, bs.replay_total, bs.replay_inline, true);
         case 16: return launch_back<16>(m, bs, bs.replay_ip, bs.replay_color, bs.replay_total, bs.replay_inline, true);
@@ -983,12 +1027,12 @@ int integrate_group(chisel_hip_map *m, int n, const chisel_hip_depth_frame *fram
     PP.W = W;
     PP.H = H;
     chisel_hip_map::BatchSet &bs = m->sets[m->batch_seq % CHISEL_FRONT_SETS];
-    bs.pending = m->pending_ring[m->batch_seq & (CHISEL_PENDING_RING - 1u)];
+    bs.pending = m->pending_ring[m->batch_seq & (CHISEL_PENDING_RING - 1u)].get();
     bs.staged = false;
     bs.caller_color = false;
     PP.rec_stride = (int)npx + 2;
     PP.pyr_stride = m->pyr_stride;
-    PP.rec = bs.rec_data + 2;
+    PP.rec = bs.rec_data.get() + 2;
     CP.n_frames = IP.n_frames = n;
     CP.pyr_stride = m->pyr_stride;
 
@@ -1006,9 +1050,7 @@ int integrate_group(chisel_hip_map *m, int n, const chisel_hip_depth_frame *fram
         rc = sync_all(m);
         if (rc) return rc;
         for (auto &b2 : m->sets) {
-            if (b2.depth_stage) HIP_TRY(hipFree(b2.depth_stage));
-            b2.depth_stage = nullptr;
-            HIP_TRY(hipMalloc(&b2.depth_stage, npx * KMAX * sizeof(float)));
+            HIP_TRY(b2.depth_stage.alloc(npx * KMAX));
         }
         m->depth_stage_elems = npx;
     }
@@ -1016,9 +1058,7 @@ int integrate_group(chisel_hip_map *m, int n, const chisel_hip_depth_frame *fram
         rc = sync_all(m);
         if (rc) return rc;
         for (auto &b2 : m->sets) {
-            if (b2.color_stage) HIP_TRY(hipFree(b2.color_stage));
-            b2.color_stage = nullptr;
-            HIP_TRY(hipMalloc(&b2.color_stage, color_bytes * KMAX));
+            HIP_TRY(b2.color_stage.alloc(color_bytes * KMAX));
         }
         m->color_stage_bytes = color_bytes;
     }
@@ -1092,7 +1132,7 @@ int integrate_group(chisel_hip_map *m, int n, const chisel_hip_depth_frame *fram
             if (mapped && !m->tune.no_zero_copy) {
                 PP.depth[k] = mapped;
             } else {
-                float *dst = bs.depth_stage + (size_t)k * m->depth_stage_elems;
+                float *dst = bs.depth_stage.get() + (size_t)k * m->depth_stage_elems;
                 HIP_TRY(hipMemcpyAsync(dst, f->depth, npx * sizeof(float), hipMemcpyHostToDevice, front));
                 PP.depth[k] = dst;
                 bs.staged = true;
@@ -1108,7 +1148,7 @@ int integrate_group(chisel_hip_map *m, int n, const chisel_hip_depth_frame *fram
                 F.color = c->color;
                 bs.caller_color = true;
             } else {
-                uint8_t *dst = bs.color_stage + (size_t)k * m->color_stage_bytes;
+                uint8_t *dst = bs.color_stage.get() + (size_t)k * m->color_stage_bytes;
                 HIP_TRY(hipMemcpyAsync(dst, c->color, (size_t)c->width * c->height * c->channels, hipMemcpyHostToDevice, front));
                 F.color = dst;
                 bs.staged = true;
@@ -1147,24 +1187,16 @@ int integrate_group(chisel_hip_map *m, int n, const chisel_hip_depth_frame *fram
         int cap = std::max(1 << 17, m->items_capacity);
         while (cap < total) cap *= 2;
         for (auto &b2 : m->sets) {
-            if (b2.boxes) HIP_TRY(hipFree(b2.boxes));
-            if (b2.brick_masks) HIP_TRY(hipFree(b2.brick_masks));
-            b2.brick_masks = nullptr;
-            if (b2.items) HIP_TRY(hipFree(b2.items));
-            if (b2.sync) HIP_TRY(hipFree(b2.sync));
-            b2.boxes = nullptr;
-            b2.items = nullptr;
-            b2.sync = nullptr;
-            HIP_TRY(hipMalloc(&b2.items, (size_t)cap * sizeof(WorkItem)));
-            HIP_TRY(hipMalloc(&b2.sync, (size_t)cap * sizeof(ItemSync)));
-            HIP_TRY(hipMalloc(&b2.boxes, (size_t)cap * KMAX * sizeof(FrameBox)));
-            HIP_TRY(hipMalloc(&b2.brick_masks, (size_t)cap * (m->N / 8) * (m->N / 8) * (m->N / 4) * sizeof(unsigned short)));
+            HIP_TRY(b2.items.alloc((size_t)cap));
+            HIP_TRY(b2.sync.alloc((size_t)cap));
+            HIP_TRY(b2.boxes.alloc((size_t)cap * KMAX));
+            HIP_TRY(b2.brick_masks.alloc((size_t)cap * (m->N / 8) * (m->N / 8) * (m->N / 4)));
         }
         m->items_capacity = cap;
     }
     {
         // (a launch set creates at most its work items' worth of chunks; the hint is a recent launch's count)
-        const int items_hint = reinterpret_cast<volatile int *>(m->error_flag_host)[2];
+        const int items_hint = reinterpret_cast<volatile int *>(m->error_flag_host.get())[ST_ITEMS];
         rc = maybe_grow(m, std::max<int64_t>(256, 2 * (int64_t)items_hint));
         if (rc) return rc;
     }
@@ -1214,8 +1246,8 @@ int integrate_frames(chisel_hip_map *m, int n, const chisel_hip_depth_frame *fra
 int fetch_listed(chisel_hip_map *m, bool dirty_only, std::vector<int> &ids, std::vector<int> *slots) {
     int rc = ensure_scratch(m, (size_t)m->view.max_chunks * 4 + 16);
     if (rc) return rc;
-    int *d_count = m->scratch_i;
-    int *d_ids = m->scratch_i + 16;
+    int *d_count = m->scratch_i.get();
+    int *d_ids = m->scratch_i.get() + 16;
     int *d_slots = d_ids + (size_t)m->view.max_chunks * 3;
     HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(int), m->stream));
     const int blocks = (m->view.max_chunks + 255) / 256;
@@ -1242,7 +1274,7 @@ int lookup_slots(chisel_hip_map *m, const int *ids, int n, std::vector<int> &slo
     if (n == 0) return CHISEL_HIP_OK;
     int rc = ensure_scratch(m, (size_t)n * 4);
     if (rc) return rc;
-    int *d_ids = m->scratch_i, *d_slots = m->scratch_i + (size_t)n * 3;
+    int *d_ids = m->scratch_i.get(), *d_slots = m->scratch_i.get() + (size_t)n * 3;
     HIP_TRY(hipMemcpyAsync(d_ids, ids, (size_t)n * 3 * sizeof(int), hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(lookup_kernel, dim3((n + 255) / 256), dim3(256), 0, m->stream, m->view, d_ids, n, d_slots);
     HIP_TRY(hipMemcpyAsync(slots.data(), d_slots, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, m->stream));
@@ -1350,17 +1382,8 @@ int chisel_hip_create(const chisel_hip_config *cfg, chisel_hip_map **out) {
     const int n_shards = cfg->n_shards < 1 ? 1 : cfg->n_shards;
     if (cfg->shard_rank < 0 || cfg->shard_rank >= n_shards) return fail(CHISEL_HIP_ERR_INVALID, "shard_rank out of range");
 
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (ndev <= 0) return fail(CHISEL_HIP_ERR_HIP, "no HIP device visible: libchisel_hip has no CPU path");
-    int dev = cfg->device_id;
-    if (dev < 0) HIP_TRY(hipGetDevice(&dev));
-    if (dev >= ndev) return fail(CHISEL_HIP_ERR_INVALID, "device_id out of range");
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, dev));
-    if (!strstr(prop.gcnArchName, "gfx950"))
-        return fail(CHISEL_HIP_ERR_HIP, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 (MI355X) only");
-    HIP_TRY(hipSetDevice(dev));
+    int dev = 0;
+    if (const int rc = open_device(cfg->device_id, &dev)) return rc;
 
     chisel_hip_map *m = new chisel_hip_map();
     m->cfg = *cfg;
@@ -1432,11 +1455,9 @@ int chisel_hip_create(const chisel_hip_config *cfg, chisel_hip_map **out) {
     }
     m->stream = m->own_stream;
     HIP_TRY_C(hipStreamCreateWithFlags(&m->copy_stream, hipStreamNonBlocking));
-    HIP_TRY_C(hipHostMalloc((void **)&m->mesh_totals_host, 16 * sizeof(int), hipHostMallocDefault));  // ([8..]: staging of small host values that are copied to the device asynchronously)
-    memset(m->mesh_totals_host, 0, 16 * sizeof(int));
-    HIP_TRY_C(hipHostGetDevicePointer((void **)&m->mesh_totals_dev, m->mesh_totals_host, 0));
-    HIP_TRY_C(hipHostMalloc((void **)&m->mesh_info_host, (size_t)MESH_INFO_PREFETCH * sizeof(JobInfo), hipHostMallocDefault));
-    HIP_TRY_C(hipHostGetDevicePointer((void **)&m->mesh_info_dev, m->mesh_info_host, 0));
+    HIP_TRY_C(m->mesh_totals_host.alloc(MH_INTS));
+    memset(m->mesh_totals_host.get(), 0, MH_INTS * sizeof(int));
+    HIP_TRY_C(m->mesh_info_host.alloc(MESH_INFO_PREFETCH));
     static_assert(sizeof(JobInfo) == 8 * sizeof(int), "the triangle kernel moves the records to the host as ints");
     HIP_TRY_C(hipEventCreateWithFlags(&m->call_event, hipEventDisableTiming));
     // A launch set's two events order kernels of ONE device across its streams: the agent-scope release every kernel ends with is all they
@@ -1450,13 +1471,13 @@ int chisel_hip_create(const chisel_hip_config *cfg, chisel_hip_map **out) {
     for (auto &bs : m->sets) {
         HIP_TRY_C(hipEventCreateWithFlags(&bs.front_done, set_event_flags));
         HIP_TRY_C(hipEventCreateWithFlags(&bs.cull_done, set_event_flags));
-        HIP_TRY_C(hipMalloc(&bs.cand_count, COUNT_INTS * sizeof(int)));
-        HIP_TRY_C(hipMemsetAsync(bs.cand_count, 0, COUNT_INTS * sizeof(int), m->own_stream));
+        HIP_TRY_C(bs.cand_count.alloc(COUNT_INTS));
+        HIP_TRY_C(hipMemsetAsync(bs.cand_count.get(), 0, COUNT_INTS * sizeof(int), m->own_stream));
     }
     for (auto &pr : m->pending_ring) {
-        HIP_TRY_C(hipMalloc(&pr, ((size_t)PENDING_CAPACITY + 1) * sizeof(uint64_t)));
-        HIP_TRY_C(hipMemsetAsync(pr, 0xff, (size_t)PENDING_CAPACITY * sizeof(uint64_t), m->own_stream));
-        HIP_TRY_C(hipMemsetAsync(pr + PENDING_CAPACITY, 0, sizeof(uint64_t), m->own_stream));
+        HIP_TRY_C(pr.alloc((size_t)PENDING_CAPACITY + 1));
+        HIP_TRY_C(hipMemsetAsync(pr.get(), 0xff, (size_t)PENDING_CAPACITY * sizeof(uint64_t), m->own_stream));
+        HIP_TRY_C(hipMemsetAsync(pr.get() + PENDING_CAPACITY, 0, sizeof(uint64_t), m->own_stream));
     }
     HIP_TRY_C(hipEventCreateWithFlags(&m->mutation_event, hipEventDisableTiming));
     m->mesh_tiny = getenv("CHISEL_HIP_MESH_TINY") != nullptr;
@@ -1486,9 +1507,10 @@ int chisel_hip_create(const chisel_hip_config *cfg, chisel_hip_map **out) {
     m->force_pipeline = m->force_uncertain || getenv("CHISEL_HIP_FORCE_PIPELINE") != nullptr;
     {
         const int one = 1;
-        HIP_TRY_C(hipMemcpyAsync(m->sets[0].cand_count + COUNT_ONE, &one, sizeof(int), hipMemcpyHostToDevice, m->own_stream));
+        HIP_TRY_C(hipMemcpyAsync(m->sets[0].cand_count.get() + COUNT_ONE, &one, sizeof(int), hipMemcpyHostToDevice, m->own_stream));
     }
     MapView &v = m->view;
+    chisel_hip_map::ViewMemory &vm = m->view_mem;
     v.max_chunks = (int)C;
     v.committed = (int)C0;
     v.hash_mask = hc - 1;
@@ -1537,24 +1559,24 @@ int chisel_hip_create(const chisel_hip_config *cfg, chisel_hip_map **out) {
         }
     }
     if (!m->growable) {
-        HIP_TRY_C(hipMalloc(&v.sdf, (size_t)v.committed * m->V * sizeof(float)));
-        HIP_TRY_C(hipMalloc(&v.wgt, (size_t)v.committed * m->V * sizeof(float)));
-        if (cfg->use_color) HIP_TRY_C(hipMalloc(&v.rgbw, (size_t)v.committed * m->V * sizeof(uchar4)));
+        HIP_TRY_C(alloc_viewed(vm.sdf, v.sdf, (size_t)v.committed * m->V));
+        HIP_TRY_C(alloc_viewed(vm.wgt, v.wgt, (size_t)v.committed * m->V));
+        if (cfg->use_color) HIP_TRY_C(alloc_viewed(vm.rgbw, v.rgbw, (size_t)v.committed * m->V));
     }
-    HIP_TRY_C(hipMalloc(&v.hash_keys, hc * sizeof(uint64_t)));
-    HIP_TRY_C(hipMalloc(&v.hash_vals, hc * sizeof(int)));
-    HIP_TRY_C(hipMalloc(&v.slot_key, (size_t)C * sizeof(uint64_t)));
+    HIP_TRY_C(alloc_viewed(vm.hash_keys, v.hash_keys, hc));
+    HIP_TRY_C(alloc_viewed(vm.hash_vals, v.hash_vals, hc));
+    HIP_TRY_C(alloc_viewed(vm.slot_key, v.slot_key, (size_t)C));
     HIP_TRY_C(hipMemsetAsync(v.slot_key, 0xff, (size_t)C * sizeof(uint64_t), m->stream));  // KEY_EMPTY: also the slots a growable pool has not committed yet
-    HIP_TRY_C(hipMalloc(&v.slot_dirty, (3 * (size_t)C + SLOT_SUMMARY_PAD) * sizeof(uint32_t)));  // flags, list of dirty slots, its length; sign summaries
+    HIP_TRY_C(alloc_viewed(vm.slot_dirty, v.slot_dirty, 3 * (size_t)C + SLOT_SUMMARY_PAD));  // flags, list of dirty slots, its length; sign summaries
     HIP_TRY_C(hipMemsetAsync(v.slot_dirty, 0, (3 * (size_t)C + SLOT_SUMMARY_PAD) * sizeof(uint32_t), m->stream));
-    HIP_TRY_C(hipMalloc(&v.free_list, (size_t)C * sizeof(int)));
-    HIP_TRY_C(hipMalloc(&v.free_top, sizeof(int)));
-    HIP_TRY_C(hipMalloc(&v.counters, 32 * sizeof(unsigned long long)));
-    HIP_TRY_C(hipMalloc(&v.block_counters, (size_t)INTEGRATE_MAX_GRID * 32 * sizeof(unsigned long long)));
+    HIP_TRY_C(alloc_viewed(vm.free_list, v.free_list, (size_t)C));
+    HIP_TRY_C(alloc_viewed(vm.free_top, v.free_top, 1));
+    HIP_TRY_C(alloc_viewed(vm.counters, v.counters, 32));
+    HIP_TRY_C(alloc_viewed(vm.block_counters, v.block_counters, (size_t)INTEGRATE_MAX_GRID * 32));
     HIP_TRY_C(hipMemsetAsync(v.block_counters, 0, (size_t)INTEGRATE_MAX_GRID * 32 * sizeof(unsigned long long), m->stream));
-    HIP_TRY_C(hipHostMalloc((void **)&m->error_flag_host, 16 * sizeof(int), hipHostMallocDefault));
-    memset(m->error_flag_host, 0, 16 * sizeof(int));
-    HIP_TRY_C(hipHostGetDevicePointer((void **)&v.error_flag, m->error_flag_host, 0));
+    HIP_TRY_C(m->error_flag_host.alloc(ST_INTS));
+    memset(m->error_flag_host.get(), 0, ST_INTS * sizeof(int));
+    v.error_flag = m->error_flag_host.dev();
     HIP_TRY_C(hipMemsetAsync(v.counters, 0, CHISEL_HIP_NUM_COUNTERS * sizeof(unsigned long long), m->stream));
     // the mesh recompute's job list, kept by the integration kernels (kernels_map.h: mesh_expand_dirty): a flag per slot, the ids of the
     // listed chunks (twice the pool: a removed chunk leaves its entry behind), the recompute totals + the list's length
@@ -1562,16 +1584,16 @@ int chisel_hip_create(const chisel_hip_config *cfg, chisel_hip_map **out) {
     // (a shard of a sharded map is meshed from a plan's job list, never from the kept one: without the flags mesh_expand_dirty returns at
     // once, and a newly dirtied chunk costs its wave no 27 hash probes)
     if (n_shards == 1) {
-        HIP_TRY_C(hipMalloc(&v.mesh_flag, C * sizeof(unsigned)));
+        HIP_TRY_C(alloc_viewed(vm.mesh_flag, v.mesh_flag, (size_t)C));
         HIP_TRY_C(hipMemsetAsync(v.mesh_flag, 0, C * sizeof(unsigned), m->stream));
     }
-    HIP_TRY_C(hipMalloc(&v.mesh_jobs, (size_t)v.mesh_jobs_capacity * 3 * sizeof(int)));
-    HIP_TRY_C(hipMalloc(&v.mesh_ctl, MC_INTS * sizeof(int)));
+    HIP_TRY_C(alloc_viewed(vm.mesh_jobs, v.mesh_jobs, (size_t)v.mesh_jobs_capacity * 3));
+    HIP_TRY_C(alloc_viewed(vm.mesh_ctl, v.mesh_ctl, MC_INTS));
     HIP_TRY_C(hipMemsetAsync(v.mesh_ctl, 0, MC_INTS * sizeof(int), m->stream));
-    m->mesh_buf.flags = v.mesh_flag;
+    m->mesh_buf.flags = v.mesh_flag;  // (the mesher's names for the two: it points at them, the map owns them)
     m->mesh_buf.totals = v.mesh_ctl;
-    HIP_TRY_C(hipMalloc(&m->view_dev, sizeof(MapView)));
-    HIP_TRY_C(hipMemcpyAsync(m->view_dev, &m->view, sizeof(MapView), hipMemcpyHostToDevice, m->stream));
+    HIP_TRY_C(m->view_dev.alloc(1));
+    HIP_TRY_C(hipMemcpyAsync(m->view_dev.get(), &m->view, sizeof(MapView), hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(reset_map_kernel, dim3(2048), dim3(256), 0, m->stream, m->view, m->V, 1);
     HIP_TRY_C(hipGetLastError());
     HIP_TRY_C(hipStreamSynchronize(m->stream));
@@ -1589,24 +1611,15 @@ int chisel_hip_destroy(chisel_hip_map *m) {
     if (!m) return CHISEL_HIP_OK;
     (void)hipSetDevice(m->device);
     if (m->stream) (void)sync_all(m);
-    MapView &v = m->view;
-    if (m->pool_mem[0].base) {  // (a growable pool: mapped ranges, not allocations)
-        for (auto &A : m->pool_mem) pool_release(A);
-        v.sdf = nullptr; v.wgt = nullptr; v.rgbw = nullptr;
-    }
-    void *ptrs[] = {v.sdf, v.wgt, v.rgbw, v.hash_keys, v.hash_vals, v.slot_key, v.slot_dirty, v.free_list, v.free_top,
-                    v.counters, v.block_counters, m->view_dev, m->scratch_i, v.mesh_jobs};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
+    // memory: the growable pool's mapped ranges and the pooled mesh arenas are released by their own protocols, every other buffer by its
+    // owner, with the map (delete, below); the map's own stream goes last
+    for (auto &A : m->pool_mem) pool_release(A);
+    clear_meshes(m);
+    release_arena_pool(m);
     for (auto &bs : m->sets) {
-        void *bp[] = {bs.pyr_data, bs.rec_data, bs.depth_stage, bs.color_stage, bs.boxes, bs.brick_masks, bs.cand_count, bs.items, bs.sync};
-        for (void *p : bp)
-            if (p) (void)hipFree(p);
         if (bs.front_done) (void)hipEventDestroy(bs.front_done);
         if (bs.cull_done) (void)hipEventDestroy(bs.cull_done);
     }
-    for (auto &pr : m->pending_ring)
-        if (pr) (void)hipFree(pr);
     for (hipEvent_t e : m->order_events)
         if (e) (void)hipEventDestroy(e);
     if (m->call_event) (void)hipEventDestroy(m->call_event);
@@ -1615,24 +1628,14 @@ int chisel_hip_destroy(chisel_hip_map *m) {
     if (m->aux2) (void)hipStreamDestroy(m->aux2);
     if (m->aux3) (void)hipStreamDestroy(m->aux3);
     if (m->copy_stream) (void)hipStreamDestroy(m->copy_stream);
-    if (m->mesh_totals_host) (void)hipHostFree(m->mesh_totals_host);
-    if (m->error_flag_host) (void)hipHostFree(m->error_flag_host);
-    if (m->mesh_info_host) (void)hipHostFree(m->mesh_info_host);
-    if (m->dirty_tail_host) (void)hipHostFree(m->dirty_tail_host);
-    if (m->shell_plan_host) (void)hipHostFree(m->shell_plan_host);
-    for (void *p : {(void *)m->shell_plan.jobset, (void *)m->shell_plan.my_jobs, (void *)m->shell_plan.ctl, (void *)m->shell_plan.send_items})
-        if (p) (void)hipFree(p);
-    clear_meshes(m);
-    release_arena_pool(m);
-    free_mesh_buffers(m->mesh_buf);
-    free_cloud_buffers(m->cloud);
     for (const ProfEvent &p : m->prof_live) {
         (void)hipEventDestroy(p.start);
         (void)hipEventDestroy(p.stop);
     }
     for (hipEvent_t e : m->event_pool) (void)hipEventDestroy(e);
-    if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
+    const hipStream_t own_stream = m->own_stream;
     delete m;
+    if (own_stream) (void)hipStreamDestroy(own_stream);
     return CHISEL_HIP_OK;
 }
 
@@ -1801,7 +1804,7 @@ int chisel_hip_garbage_collect(chisel_hip_map *m, const int *ids, int n) {
     }
     rc = ensure_scratch(m, (size_t)n * 3 + 16);
     if (rc) return rc;
-    int *d_cnt = m->scratch_i, *d_ids = m->scratch_i + 16;
+    int *d_cnt = m->scratch_i.get(), *d_ids = m->scratch_i.get() + 16;
     HIP_TRY(hipMemsetAsync(d_cnt, 0, sizeof(int), m->stream));
     HIP_TRY(hipMemcpyAsync(d_ids, ids, (size_t)n * 3 * sizeof(int), hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(remove_chunks_kernel, dim3(n), dim3(256), 0, m->stream, m->view, d_ids, n, d_cnt, m->V);
@@ -1920,27 +1923,23 @@ int chisel_hip_condition_depth(const double *src, int w0, int h0, int src_on_dev
     if (!src || !dst || w0 <= 0 || h0 <= 0 || w <= 0 || h <= 0) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t n0 = (size_t)w0 * h0, n1 = (size_t)w * h;
-    double *d_src = nullptr;
-    float *d_dst = nullptr;
+    DeviceBuffer<double> d_src;
+    DeviceBuffer<float> d_dst;
     const double *in = src;
     float *out = dst;
     if (!src_on_device) {
-        HIP_TRY(hipMalloc(&d_src, n0 * sizeof(double)));
-        HIP_TRY(hipMemcpyAsync(d_src, src, n0 * sizeof(double), hipMemcpyHostToDevice, st));
-        in = d_src;
+        HIP_TRY(d_src.alloc(n0));
+        HIP_TRY(hipMemcpyAsync(d_src.get(), src, n0 * sizeof(double), hipMemcpyHostToDevice, st));
+        in = d_src.get();
     }
     if (!dst_on_device) {
-        HIP_TRY(hipMalloc(&d_dst, n1 * sizeof(float)));
-        out = d_dst;
+        HIP_TRY(d_dst.alloc(n1));
+        out = d_dst.get();
     }
     hipLaunchKernelGGL(condition_depth_kernel, dim3((w + 255) / 256, h), dim3(256), 0, st, in, w0, h0, out, w, h);
     HIP_TRY(hipGetLastError());
-    if (!dst_on_device) HIP_TRY(hipMemcpyAsync(dst, d_dst, n1 * sizeof(float), hipMemcpyDeviceToHost, st));
-    if (!src_on_device || !dst_on_device) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (d_src) (void)hipFree(d_src);
-        if (d_dst) (void)hipFree(d_dst);
-    }
+    if (!dst_on_device) HIP_TRY(hipMemcpyAsync(dst, d_dst.get(), n1 * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (!src_on_device || !dst_on_device) HIP_TRY(hipStreamSynchronize(st));  // (the staging buffers go with this call)
     if (K) {  // collaborative_server_system.cpp:216-219
         K[0] = K[0] / (double)w0 * (double)w;
         K[2] = K[2] / (double)w0 * (double)w;
@@ -1958,26 +1957,22 @@ int chisel_hip_condition_color(const uint8_t *src, int w0, int h0, int channels,
         return fail(CHISEL_HIP_ERR_INVALID, "image too large");
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t n0 = (size_t)w0 * h0 * channels, n1 = (size_t)w * h * channels;
-    uint8_t *d_src = nullptr, *d_dst = nullptr;
+    DeviceBuffer<uint8_t> d_src, d_dst;
     const uint8_t *in = src;
     uint8_t *out = dst;
     if (!src_on_device) {
-        HIP_TRY(hipMalloc(&d_src, n0));
-        HIP_TRY(hipMemcpyAsync(d_src, src, n0, hipMemcpyHostToDevice, st));
-        in = d_src;
+        HIP_TRY(d_src.alloc(n0));
+        HIP_TRY(hipMemcpyAsync(d_src.get(), src, n0, hipMemcpyHostToDevice, st));
+        in = d_src.get();
     }
     if (!dst_on_device) {
-        HIP_TRY(hipMalloc(&d_dst, n1));
-        out = d_dst;
+        HIP_TRY(d_dst.alloc(n1));
+        out = d_dst.get();
     }
     hipLaunchKernelGGL(condition_color_kernel, dim3((w * channels + 255) / 256, h), dim3(256), 0, st, in, w0, h0, channels, out, w, h);
     HIP_TRY(hipGetLastError());
-    if (!dst_on_device) HIP_TRY(hipMemcpyAsync(dst, d_dst, n1, hipMemcpyDeviceToHost, st));
-    if (!src_on_device || !dst_on_device) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (d_src) (void)hipFree(d_src);
-        if (d_dst) (void)hipFree(d_dst);
-    }
+    if (!dst_on_device) HIP_TRY(hipMemcpyAsync(dst, d_dst.get(), n1, hipMemcpyDeviceToHost, st));
+    if (!src_on_device || !dst_on_device) HIP_TRY(hipStreamSynchronize(st));  // (the staging buffers go with this call)
     return CHISEL_HIP_OK;
 }
 
@@ -1986,619 +1981,37 @@ int chisel_hip_publish_cloud(const double *depth, const uint8_t *color, int w, i
     if (!depth || !color || !points || w <= 0 || h <= 0 || color_step < w) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t npx = (size_t)w * h, cbytes = (size_t)color_step * h;
-    double *d_depth = nullptr;
-    uint8_t *d_color = nullptr;
-    uint4 *d_pts = nullptr;
+    DeviceBuffer<double> d_depth;
+    DeviceBuffer<uint8_t> d_color;
+    DeviceBuffer<uint4> d_pts;
     const double *in_d = depth;
     const uint8_t *in_c = color;
     uint4 *out = static_cast<uint4 *>(points);
     if (!src_on_device) {
-        HIP_TRY(hipMalloc(&d_depth, npx * sizeof(double)));
-        HIP_TRY(hipMalloc(&d_color, cbytes));
-        HIP_TRY(hipMemcpyAsync(d_depth, depth, npx * sizeof(double), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_color, color, cbytes, hipMemcpyHostToDevice, st));
-        in_d = d_depth;
-        in_c = d_color;
+        HIP_TRY(d_depth.alloc(npx));
+        HIP_TRY(d_color.alloc(cbytes));
+        HIP_TRY(hipMemcpyAsync(d_depth.get(), depth, npx * sizeof(double), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_color.get(), color, cbytes, hipMemcpyHostToDevice, st));
+        in_d = d_depth.get();
+        in_c = d_color.get();
     }
     if (!dst_on_device) {
-        HIP_TRY(hipMalloc(&d_pts, npx * sizeof(uint4)));
-        out = d_pts;
+        HIP_TRY(d_pts.alloc(npx));
+        out = d_pts.get();
     }
     hipLaunchKernelGGL(publish_cloud_kernel, dim3((w + 255) / 256, h), dim3(256), 0, st, in_d, in_c, w, h, color_step, out);
     HIP_TRY(hipGetLastError());
-    if (!dst_on_device) HIP_TRY(hipMemcpyAsync(points, d_pts, npx * sizeof(uint4), hipMemcpyDeviceToHost, st));
-    if (!src_on_device || !dst_on_device) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (d_depth) (void)hipFree(d_depth);
-        if (d_color) (void)hipFree(d_color);
-        if (d_pts) (void)hipFree(d_pts);
-    }
+    if (!dst_on_device) HIP_TRY(hipMemcpyAsync(points, d_pts.get(), npx * sizeof(uint4), hipMemcpyDeviceToHost, st));
+    if (!src_on_device || !dst_on_device) HIP_TRY(hipStreamSynchronize(st));  // (the staging buffers go with this call)
     return CHISEL_HIP_OK;
 }
 
-// ---- DepthFilter (depth_filter.cpp) ----------------------------------------------------------------------------------------
-struct chisel_hip_depth_filter {
-    int device = 0;
-    int height = 0, width = 0;
-    FilterView view{};
-    double *stage_mu = nullptr, *stage_cov = nullptr, *stage_out = nullptr;  // host arrays pass through these
-};
-int chisel_hip_depth_filter_create(int height, int width, int device_id, chisel_hip_depth_filter **out) {
-    if (!out || height <= 0 || width <= 0 || (int64_t)height * width > (1 << 28)) return fail(CHISEL_HIP_ERR_INVALID, "bad filter size");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(CHISEL_HIP_ERR_HIP, "no HIP device (there is no CPU path)");
-    if (device_id < 0) (void)hipGetDevice(&device_id);
-    if (device_id >= n_dev) return fail(CHISEL_HIP_ERR_INVALID, "bad device id");
-    HIP_TRY(hipSetDevice(device_id));
-    chisel_hip_depth_filter *f = new chisel_hip_depth_filter();
-    f->device = device_id; f->height = height; f->width = width;
-    const size_t n = (size_t)height * width;
-    f->view.n = (int)n;
-    f->view.inv_depth_range = 100 - 0.01;  // m_nMaxInvDepth - m_nMinInvDepth, depth_filter.cpp:138-141
-    double **arrays[] = {&f->view.a, &f->view.b, &f->view.mu, &f->view.cov, &f->stage_mu, &f->stage_cov, &f->stage_out};
-    for (double **p : arrays)
-        if (hipMalloc(p, n * sizeof(double)) != hipSuccess) {
-            chisel_hip_depth_filter_destroy(f);
-            return fail(CHISEL_HIP_ERR_HIP, "hipMalloc failed");
-        }
-    hipLaunchKernelGGL(filter_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, f->view);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    *out = f;
-    return CHISEL_HIP_OK;
-}
-int chisel_hip_depth_filter_destroy(chisel_hip_depth_filter *f) {
-    if (!f) return CHISEL_HIP_OK;
-    (void)hipSetDevice(f->device);
-    (void)hipDeviceSynchronize();
-    void *ptrs[] = {f->view.a, f->view.b, f->view.mu, f->view.cov, f->stage_mu, f->stage_cov, f->stage_out};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    delete f;
-    return CHISEL_HIP_OK;
-}
-int chisel_hip_depth_filter_update(chisel_hip_depth_filter *f, const double *mu, const double *cov, double cov_all, int reciprocal,
-                                   int on_device) {
-    if (!f || !mu) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(f->device));
-    const size_t n = (size_t)f->view.n;
-    const double *d_mu = mu, *d_cov = cov;
-    if (!on_device) {
-        HIP_TRY(hipMemcpyAsync(f->stage_mu, mu, n * sizeof(double), hipMemcpyHostToDevice, 0));
-        d_mu = f->stage_mu;
-        if (cov) {
-            HIP_TRY(hipMemcpyAsync(f->stage_cov, cov, n * sizeof(double), hipMemcpyHostToDevice, 0));
-            d_cov = f->stage_cov;
-        }
-    }
-    hipLaunchKernelGGL(filter_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, f->view, d_mu, d_cov, cov_all, reciprocal);
-    HIP_TRY(hipGetLastError());
-    return CHISEL_HIP_OK;  // stream 0: ordered against the next call; reads wait
-}
-int chisel_hip_depth_filter_read(chisel_hip_depth_filter *f, int which, double *dst, int dst_on_device) {
-    if (!f || !dst || which < 0 || which > 6) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
-    HIP_TRY(hipSetDevice(f->device));
-    const size_t n = (size_t)f->view.n;
-    double *d_out = dst_on_device ? dst : f->stage_out;
-    hipLaunchKernelGGL(filter_read_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, f->view, which, d_out);
-    HIP_TRY(hipGetLastError());
-    if (!dst_on_device) HIP_TRY(hipMemcpyAsync(dst, d_out, n * sizeof(double), hipMemcpyDeviceToHost, 0));
-    HIP_TRY(hipStreamSynchronize(0));
-    return CHISEL_HIP_OK;
-}
+}  // extern "C"
 
-// ---- StereoMapper (sgm_stereo_mapper.cpp, calc_cost.cu) ---------------------------------------------------------------------
-struct chisel_hip_stereo {
-    int device = 0;
-    int width = 0, height = 0;
-    int measurement_cnt = 0;  // m_nMeasurementCount: reset by InitReference only (sgm_stereo_mapper.cpp:121)
-    bool has_reference = false;
-    StereoParams prm{};
-    StereoView view{};
-    float *ref = nullptr, *match = nullptr, *p2w = nullptr;
-    float *stage_a = nullptr, *stage_b = nullptr;  // host sparse maps pass through these
-    double *stage_out = nullptr;                   // read-out 3 to the host
-    // the raw-image path (chisel_hip_stereo_set_camera and after): allocated by the first set_camera
-    bool has_camera = false;
-    int real_w = 0, real_h = 0;
-    double K1[4] = {}, K2[4] = {};                   // fx, fy, cx, cy scaled to the work size (InitIntrinsic)
-    short2 *map_xy[2] = {};                          // undistort maps of camera 1 (reference) and 2 (match), CV_16SC2 + CV_16UC1
-    uint16_t *map_f[2] = {};
-    uint8_t *raw = nullptr;                          // real_w x real_h input staged contiguous
-    uint8_t *small = nullptr;                        // the W x H resize
-    int *sob_g = nullptr, *sob_x = nullptr, *sob_y = nullptr;
-    long long *sob_partials = nullptr;
-    StereoPrepStats *stats = nullptr;
-    uint8_t *mask_x = nullptr, *mask_y = nullptr;
-    float *sparse_depth = nullptr, *sparse_dist = nullptr;
-    double *pts_depth = nullptr, *pts_xy = nullptr;  // bound points (BindSparsePoints)
-    SparsePoint *pts = nullptr;
-    int n_points = 0, pts_cap = 0;
-    float *depth_real = nullptr;                     // Output's result at the camera size
-    double *stage_real = nullptr;                    // read-out 5 to the host
-};
+#include "host_filter.h"
+#include "host_stereo.h"
 
-void chisel_hip_stereo_default_params(chisel_hip_stereo_params *p) {
-    if (!p) return;
-    // dense_mapping_parameters.cpp:3-11; DEP_SAMPLE = 1.0f / (BASE_LINE * FOCAL), dense_mapping_parameters.h:24,36-37
-    const float focal = (float)((461.6 + 460.3) / 2);
-    const float base_line = 0.11f;
-    *p = {16.0f, 64.0f, 8.0f, 1.0f, 1.0f, 1.0f, 15.0f, 1.0f / (base_line * focal)};
-}
-
-int chisel_hip_stereo_create(int width, int height, const chisel_hip_stereo_params *p, int device_id, chisel_hip_stereo **out) {
-    if (!out || width < 2 || height < 2 || width > 16384 || height > 16384 || (int64_t)width * height > (1 << 24))
-        return fail(CHISEL_HIP_ERR_INVALID, "bad stereo size");
-    chisel_hip_stereo_params prm;
-    if (p) prm = *p;
-    else chisel_hip_stereo_default_params(&prm);
-    if (!(prm.dep_sample > 0.0f) || !(prm.sgm_q1 != 0.0f) || !(prm.sgm_q2 != 0.0f)) return fail(CHISEL_HIP_ERR_INVALID, "bad stereo parameters");
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return fail(CHISEL_HIP_ERR_HIP, "no HIP device (there is no CPU path)");
-    if (device_id < 0) HIP_TRY(hipGetDevice(&device_id));
-    if (device_id >= n_dev) return fail(CHISEL_HIP_ERR_INVALID, "bad device id");
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, device_id));
-    if (!strstr(prop.gcnArchName, "gfx950"))
-        return fail(CHISEL_HIP_ERR_HIP, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 (MI355X) only");
-    HIP_TRY(hipSetDevice(device_id));
-    chisel_hip_stereo *s = new chisel_hip_stereo();
-    s->device = device_id; s->width = width; s->height = height;
-    s->prm = {prm.pi1, prm.pi2, prm.tau_so, prm.sgm_q1, prm.sgm_q2, prm.var_scale, prm.sparse_ratio, prm.dep_sample};
-    const size_t n = (size_t)width * height, nv = n * STEREO_DEP_CNT;
-    bool ok = hipMalloc(&s->ref, n * sizeof(float)) == hipSuccess && hipMalloc(&s->match, n * sizeof(float)) == hipSuccess &&
-              hipMalloc(&s->p2w, n * sizeof(float)) == hipSuccess && hipMalloc(&s->stage_a, n * sizeof(float)) == hipSuccess &&
-              hipMalloc(&s->stage_b, n * sizeof(float)) == hipSuccess && hipMalloc(&s->stage_out, n * sizeof(double)) == hipSuccess &&
-              hipMalloc(&s->view.cost, nv * sizeof(float)) == hipSuccess && hipMalloc(&s->view.sgm, nv * sizeof(float)) == hipSuccess &&
-              hipMalloc(&s->view.depth, n * sizeof(float)) == hipSuccess;
-    if (!ok) {
-        chisel_hip_stereo_destroy(s);
-        return fail(CHISEL_HIP_ERR_HIP, "hipMalloc failed");
-    }
-    s->view.w = width; s->view.h = height;
-    s->view.ref = s->ref; s->view.match = s->match; s->view.p2w = s->p2w;
-    // every image and volume starts zeroed, as after ClearRawCost
-    hipError_t e = hipSuccess;
-    const std::pair<void *, size_t> zeroed[] = {{s->ref, n * sizeof(float)},       {s->match, n * sizeof(float)},
-                                                {s->p2w, n * sizeof(float)},       {s->view.cost, nv * sizeof(float)},
-                                                {s->view.sgm, nv * sizeof(float)}, {s->view.depth, n * sizeof(float)}};
-    for (const auto &z : zeroed)
-        if (e == hipSuccess) e = hipMemsetAsync(z.first, 0, z.second, 0);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) {
-        chisel_hip_stereo_destroy(s);
-        return fail(CHISEL_HIP_ERR_HIP, std::string("zeroing the stereo state: ") + hipGetErrorString(e));
-    }
-    *out = s;
-    return CHISEL_HIP_OK;
-}
-
-int chisel_hip_stereo_destroy(chisel_hip_stereo *s) {
-    if (!s) return CHISEL_HIP_OK;
-    (void)hipSetDevice(s->device);
-    (void)hipDeviceSynchronize();
-    void *ptrs[] = {s->ref,       s->match,     s->p2w,      s->stage_a,      s->stage_b,   s->stage_out, s->view.cost,
-                    s->view.sgm,  s->view.depth, s->map_xy[0], s->map_xy[1],   s->map_f[0],  s->map_f[1],  s->raw,
-                    s->small,     s->sob_g,     s->sob_x,    s->sob_y,        s->sob_partials, s->stats,  s->mask_x,
-                    s->mask_y,    s->sparse_depth, s->sparse_dist, s->pts_depth, s->pts_xy,  s->pts,       s->depth_real,
-                    s->stage_real};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    delete s;
-    return CHISEL_HIP_OK;
-}
-
-static int stereo_upload(float *dst, const float *src, size_t n, int on_device) {
-    HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(float), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, 0));
-    return CHISEL_HIP_OK;
-}
-
-int chisel_hip_stereo_set_reference(chisel_hip_stereo *s, const float *ref, const float *p2_weight, int on_device) {
-    if (!s || !ref || !p2_weight) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t n = (size_t)s->width * s->height;
-    int rc = stereo_upload(s->ref, ref, n, on_device);
-    if (rc == CHISEL_HIP_OK) rc = stereo_upload(s->p2w, p2_weight, n, on_device);
-    if (rc != CHISEL_HIP_OK) return rc;
-    if (!on_device) HIP_TRY(hipStreamSynchronize(0));
-    s->measurement_cnt = 0;
-    s->has_reference = true;
-    return CHISEL_HIP_OK;
-}
-
-// Update's cost pass (sgm_stereo_mapper.cpp:153, :184-195) on the match image already in s->match
-static int stereo_run_cost(chisel_hip_stereo *s, const float R[9], const float t[3]) {
-    const size_t n = (size_t)s->width * s->height;
-    StereoPose P;
-    memcpy(P.r, R, sizeof(P.r));
-    memcpy(P.t, t, sizeof(P.t));
-    s->measurement_cnt++;
-    hipLaunchKernelGGL(stereo_cost_kernel, dim3((unsigned)((n + 1) / 2)), dim3(256), 0, 0, s->view, P, s->measurement_cnt, s->prm.dep_sample);
-    HIP_TRY(hipGetLastError());
-    return CHISEL_HIP_OK;
-}
-
-int chisel_hip_stereo_update(chisel_hip_stereo *s, const float *match, const float R[9], const float t[3], int on_device) {
-    if (!s || !match || !R || !t) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
-    if (!s->has_reference) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_stereo_update before chisel_hip_stereo_set_reference");
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t n = (size_t)s->width * s->height;
-    int rc = stereo_upload(s->match, match, n, on_device);
-    if (rc == CHISEL_HIP_OK) rc = stereo_run_cost(s, R, t);
-    if (rc != CHISEL_HIP_OK) return rc;
-    if (!on_device) HIP_TRY(hipStreamSynchronize(0));  // the host image may go once this returns
-    return CHISEL_HIP_OK;  // stream 0: ordered against the next call; reads wait
-}
-
-// Output's device half (sgm_stereo_mapper.cpp:366-382): FuseSparseInfo when given device sparse maps, then SGM and WTA
-static int stereo_run_output(chisel_hip_stereo *s, const float *dd, const float *ds) {
-    const int W = s->width, H = s->height;
-    const size_t n = (size_t)W * H, nv = n * STEREO_DEP_CNT;
-    if (dd) {
-        hipLaunchKernelGGL(stereo_fuse_sparse_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, 0, s->view, dd, ds,
-                           s->prm.sparse_ratio, s->prm.dep_sample);
-        HIP_TRY(hipGetLastError());
-    }
-    // sgm2 (calc_cost.cu:507-546): right, left, down, up, in that order, each adding its path costs to the volume; the first
-    // writes, which equals adding to the zeroed volume of sgm_stereo_mapper.cpp:371
-    const SgmScan passes[4] = {
-        {H, W, W, 1, 0},
-        {H, W, W, -1, W - 1},
-        {W, H, 1, W, 0},
-        {W, H, 1, -W, (H - 1) * W},
-    };
-    for (int k = 0; k < 4; ++k) {
-        const dim3 grid((unsigned)((passes[k].n_lines + 3) / 4));
-        if (k == 0) hipLaunchKernelGGL(stereo_sgm_kernel<true>, grid, dim3(256), 0, 0, s->view, passes[k], s->prm);
-        else hipLaunchKernelGGL(stereo_sgm_kernel<false>, grid, dim3(256), 0, 0, s->view, passes[k], s->prm);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(stereo_wta_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, 0, s->view, s->prm.var_scale, s->prm.dep_sample);
-    HIP_TRY(hipGetLastError());
-    return CHISEL_HIP_OK;
-}
-
-int chisel_hip_stereo_output(chisel_hip_stereo *s, const float *sparse_depth, const float *sparse_dist, int on_device) {
-    if (!s || (!sparse_depth) != (!sparse_dist)) return fail(CHISEL_HIP_ERR_INVALID, "bad argument (sparse depth and distance go together)");
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t n = (size_t)s->width * s->height;
-    // FuseSparseInfo (sgm_stereo_mapper.cpp:366-368); without a prior every nDepth is -1 and it changes nothing
-    const float *dd = sparse_depth, *ds = sparse_dist;
-    if (sparse_depth && !on_device) {
-        HIP_TRY(hipMemcpyAsync(s->stage_a, sparse_depth, n * sizeof(float), hipMemcpyHostToDevice, 0));
-        HIP_TRY(hipMemcpyAsync(s->stage_b, sparse_dist, n * sizeof(float), hipMemcpyHostToDevice, 0));
-        dd = s->stage_a;
-        ds = s->stage_b;
-    }
-    const int rc = stereo_run_output(s, dd, ds);
-    if (rc != CHISEL_HIP_OK) return rc;
-    if (sparse_depth && !on_device) HIP_TRY(hipStreamSynchronize(0));
-    return CHISEL_HIP_OK;
-}
-
-int chisel_hip_stereo_clear(chisel_hip_stereo *s) {
-    if (!s) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t n = (size_t)s->width * s->height, nv = n * STEREO_DEP_CNT;
-    HIP_TRY(hipMemsetAsync(s->view.cost, 0, nv * sizeof(float), 0));
-    HIP_TRY(hipMemsetAsync(s->view.sgm, 0, nv * sizeof(float), 0));
-    HIP_TRY(hipMemsetAsync(s->view.depth, 0, n * sizeof(float), 0));
-    return CHISEL_HIP_OK;  // the measurement count stays (sgm_stereo_mapper.cpp:202-216)
-}
-
-int chisel_hip_stereo_read(chisel_hip_stereo *s, int which, void *dst, int dst_on_device) {
-    if (!s || !dst || which < 0 || which > 5) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
-    if (which >= 4 && !s->has_camera) return fail(CHISEL_HIP_ERR_INVALID, "read-outs 4 and 5 are at the camera size: chisel_hip_stereo_set_camera first");
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t n = (size_t)s->width * s->height, n_real = (size_t)s->real_w * s->real_h;
-    const hipMemcpyKind kind = dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    if (which == 0) HIP_TRY(hipMemcpyAsync(dst, s->view.cost, n * STEREO_DEP_CNT * sizeof(float), kind, 0));
-    else if (which == 1) HIP_TRY(hipMemcpyAsync(dst, s->view.sgm, n * STEREO_DEP_CNT * sizeof(float), kind, 0));
-    else if (which == 2) HIP_TRY(hipMemcpyAsync(dst, s->view.depth, n * sizeof(float), kind, 0));
-    else if (which == 4) HIP_TRY(hipMemcpyAsync(dst, s->depth_real, n_real * sizeof(float), kind, 0));
-    else {
-        const float *src = which == 3 ? s->view.depth : s->depth_real;
-        const size_t m = which == 3 ? n : n_real;
-        double *d_out = dst_on_device ? static_cast<double *>(dst) : (which == 3 ? s->stage_out : s->stage_real);
-        hipLaunchKernelGGL(stereo_widen_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, 0, src, d_out, (int)m);
-        HIP_TRY(hipGetLastError());
-        if (!dst_on_device) HIP_TRY(hipMemcpyAsync(dst, d_out, m * sizeof(double), hipMemcpyDeviceToHost, 0));
-    }
-    HIP_TRY(hipStreamSynchronize(0));
-    return CHISEL_HIP_OK;
-}
-
-// ---- the raw-image path: InitIntrinsic, InitReference, Update, BindSparsePoints, Output with their OpenCV work on the device ------
-// cv::invert(DECOMP_LU) of a 3 x 3 CV_64F matrix takes a closed form (core/src/lapack.cpp, cv::invert, n == 3): det3 expanded
-// along the first row, d = 1. / det, then every entry of the adjugate (2 x 2 cofactor differences) times d.  false: det == 0.
-static bool stereo_invert3(const double *m, double *o) {
-#define M_(i, j) m[(i) * 3 + (j)]
-    double d = M_(0, 0) * (M_(1, 1) * M_(2, 2) - M_(1, 2) * M_(2, 1)) - M_(0, 1) * (M_(1, 0) * M_(2, 2) - M_(1, 2) * M_(2, 0)) +
-               M_(0, 2) * (M_(1, 0) * M_(2, 1) - M_(1, 1) * M_(2, 0));
-    if (d == 0.) return false;
-    d = 1. / d;
-    o[0] = (M_(1, 1) * M_(2, 2) - M_(1, 2) * M_(2, 1)) * d;
-    o[1] = (M_(0, 2) * M_(2, 1) - M_(0, 1) * M_(2, 2)) * d;
-    o[2] = (M_(0, 1) * M_(1, 2) - M_(0, 2) * M_(1, 1)) * d;
-    o[3] = (M_(1, 2) * M_(2, 0) - M_(1, 0) * M_(2, 2)) * d;
-    o[4] = (M_(0, 0) * M_(2, 2) - M_(0, 2) * M_(2, 0)) * d;
-    o[5] = (M_(0, 2) * M_(1, 0) - M_(0, 0) * M_(1, 2)) * d;
-    o[6] = (M_(1, 0) * M_(2, 1) - M_(1, 1) * M_(2, 0)) * d;
-    o[7] = (M_(0, 1) * M_(2, 0) - M_(0, 0) * M_(2, 1)) * d;
-    o[8] = (M_(0, 0) * M_(1, 1) - M_(0, 1) * M_(1, 0)) * d;
-#undef M_
-    return true;
-}
-
-// 3 x 3 times 3 x cols (cols 3 or 1), every entry a0 b0 + a1 b1 + a2 b2 left to right; bt: b is 3 x 3 and used transposed
-static void stereo_mul3(const double *a, const double *b, int cols, bool bt, double *o) {
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < cols; ++j) {
-            const double b0 = bt ? b[j * 3 + 0] : b[0 * cols + j], b1 = bt ? b[j * 3 + 1] : b[1 * cols + j], b2 = bt ? b[j * 3 + 2] : b[2 * cols + j];
-            o[i * cols + j] = a[i * 3 + 0] * b0 + a[i * 3 + 1] * b1 + a[i * 3 + 2] * b2;
-        }
-}
-
-int chisel_hip_stereo_homography(const double K1[4], const double K2[4], const double Rr[9], const double tr[3], const double Rm[9],
-                                 const double tm[3], float R[9], float t[3]) {
-    if (!K1 || !K2 || !Rr || !tr || !Rm || !tm || !R || !t) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
-    const double k1[9] = {K1[0], 0.0, K1[2], 0.0, K1[1], K1[3], 0.0, 0.0, 1.0};
-    const double k2[9] = {K2[0], 0.0, K2[2], 0.0, K2[1], K2[3], 0.0, 0.0, 1.0};
-    double k1i[9], a[9], b[9], r[9], tt[3];
-    if (!stereo_invert3(k1, k1i)) return fail(CHISEL_HIP_ERR_INVALID, "K1 is singular");
-    stereo_mul3(k2, Rm, 3, true, a);  // K2 * Rm.t()
-    stereo_mul3(a, Rr, 3, false, b);  // * Rr
-    stereo_mul3(b, k1i, 3, false, r); // * K1.inv()
-    const double d[3] = {tr[0] - tm[0], tr[1] - tm[1], tr[2] - tm[2]};
-    stereo_mul3(a, d, 1, false, tt);  // K2 * Rm.t() * (tr - tm)
-    for (int k = 0; k < 9; ++k) R[k] = (float)r[k];
-    for (int k = 0; k < 3; ++k) t[k] = (float)tt[k];
-    return CHISEL_HIP_OK;
-}
-
-// cvRound as x86-64 computes it (cvtsd2si): round half to even; NaN and values outside int give INT_MIN
-static int stereo_cv_round(double v) {
-    return (v >= -2147483648.5 && v < 2147483647.5) ? (int)std::nearbyint(v) : INT32_MIN;
-}
-
-// cv::undistort(src, dst, K, D, K) of OpenCV 4 (imgproc/src/undistort.dispatch.cpp), its map restated from the scalar loop of
-// initUndistortRectifyMap with R = I and map type CV_16SC2: the rows go in stripes of min(max(1, 4096 / cols), rows); in each,
-// Ar(1,2) = v0 - y and ir = Ar^-1 (stereo_invert3; Ar * I is Ar bit for bit); per row i of the stripe _x, _y, _w start at
-// i * ir[1] + ir[2], i * ir[4] + ir[5], i * ir[7] + ir[8] and get += ir[0], ir[3], ir[6] column by column; w = 1. / _w,
-// x = _x * w, y = _y * w; kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2) with k4..k6 = 0;
-// xd = x kr + p1 2xy + p2 (r2 + 2 x2), yd = y kr + p1 (r2 + 2 y2) + p2 2xy (the thin-prism terms s1..s4 are 0 and the tilt is the
-// identity: they change at most the sign of a zero, which u = fx xd + u0 removes); u, v with fx, fy, u0, v0 of the unmodified
-// A; iu = cvRound(u * 32), iv = cvRound(v * 32); map (short)(iu >> 5), (short)(iv >> 5) and (iv & 31) * 32 + (iu & 31).
-static void stereo_undistort_map(int W, int H, const double K[4], const double D[5], short2 *xy, uint16_t *f) {
-    const double fx = K[0], fy = K[1], u0 = K[2], v0 = K[3];
-    const double k1 = D[0], k2 = D[1], p1 = D[2], p2 = D[3], k3 = D[4], k4 = 0.0, k5 = 0.0, k6 = 0.0;
-    const int stripe0 = std::min(std::max(1, 4096 / std::max(W, 1)), H);
-    for (int y = 0; y < H; y += stripe0) {
-        const int rows = std::min(stripe0, H - y);
-        const double Ar[9] = {fx, 0.0, u0, 0.0, fy, v0 - y, 0.0, 0.0, 1.0};
-        double ir[9];
-        if (!stereo_invert3(Ar, ir)) std::fill(ir, ir + 9, 0.0);  // cv::invert leaves a singular matrix's inverse zeroed
-        for (int i = 0; i < rows; ++i) {
-            double _x = i * ir[1] + ir[2], _y = i * ir[4] + ir[5], _w = i * ir[7] + ir[8];
-            for (int j = 0; j < W; ++j, _x += ir[0], _y += ir[3], _w += ir[6]) {
-                const double w = 1. / _w, x = _x * w, yy = _y * w;
-                const double x2 = x * x, y2 = yy * yy;
-                const double r2 = x2 + y2, _2xy = 2 * x * yy;
-                const double kr = (1 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2);
-                const double xd = x * kr + p1 * _2xy + p2 * (r2 + 2 * x2);
-                const double yd = yy * kr + p1 * (r2 + 2 * y2) + p2 * _2xy;
-                const double u = fx * xd + u0, v = fy * yd + v0;
-                const int iu = stereo_cv_round(u * 32), iv = stereo_cv_round(v * 32);
-                const size_t k = (size_t)(y + i) * W + j;
-                xy[k] = make_short2((short)(iu >> 5), (short)(iv >> 5));
-                f[k] = (uint16_t)((iv & 31) * 32 + (iu & 31));
-            }
-        }
-    }
-}
-
-static int stereo_alloc(void **p, size_t bytes, bool zero) {
-    if (*p) return CHISEL_HIP_OK;
-    HIP_TRY(hipMalloc(p, bytes));
-    if (zero) HIP_TRY(hipMemset(*p, 0, bytes));
-    return CHISEL_HIP_OK;
-}
-
-static void stereo_free(void **p) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-}
-
-int chisel_hip_stereo_set_camera(chisel_hip_stereo *s, int real_w, int real_h, const double K1[4], const double D1[5], const double K2[4],
-                                 const double D2[5]) {
-    if (!s || !K1 || !D1 || !K2 || !D2) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
-    if (real_w < 2 || real_h < 2 || real_w > 16384 || real_h > 16384 || (int64_t)real_w * real_h > (1 << 26))
-        return fail(CHISEL_HIP_ERR_INVALID, "bad camera image size");
-    const int W = s->width, H = s->height;
-    if (W < 9 || H < 9) return fail(CHISEL_HIP_ERR_INVALID, "the raw-image path needs a work size of at least 9 x 9 (the border of the 9-tap Sobel)");
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipDeviceSynchronize());  // buffers below may be in use by queued work
-    const size_t n = (size_t)W * H, n_real = (size_t)real_w * real_h;
-    const size_t n_blocks = (size_t)((W + SOBEL_TILE - 1) / SOBEL_TILE) * ((H + SOBEL_TILE - 1) / SOBEL_TILE);
-    if (s->real_w != real_w || s->real_h != real_h) {
-        stereo_free((void **)&s->raw);
-        stereo_free((void **)&s->depth_real);
-        stereo_free((void **)&s->stage_real);
-    }
-    struct {
-        void **p;
-        size_t bytes;
-        bool zero;
-    } bufs[] = {
-        {(void **)&s->map_xy[0], n * sizeof(short2), false}, {(void **)&s->map_xy[1], n * sizeof(short2), false},
-        {(void **)&s->map_f[0], n * sizeof(uint16_t), false}, {(void **)&s->map_f[1], n * sizeof(uint16_t), false},
-        {(void **)&s->small, n, false},                        {(void **)&s->sob_g, n * sizeof(int), false},
-        {(void **)&s->sob_x, n * sizeof(int), false},           {(void **)&s->sob_y, n * sizeof(int), false},
-        {(void **)&s->sob_partials, n_blocks * SOBEL_N_STATS * sizeof(long long), false},
-        {(void **)&s->stats, sizeof(StereoPrepStats), true},    {(void **)&s->mask_x, n, true},
-        {(void **)&s->mask_y, n, true},                         {(void **)&s->sparse_depth, n * sizeof(float), false},
-        {(void **)&s->sparse_dist, n * sizeof(float), false},   {(void **)&s->raw, n_real, false},
-        {(void **)&s->depth_real, n_real * sizeof(float), true}, {(void **)&s->stage_real, n_real * sizeof(double), false},
-    };
-    for (const auto &b : bufs) {
-        const int rc = stereo_alloc(b.p, b.bytes, b.zero);
-        if (rc != CHISEL_HIP_OK) return rc;  // what was allocated stays with s (destroy frees it); the camera is not set
-    }
-    // InitIntrinsic (sgm_stereo_mapper.cpp:31-45): fx, cx / (real_w / W), fy, cy / (real_h / H)
-    const double sx = (double)real_w / (double)W, sy = (double)real_h / (double)H;
-    const double k1[4] = {K1[0] / sx, K1[1] / sy, K1[2] / sx, K1[3] / sy}, k2[4] = {K2[0] / sx, K2[1] / sy, K2[2] / sx, K2[3] / sy};
-    std::vector<short2> xy(n);
-    std::vector<uint16_t> f(n);
-    for (int c = 0; c < 2; ++c) {
-        stereo_undistort_map(W, H, c == 0 ? k1 : k2, c == 0 ? D1 : D2, xy.data(), f.data());
-        HIP_TRY(hipMemcpy(s->map_xy[c], xy.data(), n * sizeof(short2), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(s->map_f[c], f.data(), n * sizeof(uint16_t), hipMemcpyHostToDevice));
-    }
-    memcpy(s->K1, k1, sizeof(k1));
-    memcpy(s->K2, k2, sizeof(k2));
-    s->real_w = real_w;
-    s->real_h = real_h;
-    s->has_camera = true;
-    return CHISEL_HIP_OK;
-}
-
-// cv::resize of the real_w x real_h mono8 image to W x H (condition_color_kernel), then cv::undistort with camera `cam` and
-// convertTo(CV_32F) into dst
-static int stereo_prepare(chisel_hip_stereo *s, const uint8_t *img, int step, int on_device, int cam, float *dst) {
-    const int W = s->width, H = s->height, w0 = s->real_w, h0 = s->real_h;
-    const uint8_t *src = img;
-    if (!on_device || step != w0) {
-        HIP_TRY(hipMemcpy2DAsync(s->raw, w0, img, step, w0, h0, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, 0));
-        src = s->raw;
-    }
-    hipLaunchKernelGGL(condition_color_kernel, dim3((W + 255) / 256, H), dim3(256), 0, 0, src, w0, h0, 1, s->small, W, H);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(stereo_remap_kernel, dim3((unsigned)(((size_t)W * H + 255) / 256)), dim3(256), 0, 0, s->small, W, H, s->map_xy[cam],
-                       s->map_f[cam], dst);
-    HIP_TRY(hipGetLastError());
-    return CHISEL_HIP_OK;
-}
-
-static int stereo_check_image(chisel_hip_stereo *s, const uint8_t *img, int step, const char *what) {
-    if (!s || !img) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
-    if (!s->has_camera) return fail(CHISEL_HIP_ERR_INVALID, std::string(what) + " before chisel_hip_stereo_set_camera");
-    if (step < s->real_w) return fail(CHISEL_HIP_ERR_INVALID, "row step shorter than the camera image");
-    return CHISEL_HIP_OK;
-}
-
-int chisel_hip_stereo_set_reference_image(chisel_hip_stereo *s, const uint8_t *img, int step, int on_device) {
-    int rc = stereo_check_image(s, img, step, "chisel_hip_stereo_set_reference_image");
-    if (rc != CHISEL_HIP_OK) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    const int W = s->width, H = s->height, n = W * H;
-    rc = stereo_prepare(s, img, step, on_device, 0, s->ref);
-    if (rc != CHISEL_HIP_OK) return rc;
-    const dim3 tiles((W + SOBEL_TILE - 1) / SOBEL_TILE, (H + SOBEL_TILE - 1) / SOBEL_TILE);
-    hipLaunchKernelGGL(stereo_sobel_kernel, tiles, dim3(256), 0, 0, s->ref, W, H, s->sob_g, s->sob_x, s->sob_y, s->sob_partials);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(stereo_prep_stats_kernel, dim3(1), dim3(256), 0, 0, s->sob_partials, (int)(tiles.x * tiles.y), n, s->stats);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(stereo_prep_finish_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, s->sob_g, s->sob_x, s->sob_y, s->stats, n, s->p2w,
-                       s->mask_x, s->mask_y);
-    HIP_TRY(hipGetLastError());
-    if (!on_device) HIP_TRY(hipStreamSynchronize(0));
-    s->measurement_cnt = 0;  // sgm_stereo_mapper.cpp:121
-    s->has_reference = true;
-    return CHISEL_HIP_OK;
-}
-
-int chisel_hip_stereo_update_image(chisel_hip_stereo *s, const uint8_t *img, int step, const double ref_R_wc[9], const double ref_t_wc[3],
-                                   const double match_R_wc[9], const double match_t_wc[3], int on_device) {
-    int rc = stereo_check_image(s, img, step, "chisel_hip_stereo_update_image");
-    if (rc != CHISEL_HIP_OK) return rc;
-    if (!ref_R_wc || !ref_t_wc || !match_R_wc || !match_t_wc) return fail(CHISEL_HIP_ERR_INVALID, "null pose");
-    if (!s->has_reference) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_stereo_update_image before a reference image");
-    float R[9], t[3];
-    rc = chisel_hip_stereo_homography(s->K1, s->K2, ref_R_wc, ref_t_wc, match_R_wc, match_t_wc, R, t);  // :179-182
-    if (rc != CHISEL_HIP_OK) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    rc = stereo_prepare(s, img, step, on_device, 1, s->match);
-    if (rc == CHISEL_HIP_OK) rc = stereo_run_cost(s, R, t);
-    if (rc != CHISEL_HIP_OK) return rc;
-    if (!on_device) HIP_TRY(hipStreamSynchronize(0));
-    return CHISEL_HIP_OK;
-}
-
-int chisel_hip_stereo_bind_sparse_points(chisel_hip_stereo *s, const double *depth, const double *xy, int n) {
-    if (!s || n < 0 || n > (1 << 24) || (n > 0 && (!depth || !xy))) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
-    if (!s->has_camera) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_stereo_bind_sparse_points before chisel_hip_stereo_set_camera");
-    HIP_TRY(hipSetDevice(s->device));
-    if (n > s->pts_cap) {
-        HIP_TRY(hipDeviceSynchronize());  // a queued Output may still read the old points
-        stereo_free((void **)&s->pts_depth);
-        stereo_free((void **)&s->pts_xy);
-        stereo_free((void **)&s->pts);
-        s->pts_cap = 0;
-        const int cap = std::max(n, 1024);
-        int rc = stereo_alloc((void **)&s->pts_depth, (size_t)cap * sizeof(double), false);
-        if (rc == CHISEL_HIP_OK) rc = stereo_alloc((void **)&s->pts_xy, (size_t)cap * 2 * sizeof(double), false);
-        if (rc == CHISEL_HIP_OK) rc = stereo_alloc((void **)&s->pts, (size_t)cap * sizeof(SparsePoint), false);
-        if (rc != CHISEL_HIP_OK) {
-            s->n_points = 0;
-            return rc;
-        }
-        s->pts_cap = cap;
-    }
-    if (n > 0) {  // hipMemcpy from pageable memory: ordered after queued work, done when it returns (BindSparsePoints copies)
-        HIP_TRY(hipMemcpy(s->pts_depth, depth, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(s->pts_xy, xy, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice));
-    }
-    s->n_points = n;
-    return CHISEL_HIP_OK;
-}
-
-static SparseRatios stereo_sparse_ratios() {
-    SparseRatios R;
-    for (int u = -SPARSE_WIN; u <= SPARSE_WIN; ++u)
-        for (int v = -SPARSE_WIN; v <= SPARSE_WIN; ++v) {
-            double r = (1.0 - (std::sqrt((double)(u * u + v * v)) / (SPARSE_WIN * 1.414)));  // sgm_stereo_mapper.cpp:346-347
-            r = r * r;
-            const int b = (u + SPARSE_WIN) * SPARSE_SIDE + (v + SPARSE_WIN);
-            R.ratio[b] = r;
-            R.stored[b] = (float)(r * r);  // :350
-        }
-    return R;
-}
-
-int chisel_hip_stereo_output_image(chisel_hip_stereo *s) {
-    if (!s) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
-    if (!s->has_camera) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_stereo_output_image before chisel_hip_stereo_set_camera");
-    HIP_TRY(hipSetDevice(s->device));
-    const int W = s->width, H = s->height, n = s->n_points;
-    static const SparseRatios ratios = stereo_sparse_ratios();
-    // 1. the sparse prior (:229-357): -1 / 0 where no point writes
-    if (n > 0) {
-        hipLaunchKernelGGL(stereo_sparse_points_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, s->pts_depth, s->pts_xy, n, W, H,
-                           (double)s->real_h / (double)H, (double)s->real_w / (double)W, s->mask_x, s->mask_y, s->pts);
-        HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(stereo_sparse_raster_kernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(256), 0, 0, s->pts, n, W, H, ratios,
-                       s->sparse_depth, s->sparse_dist);
-    HIP_TRY(hipGetLastError());
-    // 2-4. FuseSparseInfo (all -1 without points: it changes nothing and is skipped), SGM, WTA
-    const int rc = stereo_run_output(s, n > 0 ? s->sparse_depth : nullptr, s->sparse_dist);
-    if (rc != CHISEL_HIP_OK) return rc;
-    // 5. cv::resize to the camera size (:409)
-    hipLaunchKernelGGL(stereo_resize_f32_kernel, dim3((s->real_w + 255) / 256, s->real_h), dim3(256), 0, 0, s->view.depth, W, H, s->depth_real,
-                       s->real_w, s->real_h);
-    HIP_TRY(hipGetLastError());
-    return CHISEL_HIP_OK;
-}
-
-int chisel_hip_debug_stereo_prep(chisel_hip_stereo *s, int which, void *dst) {
-    if (!s || !dst || which < 0 || which > 6) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
-    if (which >= 3 && !s->has_camera) return fail(CHISEL_HIP_ERR_INVALID, "no camera set");
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t n = (size_t)s->width * s->height;
-    const void *src[7] = {s->ref, s->match, s->p2w, s->mask_x, s->mask_y, s->sparse_depth, s->sparse_dist};
-    HIP_TRY(hipMemcpy(dst, src[which], n * (which == 3 || which == 4 ? 1 : sizeof(float)), hipMemcpyDeviceToHost));
-    return CHISEL_HIP_OK;
-}
+extern "C" {
 
 int chisel_hip_drop_ghost_chunks(chisel_hip_map *m) {
     SETTLE(m);
@@ -2642,10 +2055,7 @@ int chisel_hip_dirty_ids_device(chisel_hip_map *m, int *out_dev, int capacity) {
     HIP_TRY(hipSetDevice(m->device));
     // meshesToUpdate entries kept on the host (27-neighbourhoods of chunks removed while dirty) come first, as entries that are not
     // expanded again (flag 1); the kernel appends the dirty chunks (flag 0) behind them
-    if (m->input_event) {  // chisel_hip_wait_event: the caller's buffer is ready behind this event (its allocator's stream, not the map's)
-        HIP_TRY(hipStreamWaitEvent(m->stream, m->input_event, 0));
-        m->input_event = nullptr;
-    }
+    if (const int rc_in = wait_for_input(m, m->stream)) return rc_in;
     // out[0] is the TRUE number of entries -- host-held ones and the kernel's appends -- also when it exceeds `capacity` (only the first
     // `capacity` are stored): a caller that reads out[0] > capacity grows its buffer and asks again; a count capped at the capacity
     // would have looked like a list that just fits, and the entries beyond it would have been dropped for good
@@ -2670,25 +2080,20 @@ namespace {
 int ensure_shell_plan(chisel_hip_map *m, int jobset_capacity, int send_capacity) {
     ShellPlan &S = m->shell_plan;
     if (!S.ctl) {
-        HIP_TRY(hipMalloc(&S.ctl, (16 + 4 * SHELL_MAX_SHARDS + 4) * sizeof(int)));  // ctl[16] | send_cur[64] (64-bit) | recv_cnt[64] (64-bit) | ghost chunks created so far (64-bit, never zeroed)
+        HIP_TRY(alloc_viewed(m->shell_mem.ctl, S.ctl, 16 + 4 * SHELL_MAX_SHARDS + 4));  // ctl[16] | send_cur[64] (64-bit) | recv_cnt[64] (64-bit) | ghost chunks created so far (64-bit, never zeroed)
         HIP_TRY(hipMemsetAsync(S.ctl, 0, (16 + 4 * SHELL_MAX_SHARDS + 4) * sizeof(int), m->stream));
         S.send_cur = reinterpret_cast<unsigned long long *>(S.ctl + 16);
         S.recv_cnt = S.send_cur + SHELL_MAX_SHARDS;
-        HIP_TRY(hipHostMalloc((void **)&m->shell_plan_host, (16 + 4 * SHELL_MAX_SHARDS + 4) * sizeof(int), hipHostMallocDefault));
-        HIP_TRY(hipHostGetDevicePointer((void **)&m->shell_plan_host_dev, m->shell_plan_host, 0));
+        HIP_TRY(m->shell_plan_host.alloc(16 + 4 * SHELL_MAX_SHARDS + 4));
     }
     if (jobset_capacity > S.jobset_capacity) {
         HIP_TRY(hipStreamSynchronize(m->stream));
-        if (S.jobset) HIP_TRY(hipFree(S.jobset));
-        S.jobset = nullptr;
-        HIP_TRY(hipMalloc(&S.jobset, 2 * (size_t)jobset_capacity * sizeof(unsigned long long)));  // (the set, then the list)
+        HIP_TRY(alloc_viewed(m->shell_mem.jobset, S.jobset, 2 * (size_t)jobset_capacity));  // (the set, then the list)
         S.jobset_capacity = jobset_capacity;
     }
     if (send_capacity > S.send_capacity) {
         HIP_TRY(hipStreamSynchronize(m->stream));
-        if (S.send_items) HIP_TRY(hipFree(S.send_items));
-        S.send_items = nullptr;
-        HIP_TRY(hipMalloc(&S.send_items, (size_t)send_capacity * 8 * sizeof(int)));
+        HIP_TRY(alloc_viewed(m->shell_mem.send_items, S.send_items, (size_t)send_capacity * 8));
         S.send_capacity = send_capacity;
     }
     return CHISEL_HIP_OK;
@@ -2708,10 +2113,7 @@ int chisel_hip_shell_plan_device(chisel_hip_map *m, const int *gathered_dev, int
     HIP_TRY(hipSetDevice(m->device));
     int rc = ensure_mesh_jobs(m, m->view.committed);
     if (rc) return rc;
-    if (m->input_event) {
-        HIP_TRY(hipStreamWaitEvent(m->stream, m->input_event, 0));
-        m->input_event = nullptr;
-    }
+    if (const int rc_in = wait_for_input(m, m->stream)) return rc_in;
     int jobset_capacity = std::max(m->shell_plan.jobset_capacity, 1 << 15), send_capacity = std::max(m->shell_plan.send_capacity, 1 << 15);
     for (int attempt = 0;; attempt++) {
         rc = ensure_shell_plan(m, jobset_capacity, send_capacity);
@@ -2719,9 +2121,7 @@ int chisel_hip_shell_plan_device(chisel_hip_map *m, const int *gathered_dev, int
         ShellPlan &S = m->shell_plan;
         if (!S.my_jobs || S.max_jobs < m->mesh_buf.capacity) {
             HIP_TRY(hipStreamSynchronize(m->stream));
-            if (S.my_jobs) HIP_TRY(hipFree(S.my_jobs));
-            S.my_jobs = nullptr;
-            HIP_TRY(hipMalloc(&S.my_jobs, (size_t)m->mesh_buf.capacity * 3 * sizeof(int)));
+            HIP_TRY(alloc_viewed(m->shell_mem.my_jobs, S.my_jobs, (size_t)m->mesh_buf.capacity * 3));
             S.max_jobs = m->mesh_buf.capacity;
         }
         HIP_TRY(hipMemsetAsync(S.jobset, 0xff, (size_t)S.jobset_capacity * sizeof(unsigned long long), m->stream));
@@ -2730,10 +2130,10 @@ int chisel_hip_shell_plan_device(chisel_hip_map *m, const int *gathered_dev, int
         hipLaunchKernelGGL(shell_jobs_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, m->stream, gathered_dev, world, cap, S, m->cfg.n_shards, m->cfg.shard_rank, m->cfg.shard_block);
         hipLaunchKernelGGL(shell_items_kernel, dim3((unsigned)std::min(S.jobset_capacity / 8, 1024)), dim3(256), 0, m->stream, S, m->N, m->cfg.n_shards, m->cfg.shard_rank, m->cfg.shard_block);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(m->shell_plan_host_dev, S.ctl, (16 + 4 * SHELL_MAX_SHARDS + 4) * sizeof(int), hipMemcpyDeviceToDevice, m->stream));
+        HIP_TRY(hipMemcpyAsync(m->shell_plan_host.dev(), S.ctl, (16 + 4 * SHELL_MAX_SHARDS + 4) * sizeof(int), hipMemcpyDeviceToDevice, m->stream));
         HIP_TRY(wait_stream_spinning(m->stream));
         std::atomic_thread_fence(std::memory_order_acquire);
-        const int *h = m->shell_plan_host;
+        const int *h = m->shell_plan_host.get();
         if (h[2] > cap) {  // the gathered list itself was cut off: the caller's turn
             out[0] = out[1] = out[3] = 0;
             out[2] = h[2];
@@ -2744,7 +2144,7 @@ int chisel_hip_shell_plan_device(chisel_hip_map *m, const int *gathered_dev, int
         jobset_capacity = 2 * S.jobset_capacity;
         send_capacity = std::max(2 * S.send_capacity, 2 * h[3]);
     }
-    const int *h = m->shell_plan_host;
+    const int *h = m->shell_plan_host.get();
     const unsigned long long *cur = reinterpret_cast<const unsigned long long *>(h + 16);
     m->shell_jobs = h[0];
     m->shell_send_items = h[3];
@@ -2778,10 +2178,7 @@ int chisel_hip_export_shells_packed(chisel_hip_map *m, void *out_dev, int64_t by
         int rc_m = check_mesh_totals(m);
         if (rc_m) return rc_m;
     }
-    if (m->input_event) {
-        HIP_TRY(hipStreamWaitEvent(m->stream, m->input_event, 0));
-        m->input_event = nullptr;
-    }
+    if (const int rc_in = wait_for_input(m, m->stream)) return rc_in;
     hipLaunchKernelGGL(shell_export_kernel, dim3((unsigned)std::max(1, m->shell_send_items)), dim3(256), 0, m->stream, m->view, m->shell_plan, m->N, m->cfg.n_shards,
                        static_cast<unsigned char *>(out_dev), 0ll, 0, (int *)nullptr);
     HIP_TRY(hipGetLastError());
@@ -2811,10 +2208,7 @@ int chisel_hip_import_shells_packed(chisel_hip_map *m, const void *in_dev, int64
     { m->topology_epoch++; m->dirty_tail_queued = false; }
     int rc = check_mesh_totals(m);
     if (rc) return rc;
-    if (m->input_event) {
-        HIP_TRY(hipStreamWaitEvent(m->stream, m->input_event, 0));
-        m->input_event = nullptr;
-    }
+    if (const int rc_in = wait_for_input(m, m->stream)) return rc_in;
     if (items > 0) {
         rc = maybe_grow(m, items);  // (ghosts take slots of this shard's pool until they are dropped again)
         if (rc) return rc;
@@ -2848,18 +2242,13 @@ int chisel_hip_shell_plan_queue(chisel_hip_map *m, const int *gathered_dev, int 
     if (rc) return rc;
     rc = ensure_mesh_jobs(m, m->view.committed);
     if (rc) return rc;
-    if (m->input_event) {
-        HIP_TRY(hipStreamWaitEvent(m->stream, m->input_event, 0));
-        m->input_event = nullptr;
-    }
+    if (const int rc_in = wait_for_input(m, m->stream)) return rc_in;
     rc = ensure_shell_plan(m, std::max(m->shell_plan.jobset_capacity, 1 << 15), std::max(m->shell_plan.send_capacity, 1 << 15));
     if (rc) return rc;
     ShellPlan &S = m->shell_plan;
     if (!S.my_jobs || S.max_jobs < m->mesh_buf.capacity) {
         HIP_TRY(hipStreamSynchronize(m->stream));
-        if (S.my_jobs) HIP_TRY(hipFree(S.my_jobs));
-        S.my_jobs = nullptr;
-        HIP_TRY(hipMalloc(&S.my_jobs, (size_t)m->mesh_buf.capacity * 3 * sizeof(int)));
+        HIP_TRY(alloc_viewed(m->shell_mem.my_jobs, S.my_jobs, (size_t)m->mesh_buf.capacity * 3));
         S.max_jobs = m->mesh_buf.capacity;
     }
     HIP_TRY(hipMemsetAsync(S.jobset, 0xff, (size_t)S.jobset_capacity * sizeof(unsigned long long), m->stream));
@@ -2883,10 +2272,7 @@ int chisel_hip_import_shells_fixed(chisel_hip_map *m, const void *in_dev, int64_
     if (!m || !in_dev || !status_dev || seg_stride != m->shell_stride || !m->shell_plan.my_jobs) return fail(CHISEL_HIP_ERR_INVALID, "bad argument (chisel_hip_shell_plan_queue first)");
     HIP_TRY(hipSetDevice(m->device));
     { m->topology_epoch++; m->dirty_tail_queued = false; }
-    if (m->input_event) {
-        HIP_TRY(hipStreamWaitEvent(m->stream, m->input_event, 0));
-        m->input_event = nullptr;
-    }
+    if (const int rc_in = wait_for_input(m, m->stream)) return rc_in;
     int rc = maybe_grow(m, std::max(256, 2 * items_hint));  // (ghosts take slots of this shard's pool until they are dropped again)
     if (rc) return rc;
     const unsigned char *in = static_cast<const unsigned char *>(in_dev);
@@ -3095,9 +2481,9 @@ int chisel_hip_upload_chunk(chisel_hip_map *m, const int id[3], const float *sdf
     if (rc) return rc;
     rc = ensure_free_exact(m, 1);
     if (rc) return rc;
-    hipLaunchKernelGGL(ensure_chunk_kernel, dim3(1), dim3(1), 0, m->stream, m->view, id[0], id[1], id[2], m->scratch_i);
+    hipLaunchKernelGGL(ensure_chunk_kernel, dim3(1), dim3(1), 0, m->stream, m->view, id[0], id[1], id[2], m->scratch_i.get());
     int slot = -1;
-    HIP_TRY(hipMemcpyAsync(&slot, m->scratch_i, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+    HIP_TRY(hipMemcpyAsync(&slot, m->scratch_i.get(), sizeof(int), hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));
     if (slot < 0) return check_device_error(m) ? CHISEL_HIP_ERR_POOL_FULL : fail(CHISEL_HIP_ERR_POOL_FULL, "no slot");
     const size_t off = (size_t)slot * m->V;
@@ -3156,21 +2542,20 @@ int chisel_hip_meshes_to_update_since(chisel_hip_map *m, uint64_t cursor[2], int
     const bool restart = (cursor[0] >> 32) != epoch_tag;
     unsigned from = restart ? 0u : (unsigned)(cursor[0] & 0xffffffffull);
     if (!m->dirty_tail_host) {
-        HIP_TRY(hipHostMalloc((void **)&m->dirty_tail_host, (2 + 3 * (size_t)DIRTY_TAIL_CAP) * sizeof(int), hipHostMallocDefault));
-        HIP_TRY(hipHostGetDevicePointer((void **)&m->dirty_tail_dev, m->dirty_tail_host, 0));
+        HIP_TRY(m->dirty_tail_host.alloc(2 + 3 * (size_t)DIRTY_TAIL_CAP));
     }
     // (the kernel may have been queued behind the integration already -- chisel_hip_meshes_to_update_prefetch -- and the caller's wait for the
     // integration then covered it: no launch and no second wait here)
     const bool prefetched = m->dirty_tail_queued && !restart && m->dirty_tail_cursor == cursor[0] && m->dirty_tail_batch == m->batch_seq;
     m->dirty_tail_queued = false;
     if (!prefetched) {
-        hipLaunchKernelGGL(list_dirty_tail_kernel, dim3(1), dim3(256), 0, m->stream, m->view, from, m->dirty_tail_dev, DIRTY_TAIL_CAP);
+        hipLaunchKernelGGL(list_dirty_tail_kernel, dim3(1), dim3(256), 0, m->stream, m->view, from, m->dirty_tail_host.dev(), DIRTY_TAIL_CAP);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(wait_stream_spinning(m->stream));
     std::atomic_thread_fence(std::memory_order_acquire);
-    const unsigned listed = (unsigned)m->dirty_tail_host[0];
-    const int n_new = m->dirty_tail_host[1];
+    const unsigned listed = (unsigned)m->dirty_tail_host.get()[0];
+    const int n_new = m->dirty_tail_host.get()[1];
     std::unordered_set<uint64_t, IdHash> joined;
     bool whole = restart;
     if (listed > (unsigned)m->view.max_chunks || n_new > DIRTY_TAIL_CAP) {
@@ -3181,7 +2566,7 @@ int chisel_hip_meshes_to_update_since(chisel_hip_map *m, uint64_t cursor[2], int
         expand27(dirty, joined);
         whole = true;
     } else {
-        std::vector<int> fresh(m->dirty_tail_host + 2, m->dirty_tail_host + 2 + 3 * (size_t)n_new);
+        std::vector<int> fresh(m->dirty_tail_host.get() + 2, m->dirty_tail_host.get() + 2 + 3 * (size_t)n_new);
         expand27(fresh, joined);
     }
     if (whole || cursor[1] != m->pending_version) joined.insert(m->pending_mesh_ids.begin(), m->pending_mesh_ids.end());
@@ -3208,10 +2593,9 @@ int chisel_hip_meshes_to_update_prefetch(chisel_hip_map *m, const uint64_t curso
     if ((cursor[0] >> 32) != (uint64_t)m->dirty_epoch + 1u) return CHISEL_HIP_OK;  // (the set was emptied since: the _since call starts over)
     HIP_TRY(hipSetDevice(m->device));
     if (!m->dirty_tail_host) {
-        HIP_TRY(hipHostMalloc((void **)&m->dirty_tail_host, (2 + 3 * (size_t)DIRTY_TAIL_CAP) * sizeof(int), hipHostMallocDefault));
-        HIP_TRY(hipHostGetDevicePointer((void **)&m->dirty_tail_dev, m->dirty_tail_host, 0));
+        HIP_TRY(m->dirty_tail_host.alloc(2 + 3 * (size_t)DIRTY_TAIL_CAP));
     }
-    hipLaunchKernelGGL(list_dirty_tail_kernel, dim3(1), dim3(256), 0, m->stream, m->view, (unsigned)(cursor[0] & 0xffffffffull), m->dirty_tail_dev, DIRTY_TAIL_CAP);
+    hipLaunchKernelGGL(list_dirty_tail_kernel, dim3(1), dim3(256), 0, m->stream, m->view, (unsigned)(cursor[0] & 0xffffffffull), m->dirty_tail_host.dev(), DIRTY_TAIL_CAP);
     HIP_TRY(hipGetLastError());
     m->dirty_tail_queued = true;
     m->dirty_tail_cursor = cursor[0];
@@ -3320,18 +2704,17 @@ int chisel_hip_mc_tables(int *triangle_table, int *edge_index_pairs) {
 int chisel_hip_mesh_cube_values(const float *vertex_coords, const float *vertex_sdf, float *edge_coords, int *configuration, float *vertices,
                                 float *normals, int *n_vertices) {
     if (!vertex_coords || !vertex_sdf) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
-    float *d = nullptr;
-    HIP_TRY(hipMalloc(&d, (32 + 2 + 36 + 90) * sizeof(float)));
+    DeviceBuffer<float> d;
+    HIP_TRY(d.alloc(32 + 2 + 36 + 90));
     float in[32];
     memcpy(in, vertex_coords, 24 * sizeof(float));
     memcpy(in + 24, vertex_sdf, 8 * sizeof(float));
-    hipError_t e = hipMemcpy(d, in, sizeof(in), hipMemcpyHostToDevice);
+    hipError_t e = hipMemcpy(d.get(), in, sizeof(in), hipMemcpyHostToDevice);
     float out[2 + 36 + 90];
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(mesh_cube_values_kernel, dim3(1), dim3(1), 0, 0, (const float *)d, (const float *)(d + 24), d + 32);
-        e = hipMemcpy(out, d + 32, sizeof(out), hipMemcpyDeviceToHost);
+        hipLaunchKernelGGL(mesh_cube_values_kernel, dim3(1), dim3(1), 0, 0, (const float *)d.get(), (const float *)(d.get() + 24), d.get() + 32);
+        e = hipMemcpy(out, d.get() + 32, sizeof(out), hipMemcpyDeviceToHost);
     }
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(CHISEL_HIP_ERR_HIP, std::string("chisel_hip_mesh_cube_values: ") + hipGetErrorString(e));
     const int nv = (int)out[1];
     if (configuration) *configuration = (int)out[0];
@@ -3344,15 +2727,14 @@ int chisel_hip_mesh_cube_values(const float *vertex_coords, const float *vertex_
 
 int chisel_hip_interpolate_vertex(const float v1[3], const float v2[3], float sdf1, float sdf2, float out[3]) {
     if (!v1 || !v2 || !out) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
-    float *d = nullptr;
-    HIP_TRY(hipMalloc(&d, 12 * sizeof(float)));
+    DeviceBuffer<float> d;
+    HIP_TRY(d.alloc(12));
     const float in[8] = {v1[0], v1[1], v1[2], v2[0], v2[1], v2[2], sdf1, sdf2};
-    hipError_t e = hipMemcpy(d, in, sizeof(in), hipMemcpyHostToDevice);
+    hipError_t e = hipMemcpy(d.get(), in, sizeof(in), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(interpolate_vertex_kernel, dim3(1), dim3(1), 0, 0, (const float *)d, d + 8);
-        e = hipMemcpy(out, d + 8, 3 * sizeof(float), hipMemcpyDeviceToHost);
+        hipLaunchKernelGGL(interpolate_vertex_kernel, dim3(1), dim3(1), 0, 0, (const float *)d.get(), d.get() + 8);
+        e = hipMemcpy(out, d.get() + 8, 3 * sizeof(float), hipMemcpyDeviceToHost);
     }
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(CHISEL_HIP_ERR_HIP, std::string("chisel_hip_interpolate_vertex: ") + hipGetErrorString(e));
     return CHISEL_HIP_OK;
 }
@@ -3361,21 +2743,20 @@ int chisel_hip_raycast(const float start[3], const float end[3], const int min_x
                        int64_t *count) {
     if (!start || !end || !min_xyz || !max_xyz || !count || capacity < 0 || (capacity > 0 && !cells)) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
     const int cap = (int)std::min<int64_t>(capacity, 1 << 24);
-    float *d_in = nullptr;
-    int *d_cells = nullptr, *d_count = nullptr;
-    HIP_TRY(hipMalloc(&d_in, 6 * sizeof(float)));
-    HIP_TRY(hipMalloc(&d_cells, ((size_t)cap * 3 + 4) * sizeof(int)));
-    HIP_TRY(hipMalloc(&d_count, sizeof(int)));
+    DeviceBuffer<float> d_in;
+    DeviceBuffer<int> d_cells, d_count;
+    HIP_TRY(d_in.alloc(6));
+    HIP_TRY(d_cells.alloc((size_t)cap * 3 + 4));
+    HIP_TRY(d_count.alloc(1));
     const float in[6] = {start[0], start[1], start[2], end[0], end[1], end[2]};
-    hipError_t e = hipMemcpy(d_in, in, sizeof(in), hipMemcpyHostToDevice);
+    hipError_t e = hipMemcpy(d_in.get(), in, sizeof(in), hipMemcpyHostToDevice);
     int c = 0;
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(kat_raycast_kernel, dim3(1), dim3(64), 0, 0, (const float *)d_in, 1, make_int3(min_xyz[0], min_xyz[1], min_xyz[2]),
-                           make_int3(max_xyz[0], max_xyz[1], max_xyz[2]), d_cells, cap, d_count);
-        e = hipMemcpy(&c, d_count, sizeof(int), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && cap > 0 && c > 0) e = hipMemcpy(cells, d_cells, (size_t)std::min(c, cap) * 3 * sizeof(int), hipMemcpyDeviceToHost);
+        hipLaunchKernelGGL(kat_raycast_kernel, dim3(1), dim3(64), 0, 0, (const float *)d_in.get(), 1, make_int3(min_xyz[0], min_xyz[1], min_xyz[2]),
+                           make_int3(max_xyz[0], max_xyz[1], max_xyz[2]), d_cells.get(), cap, d_count.get());
+        e = hipMemcpy(&c, d_count.get(), sizeof(int), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && cap > 0 && c > 0) e = hipMemcpy(cells, d_cells.get(), (size_t)std::min(c, cap) * 3 * sizeof(int), hipMemcpyDeviceToHost);
     }
-    (void)hipFree(d_in); (void)hipFree(d_cells); (void)hipFree(d_count);
     if (e != hipSuccess) return fail(CHISEL_HIP_ERR_HIP, std::string("chisel_hip_raycast: ") + hipGetErrorString(e));
     *count = c;
     return CHISEL_HIP_OK;
@@ -3446,7 +2827,7 @@ int chisel_hip_memory_statistics(chisel_hip_map *m, chisel_hip_statistics *out) 
         init.id_min[a] = INT32_MAX;
         init.id_max[a] = INT32_MIN;
     }
-    CensusOut *d = reinterpret_cast<CensusOut *>(m->scratch_i);
+    CensusOut *d = reinterpret_cast<CensusOut *>(m->scratch_i.get());
     HIP_TRY(hipMemcpyAsync(d, &init, sizeof(init), hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL(census_kernel, dim3(std::min(m->view.max_chunks, 8192)), dim3(256), 0, m->stream, m->view, m->V, d);
     HIP_TRY(hipGetLastError());
@@ -3525,10 +2906,10 @@ int chisel_hip_shade_vertices(chisel_hip_map *m, const float *vertices, int64_t 
         int rc_m = check_mesh_totals(m);
         if (rc_m) return rc_m;
     }
-    float *d = nullptr;
+    DeviceBuffer<float> d;
     const size_t f = (size_t)n * 3;
-    HIP_TRY(hipMalloc(&d, 3 * f * sizeof(float)));
-    float *dv = d, *dn = d + f, *dc = d + 2 * f;
+    HIP_TRY(d.alloc(3 * f));
+    float *dv = d.get(), *dn = d.get() + f, *dc = d.get() + 2 * f;
     HIP_TRY(hipMemcpyAsync(dv, vertices, f * sizeof(float), hipMemcpyHostToDevice, m->stream));
     if (normals && (stages & 1)) HIP_TRY(hipMemcpyAsync(dn, normals, f * sizeof(float), hipMemcpyHostToDevice, m->stream));
     const MeshParams P = mesh_params(m);
@@ -3542,7 +2923,6 @@ int chisel_hip_shade_vertices(chisel_hip_map *m, const float *vertices, int64_t 
     if (e == hipSuccess && normals && (stages & 1)) e = hipMemcpyAsync(normals, dn, f * sizeof(float), hipMemcpyDeviceToHost, m->stream);
     if (e == hipSuccess && colors && (stages & 2) && m->view.rgbw) e = hipMemcpyAsync(colors, dc, f * sizeof(float), hipMemcpyDeviceToHost, m->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    (void)hipFree(d);
     if (e != hipSuccess) return fail(CHISEL_HIP_ERR_HIP, std::string("chisel_hip_shade_vertices: ") + hipGetErrorString(e));
     return CHISEL_HIP_OK;
 }
@@ -3570,12 +2950,13 @@ int chisel_hip_render_view(chisel_hip_map *m, const chisel_hip_view *view, float
         if (rc_m) return rc_m;
     }
     const size_t px = (size_t)view->width * view->height;
-    float *d = nullptr, *dd = depth, *dn = normals, *dc = colors;
+    DeviceBuffer<float> d;
+    float *dd = depth, *dn = normals, *dc = colors;
     if (!on_device) {
-        HIP_TRY(hipMalloc(&d, 7 * px * sizeof(float)));
-        dd = d;
-        dn = normals ? d + px : nullptr;
-        dc = colors ? d + 4 * px : nullptr;
+        HIP_TRY(d.alloc(7 * px));
+        dd = d.get();
+        dn = normals ? d.get() + px : nullptr;
+        dc = colors ? d.get() + 4 * px : nullptr;
     }
     const MeshParams P = mesh_params(m);
     const dim3 grid((unsigned)((view->width + 15) / 16), (unsigned)((view->height + 15) / 16));
@@ -3590,7 +2971,6 @@ int chisel_hip_render_view(chisel_hip_map *m, const chisel_hip_view *view, float
         if (e == hipSuccess && normals) e = hipMemcpyAsync(normals, dn, 3 * px * sizeof(float), hipMemcpyDeviceToHost, m->stream);
         if (e == hipSuccess && colors) e = hipMemcpyAsync(colors, dc, 3 * px * sizeof(float), hipMemcpyDeviceToHost, m->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-        (void)hipFree(d);
     }
     if (e != hipSuccess) return fail(CHISEL_HIP_ERR_HIP, std::string("chisel_hip_render_view: ") + hipGetErrorString(e));
     return CHISEL_HIP_OK;
@@ -3620,150 +3000,7 @@ int chisel_hip_get_profile(chisel_hip_map *m, double *ms_total, int64_t *launche
     return CHISEL_HIP_OK;
 }
 
-// ---- known-answer entry points (tests only; not part of the reference surface) -------------------------
-int chisel_hip_kat_truncation(int kind, float param, const float *depths, int n, float *trunc, float *weight1) {
-    float *d_in = nullptr, *d_t = nullptr, *d_w = nullptr;
-    HIP_TRY(hipMalloc(&d_in, n * sizeof(float)));
-    HIP_TRY(hipMalloc(&d_t, n * sizeof(float)));
-    HIP_TRY(hipMalloc(&d_w, n * sizeof(float)));
-    HIP_TRY(hipMemcpy(d_in, depths, n * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(kat_truncation_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, kind, param, d_in, n, d_t, d_w);
-    HIP_TRY(hipMemcpy(trunc, d_t, n * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(weight1, d_w, n * sizeof(float), hipMemcpyDeviceToHost));
-    (void)hipFree(d_in); (void)hipFree(d_t); (void)hipFree(d_w);
-    return CHISEL_HIP_OK;
-}
-int chisel_hip_kat_dist(const float *ops, int n, float *out) {
-    float *d_in = nullptr, *d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_in, n * 3 * sizeof(float)));
-    HIP_TRY(hipMalloc(&d_out, n * 2 * sizeof(float)));
-    HIP_TRY(hipMemcpy(d_in, ops, n * 3 * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(kat_dist_kernel, dim3(1), dim3(64), 0, 0, d_in, n, d_out);
-    HIP_TRY(hipMemcpy(out, d_out, n * 2 * sizeof(float), hipMemcpyDeviceToHost));
-    (void)hipFree(d_in); (void)hipFree(d_out);
-    return CHISEL_HIP_OK;
-}
-int chisel_hip_kat_raycast(const float *rays, int n, const int lo[3], const int hi[3], int *cells, int cap, int *count) {
-    float *d_in = nullptr;
-    int *d_cells = nullptr, *d_count = nullptr;
-    HIP_TRY(hipMalloc(&d_in, (size_t)n * 6 * sizeof(float)));
-    HIP_TRY(hipMalloc(&d_cells, (size_t)n * cap * 3 * sizeof(int)));
-    HIP_TRY(hipMalloc(&d_count, (size_t)n * sizeof(int)));
-    HIP_TRY(hipMemcpy(d_in, rays, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(kat_raycast_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, d_in, n, make_int3(lo[0], lo[1], lo[2]),
-                       make_int3(hi[0], hi[1], hi[2]), d_cells, cap, d_count);
-    HIP_TRY(hipMemcpy(cells, d_cells, (size_t)n * cap * 3 * sizeof(int), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(count, d_count, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
-    (void)hipFree(d_in); (void)hipFree(d_cells); (void)hipFree(d_count);
-    return CHISEL_HIP_OK;
-}
-int chisel_hip_kat_color(const uint8_t *ops, int n, uint8_t *out) {
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_in, n * 4));
-    HIP_TRY(hipMalloc(&d_out, n * 4));
-    HIP_TRY(hipMemcpy(d_in, ops, n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(kat_color_kernel, dim3(1), dim3(64), 0, 0, d_in, n, d_out);
-    HIP_TRY(hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(d_in); (void)hipFree(d_out);
-    return CHISEL_HIP_OK;
-}
-int chisel_hip_kat_color_fresh(unsigned *mismatches) {
-    unsigned *d = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof(unsigned)));
-    HIP_TRY(hipMemset(d, 0, sizeof(unsigned)));
-    hipLaunchKernelGGL(kat_color_fresh_kernel, dim3(8 * 256 * 256 / 256), dim3(256), 0, 0, d);
-    HIP_TRY(hipMemcpy(mismatches, d, sizeof(unsigned), hipMemcpyDeviceToHost));
-    (void)hipFree(d);
-    return CHISEL_HIP_OK;
-}
-// diagnostics of the last cloud: listed chunks, (unit, point) pairs, rays of the largest unit, units with rays
-int chisel_hip_debug_cloud_stats(chisel_hip_map *m, int64_t out[4]) {
-    SETTLE(m);
-    if (m && m->is_group) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "per-shard read-out");
-    if (!m || !m->cloud.view.ctl) return fail(CHISEL_HIP_ERR_INVALID, "no cloud yet");
-    HIP_TRY(hipSetDevice(m->device));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    int ctl[2] = {0, 0};
-    HIP_TRY(hipMemcpy(ctl, m->cloud.view.ctl, sizeof(ctl), hipMemcpyDeviceToHost));
-    const int units = std::min(ctl[0], CLOUD_MAX_LISTED) * CloudUnits(m->N, 0, cloud_unit_depth(m->N)).count;
-    std::vector<int> off((size_t)units + 1);
-    HIP_TRY(hipMemcpy(off.data(), m->cloud.view.offsets, off.size() * sizeof(int), hipMemcpyDeviceToHost));
-    int64_t mx = 0, used = 0;
-    for (int i = 0; i < units; i++) {
-        mx = std::max<int64_t>(mx, off[i + 1] - off[i]);
-        used += off[i + 1] > off[i];
-    }
-    out[0] = ctl[0]; out[1] = ctl[1]; out[2] = mx; out[3] = used;
-    return CHISEL_HIP_OK;
-}
-int chisel_hip_kat_color_any(unsigned *mismatches) {
-    unsigned *d = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof(unsigned)));
-    HIP_TRY(hipMemset(d, 0, sizeof(unsigned)));
-    hipLaunchKernelGGL(kat_color_any_kernel, dim3(256 * 256 * 256 / 256), dim3(256), 0, 0, d);
-    HIP_TRY(hipMemcpy(mismatches, d, sizeof(unsigned), hipMemcpyDeviceToHost));
-    (void)hipFree(d);
-    return CHISEL_HIP_OK;
-}
-int chisel_hip_kat_reciprocal(unsigned long long *mismatches, unsigned *example_bits) {
-    unsigned long long *d = nullptr;
-    unsigned *e = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc(&e, sizeof(unsigned)));
-    HIP_TRY(hipMemset(d, 0, sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(e, 0, sizeof(unsigned)));
-    unsigned lo, hi;
-    const float fmin = FASTZ_MIN, fmax = FASTZ_MAX;
-    memcpy(&lo, &fmin, 4);
-    memcpy(&hi, &fmax, 4);
-    hipLaunchKernelGGL(kat_reciprocal_kernel, dim3(4096), dim3(256), 0, 0, lo, (unsigned long long)(hi - lo) + 1ull, d, e);
-    HIP_TRY(hipMemcpy(mismatches, d, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(example_bits, e, sizeof(unsigned), hipMemcpyDeviceToHost));
-    (void)hipFree(d);
-    (void)hipFree(e);
-    return CHISEL_HIP_OK;
-}
-int chisel_hip_kat_floor(unsigned long long *mismatches, unsigned *example_bits) {
-    unsigned long long *d = nullptr;
-    unsigned *e = nullptr;
-    HIP_TRY(hipMalloc(&d, sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc(&e, sizeof(unsigned)));
-    HIP_TRY(hipMemset(d, 0, sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(e, 0, sizeof(unsigned)));
-    hipLaunchKernelGGL(kat_floor_kernel, dim3(4096), dim3(256), 0, 0, d, e);
-    HIP_TRY(hipMemcpy(mismatches, d, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(example_bits, e, sizeof(unsigned), hipMemcpyDeviceToHost));
-    (void)hipFree(d);
-    (void)hipFree(e);
-    return CHISEL_HIP_OK;
-}
 // host-side frustum arithmetic of the product (host_frustum.h), for CPU-only tests against the oracle
-// the candidate ids cull_kernel hands to shard `rank` of `n_shards` for an id range (host evaluation of CullSpace; no GPU needed):
-// returns the number of slots, writes the ids of the slots that hold one (at most `capacity`), *count = how many do
-int chisel_hip_debug_cull_space(const int range_min[3], const int range_dim[3], int n_shards, int shard_rank, int shard_block, int *ids,
-                                int capacity, int *count) {
-    CullParams P;
-    memset(&P, 0, sizeof(P));
-    for (int a = 0; a < 3; a++) {
-        P.range_min[a] = range_min[a];
-        P.range_dim[a] = range_dim[a];
-    }
-    P.ip.n_shards = n_shards;
-    P.ip.shard_rank = shard_rank;
-    P.ip.shard_block = shard_block;
-    const CullSpace space(P);
-    int n = 0;
-    for (int c = 0; c < space.total; c++) {
-        int x, y, z;
-        if (!space.id(P, c, x, y, z)) continue;
-        if (n < capacity) {
-            ids[3 * n] = x; ids[3 * n + 1] = y; ids[3 * n + 2] = z;
-        }
-        n++;
-    }
-    *count = n;
-    return space.total;
-}
 int chisel_hip_frustum(const float pose[12], float fy, float cy, int width, int height, float near_plane, float far_plane, float *corners,
                        float *lines, float *planes) {
     if (!pose || width <= 0 || height <= 0) return fail(CHISEL_HIP_ERR_INVALID, "bad frustum arguments");
@@ -3791,14 +3028,7 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
     }
     return CHISEL_HIP_OK;
 }
-int chisel_hip_debug_frustum_range(const float *pose, float near_plane, float far_plane, float fy, float cy, int W, int H,
-                                   int chunk_n, float res, int *range_min3, int *range_dim3, float *planes24, float *corners24) {
-    hostmath::FrustumRange fr = hostmath::frustum_range(pose, near_plane, far_plane, fy, cy, W, H, chunk_n, res);
-    memcpy(range_min3, fr.range_min, sizeof(fr.range_min));
-    memcpy(range_dim3, fr.range_dim, sizeof(fr.range_dim));
-    if (planes24) memcpy(planes24, fr.planes, sizeof(fr.planes));
-    if (corners24) memcpy(corners24, fr.corners, sizeof(fr.corners));
-    return CHISEL_HIP_OK;
-}
 
 }  // extern "C"
+
+#include "host_selftest.h"

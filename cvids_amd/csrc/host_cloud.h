@@ -19,14 +19,6 @@ void invert_affine(const float *m, float *r) {
     for (int i = 0; i < 3; i++) r[4 * i + 3] = -(r[4 * i] * m[3] + (r[4 * i + 1] * m[7] + r[4 * i + 2] * m[11]));
 }
 
-void free_cloud_buffers(chisel_hip_map::CloudBuffers &B) {
-    void *ptrs[] = {B.points, B.colors, B.view.rays, B.view.rgb, B.view.tile_prefix, B.view.table_keys /* + ctl, offsets, cursors */, B.view.table_vals,
-                    B.view.listed, B.view.pairs, B.view.sorted};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    B = chisel_hip_map::CloudBuffers();
-}
-
 int ensure_cloud_buffers(chisel_hip_map *m, int64_t n) {
     chisel_hip_map::CloudBuffers &B = m->cloud;
     CloudView &C = B.view;
@@ -34,32 +26,27 @@ int ensure_cloud_buffers(chisel_hip_map *m, int64_t n) {
         // one allocation for everything a cloud starts from zero: table keys | control words | per-unit counts (+1) | per-unit cursors
         const size_t units = (size_t)CLOUD_MAX_LISTED * CloudUnits(m->N, 0, cloud_unit_depth(m->N)).count;
         B.zeroed_bytes = (size_t)CLOUD_TABLE_SLOTS * sizeof(uint64_t) + 16 * sizeof(int) + (units + 1) * sizeof(int) + units * sizeof(int);
-        char *base = nullptr;
-        HIP_TRY(hipMalloc(&base, B.zeroed_bytes));
+        HIP_TRY(B.zeroed.alloc(B.zeroed_bytes));
+        char *base = B.zeroed.get();
         C.table_keys = reinterpret_cast<uint64_t *>(base);
         C.ctl = reinterpret_cast<int *>(base + (size_t)CLOUD_TABLE_SLOTS * sizeof(uint64_t));
         C.offsets = C.ctl + 16;
         C.cursors = C.offsets + units + 1;
-        HIP_TRY(hipMalloc(&C.table_vals, (size_t)CLOUD_TABLE_SLOTS * sizeof(int)));
-        HIP_TRY(hipMalloc(&C.listed, (size_t)CLOUD_MAX_LISTED * sizeof(uint64_t)));
+        HIP_TRY(alloc_viewed(B.table_vals, C.table_vals, (size_t)CLOUD_TABLE_SLOTS));
+        HIP_TRY(alloc_viewed(B.listed, C.listed, (size_t)CLOUD_MAX_LISTED));
     }
     if (n <= B.capacity) return CHISEL_HIP_OK;
     HIP_TRY(hipStreamSynchronize(m->stream));
-    void *ptrs[] = {B.points, B.colors, C.rays, C.rgb, C.tile_prefix, C.pairs, C.sorted};
-    for (void *p : ptrs)
-        if (p) HIP_TRY(hipFree(p));
-    B.points = B.colors = nullptr;
-    C.rays = nullptr; C.rgb = nullptr; C.tile_prefix = nullptr; C.pairs = nullptr; C.sorted = nullptr;
     B.capacity = 0;
     int64_t cap = 1 << 16;
     while (cap < n) cap *= 2;
-    HIP_TRY(hipMalloc(&B.points, (size_t)cap * 3 * sizeof(float)));
-    HIP_TRY(hipMalloc(&B.colors, (size_t)cap * 3 * sizeof(float)));
-    HIP_TRY(hipMalloc(&C.rays, (size_t)cap * sizeof(CloudRay)));
-    HIP_TRY(hipMalloc(&C.rgb, (size_t)cap * sizeof(unsigned)));
-    HIP_TRY(hipMalloc(&C.tile_prefix, (size_t)(cap / CLOUD_TILE + 2) * sizeof(int)));
-    HIP_TRY(hipMalloc(&C.pairs, (size_t)cap * CLOUD_PAIRS_PER_POINT * sizeof(int)));
-    HIP_TRY(hipMalloc(&C.sorted, (size_t)cap * CLOUD_PAIRS_PER_POINT * sizeof(int)));
+    HIP_TRY(B.points.alloc((size_t)cap * 3));
+    HIP_TRY(B.colors.alloc((size_t)cap * 3));
+    HIP_TRY(alloc_viewed(B.rays, C.rays, (size_t)cap));
+    HIP_TRY(alloc_viewed(B.rgb, C.rgb, (size_t)cap));
+    HIP_TRY(alloc_viewed(B.tile_prefix, C.tile_prefix, (size_t)(cap / CLOUD_TILE + 2)));
+    HIP_TRY(alloc_viewed(B.pairs, C.pairs, (size_t)cap * CLOUD_PAIRS_PER_POINT));
+    HIP_TRY(alloc_viewed(B.sorted, C.sorted, (size_t)cap * CLOUD_PAIRS_PER_POINT));
     C.pairs_capacity = (int)std::min<int64_t>(cap * CLOUD_PAIRS_PER_POINT, 0x7fffffff);
     B.capacity = cap;
     return CHISEL_HIP_OK;
@@ -69,30 +56,27 @@ template <int N>
 void launch_cloud_integrate(chisel_hip_map *m, const CloudParams &P, const CloudView &C) {
     m->mesh_mark_needed = true;  // (this kernel dirties slots without listing their neighbourhoods: the next recompute runs mesh_mark_kernel)
     if (m->cfg.use_color)
-        hipLaunchKernelGGL((cloud_integrate_kernel<N, true>), dim3(CLOUD_GRID), dim3(64 * CloudGeom<N>::WAVES), 0, m->stream, P, m->view, m->view_dev, C);
+        hipLaunchKernelGGL((cloud_integrate_kernel<N, true>), dim3(CLOUD_GRID), dim3(64 * CloudGeom<N>::WAVES), 0, m->stream, P, m->view, m->view_dev.get(), C);
     else
-        hipLaunchKernelGGL((cloud_integrate_kernel<N, false>), dim3(CLOUD_GRID), dim3(64 * CloudGeom<N>::WAVES), 0, m->stream, P, m->view, m->view_dev, C);
+        hipLaunchKernelGGL((cloud_integrate_kernel<N, false>), dim3(CLOUD_GRID), dim3(64 * CloudGeom<N>::WAVES), 0, m->stream, P, m->view, m->view_dev.get(), C);
 }
 
 // what both entry points below need of a cloud: buffers, the points in HBM, the parameters of the per-point kernels
 int cloud_setup(chisel_hip_map *m, const chisel_hip_pointcloud *cloud, CloudParams &P, CloudView &C) {
     int rc = ensure_cloud_buffers(m, cloud->n_points);
     if (rc) return rc;
-    if (m->input_event) {  // chisel_hip_wait_event: a device cloud produced on another stream is ready behind this event
-        HIP_TRY(hipStreamWaitEvent(m->stream, m->input_event, 0));
-        m->input_event = nullptr;
-    }
+    if (const int rc_in = wait_for_input(m, m->stream)) return rc_in;
     const int n = (int)cloud->n_points;
     C = m->cloud.view;
     if (cloud->on_device) {
         C.points = cloud->points;
         C.colors = cloud->colors;
     } else {
-        HIP_TRY(hipMemcpyAsync(m->cloud.points, cloud->points, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, m->stream));
+        HIP_TRY(hipMemcpyAsync(m->cloud.points.get(), cloud->points, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, m->stream));
         if (cloud->colors)
-            HIP_TRY(hipMemcpyAsync(m->cloud.colors, cloud->colors, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, m->stream));
-        C.points = m->cloud.points;
-        C.colors = cloud->colors ? m->cloud.colors : nullptr;
+            HIP_TRY(hipMemcpyAsync(m->cloud.colors.get(), cloud->colors, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, m->stream));
+        C.points = m->cloud.points.get();
+        C.colors = cloud->colors ? m->cloud.colors.get() : nullptr;
     }
     memset(&P, 0, sizeof(P));
     P.ip.trunc_kind = m->integ.truncator_kind;

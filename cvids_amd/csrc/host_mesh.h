@@ -23,8 +23,8 @@ void launch_mesh_triangles(chisel_hip_map *m, const MeshParams &P, float *arena,
     MeshBuffers &B = m->mesh_buf;
     const JobInfo *bases = B.info;
     const int *totals = B.totals;
-    int *host_info = m->mesh_info_dev;
-    volatile int *host_flags = (volatile int *)m->mesh_totals_dev;
+    int *host_info = reinterpret_cast<int *>(m->mesh_info_host.dev());
+    volatile int *host_flags = (volatile int *)m->mesh_totals_host.dev();
     const int max_jobs = std::min(MESH_INFO_PREFETCH, B.capacity), seq = m->mesh_seq, part = B.tri_capacity / MESH_PARTS;
     const dim3 grid(4096), block(MESH_TRI_BLOCK);  // persistent: the number of triangles (per partition of the list) is read on the device
     switch (m->N) {
@@ -40,16 +40,15 @@ int ensure_mesh_jobs(chisel_hip_map *m, int n) {
     MeshBuffers &B = m->mesh_buf;
     if (n <= B.capacity) return CHISEL_HIP_OK;
     HIP_TRY(hipStreamSynchronize(m->stream));
-    for (void *p : {(void *)B.jobs, (void *)B.ids, (void *)B.info, (void *)B.cnt, (void *)B.job_acc})
-        if (p) HIP_TRY(hipFree(p));
-    B.jobs = nullptr; B.ids = nullptr; B.info = nullptr; B.cnt = nullptr; B.job_acc = nullptr;
+    chisel_hip_map::MeshMemory &O = m->mesh_mem;
     int cap = std::max(4096, B.capacity);
     while (cap < n) cap *= 2;
-    HIP_TRY(hipMalloc(&B.jobs, (size_t)cap * sizeof(MeshJob)));
-    HIP_TRY(hipMalloc(&B.ids, (size_t)cap * 3 * sizeof(int)));
-    HIP_TRY(hipMalloc(&B.info, (size_t)cap * sizeof(JobInfo)));
-    HIP_TRY(hipMalloc(&B.cnt, (size_t)cap * mesh_row_ints(m) * sizeof(unsigned)));
-    HIP_TRY(hipMalloc(&B.job_acc, (size_t)cap * sizeof(unsigned long long)));
+    B.capacity = 0;  // (until all five are there)
+    HIP_TRY(alloc_viewed(O.jobs, B.jobs, (size_t)cap));
+    HIP_TRY(alloc_viewed(O.ids, B.ids, (size_t)cap * 3));
+    HIP_TRY(alloc_viewed(O.info, B.info, (size_t)cap));
+    HIP_TRY(alloc_viewed(O.cnt, B.cnt, (size_t)cap * mesh_row_ints(m)));
+    HIP_TRY(alloc_viewed(O.job_acc, B.job_acc, (size_t)cap));
     HIP_TRY(hipMemsetAsync(B.job_acc, 0, (size_t)cap * sizeof(unsigned long long), m->stream));  // (the count kernel's last arrivers keep them at zero)
     B.capacity = cap;
     return CHISEL_HIP_OK;
@@ -71,7 +70,7 @@ hipError_t zero_mesh_counters(chisel_hip_map *m) {
 // appends its neighbourhood), so a recompute normally starts with its count kernel; mesh_mark_kernel builds the same entries from the
 // dirty flags when something else has dirtied slots since (point clouds), when the kept list has been given up (`rebuild`), or
 // completes it with `extra` host-side ids (neighbourhoods of chunks that were removed while dirty).  The number of entries stays on
-// the device (mesh_ctl[4], copied to the totals by the count kernel); nothing here waits for the stream unless `extra` is used.
+// the device (mesh_ctl[MC_KEPT], copied to the totals by the count kernel); nothing here waits for the stream unless `extra` is used.
 int collect_mesh_ids(chisel_hip_map *m, const std::vector<int> &extra) {
     MeshBuffers &B = m->mesh_buf;
     const int C = m->view.committed;
@@ -95,12 +94,11 @@ int collect_mesh_ids(chisel_hip_map *m, const std::vector<int> &extra) {
         std::vector<int> slots;
         rc = lookup_slots(m, extra.data(), ne, slots);
         if (rc) return rc;
-        int *d_slots = nullptr;
-        HIP_TRY(hipMalloc(&d_slots, (size_t)ne * sizeof(int)));
-        HIP_TRY(hipMemcpy(d_slots, slots.data(), (size_t)ne * sizeof(int), hipMemcpyHostToDevice));  // (pageable source, rare path: a blocking copy; lookup_slots has waited for the stream already)
-        hipLaunchKernelGGL(mesh_append_kernel, dim3((ne + 255) / 256), dim3(256), 0, m->stream, m->view, B.flags, (const int *)d_slots, ne, m->view.mesh_jobs, n_jobs);
+        DeviceBuffer<int> d_slots;
+        HIP_TRY(d_slots.alloc((size_t)ne));
+        HIP_TRY(hipMemcpy(d_slots.get(), slots.data(), (size_t)ne * sizeof(int), hipMemcpyHostToDevice));  // (pageable source, rare path: a blocking copy; lookup_slots has waited for the stream already)
+        hipLaunchKernelGGL(mesh_append_kernel, dim3((ne + 255) / 256), dim3(256), 0, m->stream, m->view, B.flags, (const int *)d_slots.get(), ne, m->view.mesh_jobs, n_jobs);
         HIP_TRY(hipStreamSynchronize(m->stream));
-        HIP_TRY(hipFree(d_slots));
     }
     HIP_TRY(hipGetLastError());
     return CHISEL_HIP_OK;
@@ -205,8 +203,8 @@ int recompute_meshes(chisel_hip_map *m) {
     const MeshParams P = mesh_params(m);
     if (!B.tris) {
         B.tri_capacity = std::max(B.tri_capacity, m->mesh_tiny ? 4 * MESH_PARTS : 1 << 20);
-        HIP_TRY(hipMalloc(&B.tris, (size_t)B.tri_capacity * sizeof(TriRec)));
-        HIP_TRY(hipMalloc(&B.corners, (size_t)B.tri_capacity * sizeof(CubeCorners)));
+        HIP_TRY(alloc_viewed(m->mesh_mem.tris, B.tris, (size_t)B.tri_capacity));
+        HIP_TRY(alloc_viewed(m->mesh_mem.corners, B.corners, (size_t)B.tri_capacity));
     }
     // an arena record and a buffer that should do: twice what the previous recompute needed
     int arena_id = -1;
@@ -255,7 +253,7 @@ int recompute_meshes(chisel_hip_map *m) {
 // The totals of the recompute in flight: sizes the arena's contents, emits again when the batch outgrew the triangle
 // list or the arena.  Must run before anything else changes the map (a second emission reads the voxels): every entry
 // point that queues map-changing work calls it first; it waits for the count kernel only, not for the stream.
-bool mesh_totals_published(const chisel_hip_map *m) { return ((volatile const int *)m->mesh_totals_host)[5] == m->mesh_seq; }
+bool mesh_totals_published(const chisel_hip_map *m) { return ((volatile const int *)m->mesh_totals_host.get())[MH_PUBLISHED] == m->mesh_seq; }
 int replay_deferred_set(chisel_hip_map *m, int set);  // chisel_hip.hip
 void launch_fixed_drop(chisel_hip_map *m, const int *latch);  // chisel_hip.hip
 int check_mesh_totals(chisel_hip_map *m) {
@@ -271,18 +269,18 @@ int check_mesh_totals(chisel_hip_map *m) {
     const MeshParams P = mesh_params(m);
     int arena_id = m->pending_meshes.arena;
     {
-        // the device writes totals and sequence number as one 16-byte store (mesh_triangle_kernel): word 3 is the sequence number
-        volatile int *host = m->mesh_totals_host;
+        // the device writes totals and sequence number as one 16-byte store (mesh_triangle_kernel): MH_TRIS .. MH_SEQ
+        volatile int *host = m->mesh_totals_host.get();
         const auto t0 = std::chrono::steady_clock::now();
-        while (host[5] != m->mesh_seq) {  // (the copy of the sequence number written behind a system-scope fence: words 0-3 are complete)
+        while (host[MH_PUBLISHED] != m->mesh_seq) {  // (the copy of the sequence number written behind a system-scope fence: the four totals are complete)
             if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
                 HIP_TRY(hipStreamSynchronize(m->stream));  // long queue in front of the recompute, or a failed launch: no more polling
-                if (host[5] != m->mesh_seq || host[3] != m->mesh_seq) return fail(CHISEL_HIP_ERR_HIP, "mesh totals were not published");
+                if (host[MH_PUBLISHED] != m->mesh_seq || host[MH_SEQ] != m->mesh_seq) return fail(CHISEL_HIP_ERR_HIP, "mesh totals were not published");
             }
         }
         std::atomic_thread_fence(std::memory_order_acquire);
     }
-    const bool device_unfit = m->mesh_totals_host[4] != 0;  // the triangle kernel's own verdict (what MC_LATCH was set by)
+    const bool device_unfit = m->mesh_totals_host.get()[MH_UNFIT] != 0;  // the triangle kernel's own verdict (what MC_LATCH was set by)
     // From here on MC_LATCH is known to be set (device_unfit) and the deferred set's kernel to have left the map alone: whatever way this
     // function ends -- also through one of the error returns below -- the latch is cleared and that integration launched again; a frame
     // must not be lost, and no later launch find the latch still up, because a mesh buffer could not be grown.
@@ -297,14 +295,14 @@ int check_mesh_totals(chisel_hip_map *m) {
             if (deferred >= 0) (void)replay_deferred_set(m, deferred);
         }
     } latch_guard{m, deferred, device_unfit};
-    const unsigned packed_jobs = (unsigned)m->mesh_totals_host[2];
-    int totals[4] = {m->mesh_totals_host[0], m->mesh_totals_host[1], (int)(packed_jobs >> 31), (int)(packed_jobs & 0x7fffffffu)};
-    // A chunk of an earlier batch could not be allocated (word [0] of the map's error flags: pool / hash; cloud reports live in
-    // word [1] and are none of this function's business): the map is incomplete.  The recompute is finished all the same -- its
+    const unsigned packed_jobs = (unsigned)m->mesh_totals_host.get()[MH_JOBS];
+    int totals[4] = {m->mesh_totals_host.get()[MH_TRIS], m->mesh_totals_host.get()[MH_GRIDS], (int)(packed_jobs >> 31), (int)(packed_jobs & 0x7fffffffu)};
+    // A chunk of an earlier batch could not be allocated (ST_POOL_ERROR of the map's status block: pool / hash; cloud reports live in
+    // ST_CLOUD_ERROR and are none of this function's business): the map is incomplete.  The recompute is finished all the same -- its
     // mark / collect kernels have already consumed the dirty flags, abandoning it would leave those chunks without a mesh for
     // good -- and the failure is reported afterwards.
     // (read from the flag itself: every kernel that could have raised it finished before the count kernel started)
-    const int pool_error = reinterpret_cast<volatile int *>(m->error_flag_host)[0];
+    const int pool_error = reinterpret_cast<volatile int *>(m->error_flag_host.get())[ST_POOL_ERROR];
     bool redo = false;
     if (totals[MT_OVERFLOW]) {
         // a partition of the record lists was too small: grow them to (at least) twice what this batch needs and list again, until every
@@ -312,21 +310,22 @@ int check_mesh_totals(chisel_hip_map *m) {
         const int n_again = totals[MT_JOBS];
         for (int attempt = 0;; attempt++) {
             HIP_TRY(hipStreamSynchronize(m->stream));
-            HIP_TRY(hipFree(B.tris));
-            HIP_TRY(hipFree(B.corners));
+            m->mesh_mem.tris.reset();
+            m->mesh_mem.corners.reset();
             B.tris = nullptr;
             B.corners = nullptr;
             const long long want = std::max<long long>(2ll * B.tri_capacity, 2ll * std::max(totals[MT_TRIS], totals[MT_GRIDS]) + 16 * MESH_PARTS);
             if (want > (1ll << 30)) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "mesh record lists beyond 2^30 entries");
             B.tri_capacity = (int)((want + MESH_PARTS - 1) / MESH_PARTS * MESH_PARTS);
-            HIP_TRY(hipMalloc(&B.tris, (size_t)B.tri_capacity * sizeof(TriRec)));
-            HIP_TRY(hipMalloc(&B.corners, (size_t)B.tri_capacity * sizeof(CubeCorners)));
+            HIP_TRY(alloc_viewed(m->mesh_mem.tris, B.tris, (size_t)B.tri_capacity));
+            HIP_TRY(alloc_viewed(m->mesh_mem.corners, B.corners, (size_t)B.tri_capacity));
             HIP_TRY(zero_mesh_counters(m));
             // (the kept job list's counter has been emptied by the first emission; its entries are untouched -- nothing has integrated since --
             // and their number is in the totals)
             if (B.n_jobs) {
-                m->mesh_totals_host[8] = n_again;  // (page-locked: an asynchronous copy must not read a local of this function)
-                HIP_TRY(hipMemcpyAsync(B.n_jobs, &m->mesh_totals_host[8], sizeof(int), hipMemcpyHostToDevice, m->stream));
+                int *stage = m->mesh_totals_host.get() + MH_STAGE;  // (page-locked: an asynchronous copy must not read a local of this function)
+                *stage = n_again;
+                HIP_TRY(hipMemcpyAsync(B.n_jobs, stage, sizeof(int), hipMemcpyHostToDevice, m->stream));
             }
             launch_mesh_count(m);
             if (B.n_jobs) HIP_TRY(hipMemsetAsync(B.n_jobs, 0, sizeof(int), m->stream));
@@ -336,7 +335,7 @@ int check_mesh_totals(chisel_hip_map *m) {
             if (attempt == 12) return fail(CHISEL_HIP_ERR_HIP, "mesh record lists overflow after growing them");
         }
         redo = true;
-        HIP_TRY(hipMemcpy(m->mesh_info_host, B.info, (size_t)std::min(MESH_INFO_PREFETCH, B.capacity) * sizeof(JobInfo), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(m->mesh_info_host.get(), B.info, (size_t)std::min(MESH_INFO_PREFETCH, B.capacity) * sizeof(JobInfo), hipMemcpyDeviceToHost));
     }
     const int n = totals[MT_JOBS];
     if ((size_t)totals[MT_TRIS] > 0x7fffffffull / 9) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "more than 2^31 / 9 mesh triangles in one recompute");
@@ -407,12 +406,12 @@ int resolve_pending_meshes(chisel_hip_map *m) {
     const int n = m->pending_meshes.n, arena_id = m->pending_meshes.arena;
     // the records of the first MESH_INFO_PREFETCH jobs are on the host (mesh_triangle_kernel wrote them and then the sequence number)
     {
-        volatile int *host = m->mesh_totals_host;
+        volatile int *host = m->mesh_totals_host.get();
         const auto t0 = std::chrono::steady_clock::now();
-        while (host[6] != m->mesh_seq) {
+        while (host[MH_INFO_SEQ] != m->mesh_seq) {
             if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) {
                 HIP_TRY(hipStreamSynchronize(m->stream));
-                if (host[6] != m->mesh_seq) return fail(CHISEL_HIP_ERR_HIP, "mesh job records were not published");
+                if (host[MH_INFO_SEQ] != m->mesh_seq) return fail(CHISEL_HIP_ERR_HIP, "mesh job records were not published");
             }
         }
         std::atomic_thread_fence(std::memory_order_acquire);
@@ -426,7 +425,7 @@ int resolve_pending_meshes(chisel_hip_map *m) {
     }
     int with_tris = 0;
     for (int j = 0; j < n; j++) {
-        const JobInfo &ji = j < MESH_INFO_PREFETCH ? m->mesh_info_host[j] : tail[(size_t)j - MESH_INFO_PREFETCH];
+        const JobInfo &ji = j < MESH_INFO_PREFETCH ? m->mesh_info_host.get()[j] : tail[(size_t)j - MESH_INFO_PREFETCH];
         if (!ji.present) continue;  // RecomputeMesh: "if (!HasChunk(chunkID)) return" (ChunkManager.cpp:93-96)
         const uint64_t key = pack_id(ji.x, ji.y, ji.z);
         const size_t cv = (size_t)ji.n_vertices, cg = (size_t)ji.n_grids;
@@ -490,7 +489,7 @@ int view_mesh(chisel_hip_map *m, const MeshRef &ref, MeshView &out) {
 
 int query_sdf(chisel_hip_map *m, const float pos[3], int with_gradient, double *dist, float *grad, int *found) {
     HIP_TRY(hipSetDevice(m->device));
-    if (!m->mesh_buf.query) HIP_TRY(hipMalloc(&m->mesh_buf.query, 8 * sizeof(double)));
+    if (!m->mesh_buf.query) HIP_TRY(alloc_viewed(m->mesh_mem.query, m->mesh_buf.query, 8));
     const MeshParams P = mesh_params(m);
     switch (m->N) {
         case 8: hipLaunchKernelGGL(query_sdf_kernel<8>, dim3(1), dim3(1), 0, m->stream, m->view, P, pos[0], pos[1], pos[2], with_gradient, m->mesh_buf.query); break;
@@ -654,8 +653,8 @@ int chisel_hip_mesh_cube(chisel_hip_map *m, const int id[3], const int voxel[3],
     HIP_TRY(hipSetDevice(m->device));
     int rc = check_mesh_totals(m);
     if (rc) return rc;
-    if (!m->mesh_buf.query) HIP_TRY(hipMalloc(&m->mesh_buf.query, 8 * sizeof(double)));
-    if (!m->mesh_buf.cube) HIP_TRY(hipMalloc(&m->mesh_buf.cube, 92 * sizeof(float)));
+    if (!m->mesh_buf.query) HIP_TRY(alloc_viewed(m->mesh_mem.query, m->mesh_buf.query, 8));
+    if (!m->mesh_buf.cube) HIP_TRY(alloc_viewed(m->mesh_mem.cube, m->mesh_buf.cube, 92));
     const MeshParams P = mesh_params(m);
     float *out = m->mesh_buf.cube;
     switch (m->N) {

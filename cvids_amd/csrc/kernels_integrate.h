@@ -240,8 +240,8 @@ __global__ __launch_bounds__(64 * INTEGRATE_WPB, (VPL0 == 2 ? INTEGRATE_WAVES2 :
     // this launch has started: everything queued in front of it on the map's stream is over (the host's substitute for events on that
     // stream, chisel_hip.hip: launch_seq; pinned memory, one thread -- also of a launch that leaves at once)
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        reinterpret_cast<volatile int *>(M.error_flag)[4] = lseq;
-        reinterpret_cast<volatile int *>(M.error_flag)[7] = M.committed - *M.free_top;  // slots in use (what a growable pool's host looks at)
+        reinterpret_cast<volatile int *>(M.error_flag)[ST_STARTED] = lseq;
+        reinterpret_cast<volatile int *>(M.error_flag)[ST_USED] = M.committed - *M.free_top;  // slots in use (what a growable pool's host looks at)
     }
     if (latch) return;
     if (n_items > max_items) n_items = max_items;
@@ -253,17 +253,17 @@ __global__ __launch_bounds__(64 * INTEGRATE_WPB, (VPL0 == 2 ? INTEGRATE_WAVES2 :
         const int *cls = work_count - COUNT_ITEMS + COUNT_CLASS0;
         int pairs = 0;
         for (int c = 0; c < 8; c++) pairs += cls[c] * (KMAX - 2 * c);
-        report[2] = n_items;
-        report[3] = pairs;
+        report[ST_ITEMS] = n_items;
+        report[ST_PAIRS] = pairs;
         // the totals of the next mesh recompute start from zero (no recompute is in flight while this kernel runs: same stream)
         if (M.mesh_ctl) {
-            M.mesh_ctl[0] = 0;
-            M.mesh_ctl[1] = 0;
-            M.mesh_ctl[2] = 0;
+            M.mesh_ctl[MC_TRIS] = 0;
+            M.mesh_ctl[MC_GRIDS] = 0;
+            M.mesh_ctl[MC_OVERFLOW] = 0;
         }
     }
-    // ... and so do the cursors of its record lists (kernels_mesh.h: MC_CURSORS = 8 ints in, MESH_PARTS = 64 64-bit words)
-    if (blockIdx.x == 0 && threadIdx.x < 64 && M.mesh_ctl) reinterpret_cast<unsigned long long *>(M.mesh_ctl + 8)[threadIdx.x] = 0ull;
+    // ... and so do the cursors of its record lists (MC_CURSORS; kernels_mesh.h: MESH_PARTS = 64 64-bit words)
+    if (blockIdx.x == 0 && threadIdx.x < 64 && M.mesh_ctl) reinterpret_cast<unsigned long long *>(M.mesh_ctl + MC_CURSORS)[threadIdx.x] = 0ull;
     const int grid_waves = nb * G::WPB;
 #if defined(CHISEL_PHASES) && defined(PHASE0_AT)
 #define PHASE0(at, dep) do { if (PHASE0_AT == at) { asm volatile("" ::"s"(dep)); PHASE(0); } } while (0)  // diagnostic: where inside the "item" stage the first stamp sits

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void reset_map_kernel(MapView M, int V, int al
     if (gid == 0) {
         M.slot_dirty[2 * (size_t)M.max_chunks] = 0;  // the list of dirty slots is empty
         if (M.mesh_ctl) {
-            M.mesh_ctl[4] = 0;                       // and so is the job list
+            M.mesh_ctl[MC_KEPT] = 0;                 // and so is the job list
             M.mesh_ctl[MC_LATCH] = 0;                // (a recompute that did not fit: void with the map)
             for (int a = 0; a < 3; a++) {            // the box of created ids: empty
                 M.mesh_ctl[MC_BBOX + a] = INT32_MAX;
@@ -65,8 +65,8 @@ __global__ __launch_bounds__(256) void reset_map_kernel(MapView M, int V, int al
             }
         }
         *M.free_top = M.committed;
-        M.error_flag[0] = 0;
-        M.error_flag[1] = 0;
+        M.error_flag[ST_POOL_ERROR] = 0;
+        M.error_flag[ST_CLOUD_ERROR] = 0;
     }
 }
 
@@ -151,7 +151,7 @@ __device__ __attribute__((noinline)) void mesh_expand_dirty(const MapView *__res
         ns = hash_find(M, nx, ny, nz);
         if (ns >= 0 && (ns >= M.max_chunks || M.slot_key[ns] != pack_id(nx, ny, nz))) ns = -1;
     }
-    if (ns >= 0) mesh_append_job(M, M.mesh_flag, ns, M.mesh_jobs, M.mesh_ctl + 4);
+    if (ns >= 0) mesh_append_job(M, M.mesh_flag, ns, M.mesh_jobs, M.mesh_ctl + MC_KEPT);
 }
 
 // HasChunk / GetChunk (ChunkManager.h:79-87): slot per id, -1 when absent
@@ -832,7 +832,7 @@ __global__ void clear_dirty_kernel(MapView M, const int *abort) {  // (abort: a 
     }
     if (i == 0) {
         M.slot_dirty[2 * (size_t)M.max_chunks] = 0;  // and their list
-        if (M.mesh_ctl) M.mesh_ctl[4] = 0;           // and the job list kept while integrating
+        if (M.mesh_ctl) M.mesh_ctl[MC_KEPT] = 0;     // and the job list kept while integrating
     }
 }
 

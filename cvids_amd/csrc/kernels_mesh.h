@@ -348,13 +348,10 @@ struct MeshBox {
     static constexpr unsigned PLUS = TYPE == 0 ? 0x01u : (TYPE == 1 ? 0x0Fu : (TYPE == 2 ? 0x05u : 0xFFu));  // "+" chunks (bit dx + 2 dy + 4 dz) that hold its corners
 };
 constexpr int MESH_PARTS = 64;  // partitions of the unordered record lists
-// MapView::mesh_ctl / MeshBuffers::totals (ints): the recompute's totals -- [0] triangles and [1] grids are ONE 64-bit word for the
-// last arrivers' atomic --, [2] record-list overflow, [3] jobs; [4] entries of the job list the integration kernels keep;
-// from [8] on MESH_PARTS 64-bit cursors (triangles | cubes << 32).  [0..2] and the cursors start every recompute at zero.
-enum { MC_TRIS = 0, MC_GRIDS = 1, MC_OVERFLOW = 2, MC_JOBS = 3, MC_KEPT = 4, MC_CURSORS = 8, MC_INTS = MC_BBOX + 8 };  // (MC_BBOX: chisel_device.h)
+// (the words of MapView::mesh_ctl / MeshBuffers::totals: MC_* in chisel_device.h)
 static_assert(MC_BBOX == MC_CURSORS + 2 * MESH_PARTS, "the created-id box sits behind the cursors");
 static_assert(MC_LATCH > MC_KEPT && MC_LATCH < MC_CURSORS, "a free word in front of the cursors");
-static_assert(MC_CURSORS == 8 && MESH_PARTS == 64 && MC_KEPT == 4, "kernels_integrate.h / kernels_map.h address these words by number");
+static_assert(MESH_PARTS == 64, "integrate_kernel zeroes the cursors with one wave");
 
 #ifndef MESH_COUNT_WAVES
 #define MESH_COUNT_WAVES 6  // waves per SIMD the count kernel is compiled for (its 6 KB of LDS per wave allow 27 per CU of 160 KB)
@@ -426,8 +423,8 @@ __device__ __forceinline__ void mesh_count_body(const MapView &M, const int *__r
     int n = *n_jobs;  // the job count stays on the device: the grid is persistent
     if (n > ids_capacity) n = ids_capacity;  // (the kept list never gets there: the host gives it up first)
     if (blockIdx.x == 0 && lane == 0) ctl[MC_JOBS] = n;  // where the kernels behind this one (and a second emission) read it
-    // every integration launch queued before this recompute is over (pinned word [5]: the host's substitute for an event on the map's stream)
-    if (blockIdx.x == 0 && lane == 2 && done_seq > 0) reinterpret_cast<volatile int *>(M.error_flag)[5] = done_seq;
+    // every integration launch queued before this recompute is over (ST_DONE of the status block: the host's substitute for an event on the map's stream)
+    if (blockIdx.x == 0 && lane == 2 && done_seq > 0) reinterpret_cast<volatile int *>(M.error_flag)[ST_DONE] = done_seq;
     // the list of dirty slots has been consumed -- also when none of them became a job (every listed chunk removed since)
     if (blockIdx.x == 0 && lane == 1 && !keep_dirty) M.slot_dirty[2 * (size_t)M.max_chunks] = 0u;
     s_counts[lane] = reinterpret_cast<const unsigned *>(c_mc_counts)[lane];
@@ -711,7 +708,7 @@ template <int N>
 // writes nothing (the host, which reads the same totals, then runs the kernel again on a larger one).
 // Housekeeping that rides along (an extra kernel, copy or event on the map's stream would sit on the critical path in front of the
 // next integration): workgroup 0 writes the per-job records into pinned host memory (`host_info`, at most max_jobs of them; the
-// host needs them at the next recompute) and then `seq` into host_flags[6].
+// host needs them at the next recompute) and then `seq` into host_flags[MH_INFO_SEQ].
 __global__ __launch_bounds__(MESH_TRI_BLOCK, MESH_TRI_WAVES) void mesh_triangle_kernel(MapView M, MeshParams P, const MeshJob *__restrict__ jobs,
                                                                     const JobInfo *__restrict__ info, const TriRec *__restrict__ tris,
                                                                     const CubeCorners *__restrict__ corners, const int *__restrict__ totals,
@@ -741,7 +738,7 @@ __global__ __launch_bounds__(MESH_TRI_BLOCK, MESH_TRI_WAVES) void mesh_triangle_
     const int n_jobs = totals[MC_JOBS];
     if ((publish & 1) && blockIdx.x == 0 && threadIdx.x == 0) {  // (publish: bit 0 = totals to the host, bit 1 = the kept job list was this recompute's input)
         // The recompute's totals, straight into pinned host memory as ONE 16-byte store -- {triangles, grids, jobs | overflow << 31,
-        // sequence number} -- before anything else: the host polls word 3 for this recompute's sequence number when the caller next
+        // sequence number}, MH_TRIS .. MH_SEQ -- before anything else: the host polls for this recompute's sequence number when the caller next
         // touches the map.  No copy engine, no event, no stream wait and no kernel of its own in between (an event record on the
         // map's stream costs a barrier packet of 7-12 us in front of the next kernel, a one-thread kernel 5 us).
         uint4 v;
@@ -749,12 +746,12 @@ __global__ __launch_bounds__(MESH_TRI_BLOCK, MESH_TRI_WAVES) void mesh_triangle_
         v.y = (unsigned)totals[MC_GRIDS];
         v.z = (unsigned)n_jobs | (totals[MC_OVERFLOW] ? 0x80000000u : 0u);
         v.w = (unsigned)seq;
-        *reinterpret_cast<uint4 *>(const_cast<int *>(host_flags)) = v;
+        *reinterpret_cast<uint4 *>(const_cast<int *>(host_flags + MH_TRIS)) = v;
         // what the host polls is a second copy of the sequence number behind a system-scope fence: that the 16 bytes above arrive
         // as one piece is how the bus behaves, not a guarantee (this thread alone pays the few hundred nanoseconds)
-        host_flags[4] = (totals[MC_OVERFLOW] == 0 && (size_t)n_tris * 9 * (P.use_color ? 3 : 2) + (size_t)totals[MC_GRIDS] * 3 <= arena_floats) ? 0 : 1;  // (`fits`, below)
+        host_flags[MH_UNFIT] = (totals[MC_OVERFLOW] == 0 && (size_t)n_tris * 9 * (P.use_color ? 3 : 2) + (size_t)totals[MC_GRIDS] * 3 <= arena_floats) ? 0 : 1;  // (`fits`, below)
         __threadfence_system();
-        host_flags[5] = seq;
+        host_flags[MH_PUBLISHED] = seq;
         // the job list the integration kernels keep has been consumed by the count kernel (its number is in totals[3]): empty again
         if ((publish & 2) && M.mesh_ctl) M.mesh_ctl[MC_KEPT] = 0;
     }
@@ -769,7 +766,7 @@ __global__ __launch_bounds__(MESH_TRI_BLOCK, MESH_TRI_WAVES) void mesh_triangle_
         for (int i = threadIdx.x; i < n; i += MESH_TRI_BLOCK) host_info[i] = src[i];
         __threadfence_system();
         __syncthreads();
-        if (threadIdx.x == 0) host_flags[6] = seq;
+        if (threadIdx.x == 0) host_flags[MH_INFO_SEQ] = seq;
     }
     if (fits) {
     float *vertices = arena, *normals = arena + nv3, *colors = P.use_color ? arena + 2 * nv3 : nullptr;
@@ -1008,7 +1005,7 @@ __global__ void shade_vertices_kernel(MapView M, MeshParams P, const float *__re
     }
 }
 
-struct MeshBuffers {
+struct MeshBuffers {             // (pointers only: the map owns what they point at, chisel_hip.hip)
     MeshJob *jobs = nullptr;
     int *ids = nullptr;
     JobInfo *info = nullptr; // [capacity] per-job results of a recompute
@@ -1027,19 +1024,5 @@ struct MeshBuffers {
     double *query = nullptr;
     float *cube = nullptr;      // result of mesh_one_cube_kernel
 };
-inline void free_mesh_buffers(MeshBuffers &b) {
-    if (b.jobs) (void)hipFree(b.jobs);
-    if (b.ids) (void)hipFree(b.ids);
-    if (b.info) (void)hipFree(b.info);
-    if (b.totals) (void)hipFree(b.totals);
-    if (b.tris) (void)hipFree(b.tris);
-    if (b.corners) (void)hipFree(b.corners);
-    if (b.cnt) (void)hipFree(b.cnt);
-    if (b.job_acc) (void)hipFree(b.job_acc);
-    if (b.flags) (void)hipFree(b.flags);
-    if (b.query) (void)hipFree(b.query);
-    if (b.cube) (void)hipFree(b.cube);
-    b = MeshBuffers();
-}
 
 }  // namespace chisel_hip

@@ -9,7 +9,7 @@
 //   stereo_sparse_points_kernel Output's window loop (:231-357) per bound point: bounds from the masks, then the pixels it may write
 //   stereo_sparse_raster_kernel the same loop per pixel: the points whose window covers it, in index order
 //   stereo_resize_f32_kernel    the final cv::resize of the depth map to the camera size (:409)
-// The undistort maps are built on the host (stereo_undistort_map in chisel_hip.hip) and the 8-bit resize is
+// The undistort maps are built on the host (stereo_undistort_map in host_stereo.h) and the 8-bit resize is
 // condition_color_kernel (kernels_map.h).  Every value is exact integer arithmetic or the reference's double / float operations
 // in its order; the library builds with -ffp-contract=off.
 #pragma once
