@@ -68,6 +68,14 @@ class View(C.Structure):
                 ("cx", C.c_float), ("cy", C.c_float), ("near_plane", C.c_float), ("far_plane", C.c_float), ("step", C.c_float)]
 
 
+class Ray(C.Structure):
+    """chisel_hip_ray (include/chisel_hip.h): one ray of chisel_hip_cast_rays, 32 bytes"""
+    _fields_ = [("origin", C.c_float * 3), ("direction", C.c_float * 3), ("t_near", C.c_float), ("t_far", C.c_float)]
+
+
+RAY_MAX_SAMPLES = 65536  # CHISEL_HIP_RAY_MAX_SAMPLES
+
+
 EXPORTS = [
     "chisel_hip_abi_version", "chisel_hip_last_error", "chisel_hip_device_count", "chisel_hip_host_alloc", "chisel_hip_host_free", "chisel_hip_create",
     "chisel_hip_destroy", "chisel_hip_reset", "chisel_hip_set_integrator", "chisel_hip_set_stream",
@@ -85,6 +93,7 @@ EXPORTS = [
     "chisel_hip_stereo_bind_sparse_points", "chisel_hip_stereo_output_image", "chisel_hip_stereo_homography",
     "chisel_hip_get_counters", "chisel_hip_memory_statistics", "chisel_hip_topology_epoch", "chisel_hip_candidates", "chisel_hip_cloud_candidates", "chisel_hip_mesh_cube", "chisel_hip_write_mesh_ply", "chisel_hip_shade_vertices", "chisel_hip_generate_mesh", "chisel_hip_recompute_mesh", "chisel_hip_integrate_chunk", "chisel_hip_dirty_ids_device", "chisel_hip_mesh_shell_plan",
     "chisel_hip_shell_volume", "chisel_hip_set_profiling", "chisel_hip_get_profile", "chisel_hip_get_launch_stats", "chisel_hip_pool_info", "chisel_hip_mc_tables", "chisel_hip_mesh_cube_values", "chisel_hip_interpolate_vertex", "chisel_hip_raycast", "chisel_hip_chunk_owner", "chisel_hip_frustum", "chisel_hip_frustum_from_vectors", "chisel_hip_create_group", "chisel_hip_render_view",
+    "chisel_hip_query_points", "chisel_hip_cast_rays",
 ]
 # the device self-tests and debug read-outs include/chisel_hip_selftest.h declares
 SELFTEST_EXPORTS = [
@@ -231,6 +240,8 @@ def load_library():
     # entry points added after ABI version 1 was first built (an older library simply lacks them: A/B runs of tools/)
     for name, types in (("chisel_hip_wait_event", [vp, vp]), ("chisel_hip_record_event", [vp, vp]),
                         ("chisel_hip_order_stream_after_map", [vp, vp]), ("chisel_hip_order_map_after_stream", [vp, vp]),
+                        ("chisel_hip_query_points", [vp, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int]),
+                        ("chisel_hip_cast_rays", [vp, vp, C.c_int64, C.c_float, vp, vp, vp, vp, C.c_int]),
                         ("chisel_hip_kat_color_fresh", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_kat_color_any", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_debug_cloud_stats", [vp, i64p]),

@@ -99,6 +99,18 @@ def _pose12(pose):
     return (C.c_float * 12)(*p.tolist())
 
 
+def pack_rays(origins, directions, t_near, t_far):
+    """-> (n, 8) float32, one chisel_hip_ray per row: origin, direction, t_near, t_far.  origins (3,) or (n, 3), directions (n, 3),
+    t_near / t_far scalars or (n,)"""
+    d = np.asarray(directions, np.float32).reshape(-1, 3)
+    rays = np.empty((len(d), 8), np.float32)
+    rays[:, 0:3] = np.asarray(origins, np.float32)
+    rays[:, 3:6] = d
+    rays[:, 6] = np.asarray(t_near, np.float32)
+    rays[:, 7] = np.asarray(t_far, np.float32)
+    return rays
+
+
 def depth_frame(depth, pose, camera):
     addr, dev, keep = _image_pointer(depth, np.float32)
     H, W = depth.shape[-2], depth.shape[-1]
@@ -482,6 +494,96 @@ class Chisel:
                "colors": np.empty((H, W, 3), np.float32) if colors else None}
         ptr = lambda a: a.ctypes.data if a is not None else None
         check(self.L.chisel_hip_render_view(self.h, C.byref(v), ptr(res["depth"]), ptr(res["normals"]), ptr(res["colors"]), 0))
+        return res
+
+    _POINT_OUTPUTS = (("found", np.uint8, ()), ("sdf", np.float32, ()), ("weight", np.float32, ()), ("gradient", np.float32, (3,)),
+                      ("colors", np.float32, (3,)))
+    _RAY_OUTPUTS = (("t_hit", np.float32, ()), ("status", np.uint8, ()), ("normals", np.float32, (3,)), ("colors", np.float32, (3,)))
+
+    @staticmethod
+    def _device_outputs(out, spec, n):
+        """addresses of the tensors of `out` in the order of `spec` (None where a name is missing), each checked"""
+        import torch
+        unknown = set(out) - {name for name, _, _ in spec}
+        assert not unknown, "out: unknown outputs %s" % sorted(unknown)
+        ptrs = []
+        for name, dtype, tail in spec:
+            t = out.get(name)
+            want = torch.uint8 if dtype is np.uint8 else torch.float32
+            assert t is None or (t.is_cuda and t.dtype == want and t.is_contiguous() and tuple(t.shape) == (n,) + tail), \
+                "out[%r]: a contiguous %s CUDA tensor of shape %s" % (name, want, (n,) + tail)
+            ptrs.append(t.data_ptr() if t is not None else None)
+        return ptrs
+
+    def QueryPoints(self, positions, sdf=True, weight=False, gradient=False, colors=False, out=None):
+        """chisel_hip_query_points: the map at the n positions (n, 3) in one launch.  -> {"found": (n,) uint8 -- bit 0 GetSDF(p) true,
+        bit 1 GetSDFAndGradient(p) true (only with gradient) --, "sdf": (n,), "weight": (n,), "gradient": (n, 3), "colors": (n, 3)}:
+        numpy arrays, float32 but for "found", None for what was not asked for; NaN where the map has no answer.
+        `out`: a dict of contiguous torch CUDA tensors of those shapes, with `positions` a contiguous float32 CUDA tensor that is
+        complete on the map's stream: exactly the outputs named in it are filled in place on the map's stream, nothing is waited
+        for; it is returned."""
+        if out is not None:
+            import torch
+            assert positions.is_cuda and positions.dtype == torch.float32 and positions.is_contiguous() and positions.dim() == 2 and \
+                positions.shape[1] == 3, "positions: a contiguous float32 CUDA tensor of shape (n, 3)"
+            n = int(positions.shape[0])
+            ptrs = self._device_outputs(out, self._POINT_OUTPUTS, n)
+            if n:  # (an empty tensor has no address)
+                check(self.L.chisel_hip_query_points(self.h, positions.data_ptr(), n, *ptrs, 1))
+            self._keep = [positions, out]
+            return out
+        p = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+        n = len(p)
+        asked = {"found": True, "sdf": sdf, "weight": weight, "gradient": gradient, "colors": colors}
+        res = {name: (np.empty((n,) + tail, dtype) if asked[name] else None) for name, dtype, tail in self._POINT_OUTPUTS}
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        check(self.L.chisel_hip_query_points(self.h, ptr(p), n, *[ptr(res[name]) for name, _, _ in self._POINT_OUTPUTS], 0))
+        return res
+
+    def CastRays(self, origins, directions, t_near, t_far, step=0.0, status=True, normals=False, colors=False, out=None):
+        """chisel_hip_cast_rays: RenderView's march along n rays of the caller's own.  origins, directions: (n, 3) (an origin of
+        shape (3,) serves every ray); t_near, t_far: scalars or (n,); the samples are origin + t direction for t = t_near + k step,
+        the direction as given (unit directions: t is Euclidean range); step <= 0 = the voxel resolution.
+        -> {"t_hit": (n,) float32, NaN without a hit, "status": (n,) uint8 -- 1 hit, 2 the ray came up behind a surface, 0 it never
+        ended --, "normals": (n, 3), "colors": (n, 3)}, None for what was not asked for.
+        `out`: a dict of contiguous torch CUDA tensors of those shapes ("t_hit" required), with origins, directions (and t_near,
+        t_far, where they are not scalars) float32 CUDA tensors: the rays are packed on torch's current stream, the map's stream is
+        ordered behind it (and torch's stream behind the kernel, which reads a buffer of this call's own), the outputs named in
+        `out` are filled in place and nothing is waited for by the host; `out` is returned.  Rays
+        that are packed already -- a (n, 8) tensor origin, direction, t_near, t_far per row -- go in as `origins` with
+        directions None."""
+        if out is not None:
+            import torch
+            if directions is None:
+                rays = origins
+            else:
+                n = int(directions.shape[0])
+                rays = torch.empty((n, 8), dtype=torch.float32, device=directions.device)
+                rays[:, 0:3] = origins
+                rays[:, 3:6] = directions
+                rays[:, 6] = t_near
+                rays[:, 7] = t_far
+            assert rays.is_cuda and rays.dtype == torch.float32 and rays.is_contiguous() and rays.dim() == 2 and rays.shape[1] == 8, \
+                "packed rays: a contiguous float32 CUDA tensor of shape (n, 8)"
+            n = int(rays.shape[0])
+            ptrs = self._device_outputs(out, self._RAY_OUTPUTS, n)
+            assert out.get("t_hit") is not None, "out['t_hit'] is required"
+            if n:
+                if directions is not None:  # (packed just now, on torch's stream)
+                    self.order_map_after_stream(torch.cuda.current_stream().cuda_stream)
+                check(self.L.chisel_hip_cast_rays(self.h, rays.data_ptr(), n, float(step), *ptrs, 1))
+                if directions is not None:
+                    # the packed rays are this call's own: when the tensor is released its block goes back to torch's stream, so that
+                    # stream is ordered behind the kernel that reads it (the caller's own tensors are the caller's to keep)
+                    self.order_stream_after_map(torch.cuda.current_stream().cuda_stream)
+            self._keep = [rays, out]
+            return out
+        rays = pack_rays(origins, directions, t_near, t_far)
+        n = len(rays)
+        asked = {"t_hit": True, "status": status, "normals": normals, "colors": colors}
+        res = {name: (np.empty((n,) + tail, dtype) if asked[name] else None) for name, dtype, tail in self._RAY_OUTPUTS}
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        check(self.L.chisel_hip_cast_rays(self.h, ptr(rays), n, float(step), *[ptr(res[name]) for name, _, _ in self._RAY_OUTPUTS], 0))
         return res
 
     def MemoryStatistics(self):

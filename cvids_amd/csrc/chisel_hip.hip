@@ -36,6 +36,7 @@
 #include "kernels_map.h"
 #include "kernels_mesh.h"
 #include "kernels_render.h"
+#include "kernels_query.h"
 #include "kernels_cloud.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
@@ -3031,4 +3032,5 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 
 }  // extern "C"
 
+#include "host_query.h"
 #include "host_selftest.h"

@@ -45,7 +45,7 @@ extern "C" {
  *      chisel_hip_frustum_from_vectors, chisel_hip_order_stream_after_map / _map_after_stream, the wait-free sharded recompute
  *      (chisel_hip_shell_plan_queue, _import_shells_fixed, _shell_commit), the stereo matcher (chisel_hip_stereo_*)
  *   3  chisel_hip_export_chunks, _import_ghost_chunks, _export_shells, _import_ghost_shells removed; later additions within 3 (nothing
- *      removed or re-typed): chisel_hip_render_view */
+ *      removed or re-typed): chisel_hip_render_view, chisel_hip_query_points, chisel_hip_cast_rays */
 #define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -532,6 +532,46 @@ typedef struct {
  * otherwise host arrays, complete on return.  CHISEL_HIP_ERR_INVALID: colors on a map without colour voxels, K < 1 or K > 65536, a
  * non-positive size; CHISEL_HIP_ERR_UNSUPPORTED: a group or one shard of several (a ray needs every owner's voxels). */
 int chisel_hip_render_view(chisel_hip_map *map, const chisel_hip_view *view, float *depth, float *normals, float *colors, int on_device);
+/* Not in the reference: the map read at n positions of the caller's in one launch (one thread per position; DESIGN.md "Querying points
+ * and rays" has the definition to the bit).  Any output may be NULL; what is not asked for is not computed.  Per position p:
+ *   found     bit 0: ChunkManager::GetSDF(p) returns true (src/ChunkManager.cpp:476-499); bit 1: GetSDFAndGradient(p) does (:449-474) --
+ *             evaluated only when `gradient` is asked for, 0 otherwise
+ *   sdf       the stored distance of the voxel GetSDF reads (the float whose double chisel_hip_get_sdf returns); NaN where bit 0 is clear
+ *   weight    the weight of that voxel wherever its chunk is resident and the linear voxel id in range (Chunk.h:81-84), weights
+ *             <= 1e-12 included; NaN elsewhere
+ *   gradient  3 floats: what chisel_hip_get_sdf_and_gradient returns; NaN x 3 where bit 1 is clear
+ *   colors    3 floats: ChunkManager::InterpolateColor(p) (:501-573), what chisel_hip_shade_vertices (stage 2) writes, its (0, 0, 0)
+ *             answers included
+ * A position with a non-finite component is answered without a look at the map: found 0, NaN in every other output.  on_device:
+ * positions and outputs are device pointers, the kernel goes on the map's stream (behind the event of a chisel_hip_wait_event or
+ * chisel_hip_order_map_after_stream before it, which says that the positions are ready) and nothing is waited for; otherwise host
+ * arrays, complete on return.  The map is only read.  CHISEL_HIP_ERR_UNSUPPORTED: a group or one shard of several.  Then
+ * CHISEL_HIP_ERR_INVALID for n < 0; then n == 0 is CHISEL_HIP_OK, launches nothing and looks at no other argument; then
+ * CHISEL_HIP_ERR_INVALID for null positions, no output at all, or colors on a map without colour voxels. */
+int chisel_hip_query_points(chisel_hip_map *map, const float *positions /* 3 n */, int64_t n, uint8_t *found, float *sdf, float *weight,
+                            float *gradient /* 3 n */, float *colors /* 3 n */, int on_device);
+/* A ray for chisel_hip_cast_rays: the samples are origin + t direction, t from t_near to t_far.  The direction is used as given (t is
+ * in units of its length: unit directions give Euclidean range).  Device arrays of rays are 16-byte aligned. */
+typedef struct {
+    float origin[3];
+    float direction[3];
+    float t_near, t_far;
+} chisel_hip_ray;           /* 32 bytes */
+#define CHISEL_HIP_RAY_MAX_SAMPLES 65536 /* per ray (chisel_hip_render_view's limit) */
+/* Not in the reference: chisel_hip_render_view's march along n rays of the caller's, one ray per lane in the caller's order.  Ray r
+ * takes K = floor((t_far - t_near) / step) + 1 samples (at most CHISEL_HIP_RAY_MAX_SAMPLES; none where the quotient is negative or NaN,
+ * or the ray has a non-finite origin, direction or t_near) ChunkManager::GetSDF (nearest voxel) at t_k = t_near + k step; step <= 0:
+ * the map's voxel resolution.  It ends at the first observed sample with a distance <= 0.
+ *   status   1 (hit): the sample before the end is observed with a distance > 0; 2: the ray ended otherwise (it came up behind a
+ *            surface); 0: it took all its samples without ending, or took none
+ *   t_hit    status 1: where the distance changes sign between the two samples, interpolated linearly; NaN otherwise.  Required.
+ *   normals / colors (3 floats per ray): as chisel_hip_render_view shades a hit, at origin + t_hit direction; NaN without a hit
+ * status, normals and colors may be NULL.  A ray's outputs depend on that ray and the map alone, not on its neighbours or its place
+ * in the array.  The rays of a chisel_hip_view (direction = R (xc, yc, 1), t_near = near, t_far = far) give chisel_hip_render_view's
+ * image bit for bit.  on_device, the map, n == 0 and the error codes: as chisel_hip_query_points; also CHISEL_HIP_ERR_INVALID for a
+ * NaN step or a null t_hit.  DESIGN.md "Querying points and rays" has the definition to the bit. */
+int chisel_hip_cast_rays(chisel_hip_map *map, const chisel_hip_ray *rays, int64_t n, float step, float *t_hit, uint8_t *status,
+                         float *normals /* 3 n */, float *colors /* 3 n */, int on_device);
 /* ProjectionIntegrator::Integrate<DataType>(depthImage, camera, cameraPose, chunk) / IntegrateColor (ProjectionIntegrator.h:51-52,
  * :101-102): ONE frame into ONE resident chunk -- whether or not the frustum's id range holds it, as the reference's per-chunk call
  * knows nothing of frusta --; color may be NULL (the depth-only update rule).  *updated = the call's return value there ("some voxel
