@@ -76,6 +76,22 @@ class Ray(C.Structure):
 RAY_MAX_SAMPLES = 65536  # CHISEL_HIP_RAY_MAX_SAMPLES
 
 
+class AlignParams(C.Structure):
+    """chisel_hip_align_params (include/chisel_hip.h): the loop of chisel_hip_align_depth, 40 bytes"""
+    _fields_ = [("max_iterations", C.c_int), ("min_pixels", C.c_int), ("max_residual", C.c_float), ("reserved", C.c_float),
+                ("damping", C.c_double), ("min_translation", C.c_double), ("min_rotation", C.c_double)]
+
+
+class AlignResult(C.Structure):
+    """chisel_hip_align_result (include/chisel_hip.h), 664 bytes"""
+    _fields_ = [("pose", C.c_double * 12), ("xi_last", C.c_double * 6), ("terms_first", C.c_double * 32), ("terms_last", C.c_double * 32),
+                ("iterations", C.c_int), ("status", C.c_int)]
+
+
+ALIGN_CONVERGED, ALIGN_ITERATION_LIMIT, ALIGN_TOO_FEW_PIXELS, ALIGN_DEGENERATE = 0, 1, 2, 3  # CHISEL_HIP_ALIGN_*
+ALIGN_STATUS = {0: "CONVERGED", 1: "ITERATION_LIMIT", 2: "TOO_FEW_PIXELS", 3: "DEGENERATE"}
+
+
 EXPORTS = [
     "chisel_hip_abi_version", "chisel_hip_last_error", "chisel_hip_device_count", "chisel_hip_host_alloc", "chisel_hip_host_free", "chisel_hip_create",
     "chisel_hip_destroy", "chisel_hip_reset", "chisel_hip_set_integrator", "chisel_hip_set_stream",
@@ -93,7 +109,7 @@ EXPORTS = [
     "chisel_hip_stereo_bind_sparse_points", "chisel_hip_stereo_output_image", "chisel_hip_stereo_homography",
     "chisel_hip_get_counters", "chisel_hip_memory_statistics", "chisel_hip_topology_epoch", "chisel_hip_candidates", "chisel_hip_cloud_candidates", "chisel_hip_mesh_cube", "chisel_hip_write_mesh_ply", "chisel_hip_shade_vertices", "chisel_hip_generate_mesh", "chisel_hip_recompute_mesh", "chisel_hip_integrate_chunk", "chisel_hip_dirty_ids_device", "chisel_hip_mesh_shell_plan",
     "chisel_hip_shell_volume", "chisel_hip_set_profiling", "chisel_hip_get_profile", "chisel_hip_get_launch_stats", "chisel_hip_pool_info", "chisel_hip_mc_tables", "chisel_hip_mesh_cube_values", "chisel_hip_interpolate_vertex", "chisel_hip_raycast", "chisel_hip_chunk_owner", "chisel_hip_frustum", "chisel_hip_frustum_from_vectors", "chisel_hip_create_group", "chisel_hip_render_view",
-    "chisel_hip_query_points", "chisel_hip_cast_rays",
+    "chisel_hip_query_points", "chisel_hip_cast_rays", "chisel_hip_align_terms", "chisel_hip_align_solve", "chisel_hip_align_depth",
 ]
 # the device self-tests and debug read-outs include/chisel_hip_selftest.h declares
 SELFTEST_EXPORTS = [
@@ -242,6 +258,9 @@ def load_library():
                         ("chisel_hip_order_stream_after_map", [vp, vp]), ("chisel_hip_order_map_after_stream", [vp, vp]),
                         ("chisel_hip_query_points", [vp, vp, C.c_int64, vp, vp, vp, vp, vp, C.c_int]),
                         ("chisel_hip_cast_rays", [vp, vp, C.c_int64, C.c_float, vp, vp, vp, vp, C.c_int]),
+                        ("chisel_hip_align_terms", [vp, C.POINTER(DepthFrame), C.c_float, vp, C.c_int]),
+                        ("chisel_hip_align_solve", [C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double)]),
+                        ("chisel_hip_align_depth", [vp, C.POINTER(DepthFrame), C.POINTER(AlignParams), C.POINTER(AlignResult)]),
                         ("chisel_hip_kat_color_fresh", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_kat_color_any", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_debug_cloud_stats", [vp, i64p]),

@@ -586,6 +586,38 @@ class Chisel:
         check(self.L.chisel_hip_cast_rays(self.h, ptr(rays), n, float(step), *[ptr(res[name]) for name, _, _ in self._RAY_OUTPUTS], 0))
         return res
 
+    def AlignTerms(self, depth, pose, camera, max_residual=0.0, out=None):
+        """chisel_hip_align_terms: the normal equations of one Gauss-Newton step that aligns the depth image (numpy, or a torch CUDA
+        tensor used in place) taken by `camera` at the guess `pose` (camera -> world) to the map.  -> (32,) float64: [0..20] the upper
+        triangle of sum J J^T, [21..26] sum J rho, [27] sum rho^2, [28] used pixels, [29] valid pixels, [30], [31] 0.
+        `out`: a contiguous float64 torch CUDA tensor of 32 elements, filled on the map's stream, nothing waited for; it is returned."""
+        f, keep = depth_frame(depth, pose, camera)
+        if out is not None:
+            import torch
+            assert out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 32, \
+                "out: a contiguous float64 CUDA tensor of 32 elements"
+            check(self.L.chisel_hip_align_terms(self.h, C.byref(f), float(max_residual), out.data_ptr(), 1))
+            self._keep = [keep, out]
+            return out
+        terms = np.empty(32, np.float64)
+        check(self.L.chisel_hip_align_terms(self.h, C.byref(f), float(max_residual), terms.ctypes.data, 0))
+        return terms
+
+    def AlignDepth(self, depth, pose, camera, max_iterations=10, max_residual=0.0, damping=1e-3, min_translation=1e-5,
+                   min_rotation=1e-5, min_pixels=100):
+        """chisel_hip_align_depth: Gauss-Newton on the pose of a depth frame against the map, from the guess `pose` -- to refine a
+        keyframe's pose before IntegrateDepthScan.  -> {"pose": (3, 4) float64, "status": capi.ALIGN_*, "iterations": updates applied,
+        "xi_last": (6,) the last update (v, w), "terms_first" / "terms_last": (32,) AlignTerms at the guess / as last evaluated}.
+        All four statuses are outcomes, not errors."""
+        f, keep = depth_frame(depth, pose, camera)
+        p = capi.AlignParams(int(max_iterations), int(min_pixels), float(max_residual), 0.0, float(damping), float(min_translation),
+                             float(min_rotation))
+        r = capi.AlignResult()
+        check(self.L.chisel_hip_align_depth(self.h, C.byref(f), C.byref(p), C.byref(r)))
+        return {"pose": np.array(r.pose, np.float64).reshape(3, 4), "status": int(r.status), "iterations": int(r.iterations),
+                "xi_last": np.array(r.xi_last, np.float64), "terms_first": np.array(r.terms_first, np.float64),
+                "terms_last": np.array(r.terms_last, np.float64)}
+
     def MemoryStatistics(self):
         """ChunkManager::PrintMemoryStatistics (ChunkManager.cpp:641-678) as numbers: the voxel census of Chunk::ComputeStatistics over
         the resident chunks, the weight sum, the bounds of the chunk boxes and the two memory figures the reference prints (it
@@ -931,6 +963,18 @@ class DepthEstimator:
     def read(self, which, out=None):
         """the filter's maps (DepthFilter.read): DepthFilter.DEPTH is the depth map ServerKeyFrame integrates"""
         return self.filter.read(which, out=out)
+
+
+def align_solve(terms, damping):
+    """chisel_hip_align_solve: the Gauss-Newton step xi = (v, w), (6,) float64, of the normal equations `terms` (32 doubles as
+    Chisel.AlignTerms gives them) with absolute damping per used pixel; host arithmetic, no GPU needed.  Degenerate equations raise
+    ChiselHipError with code 5."""
+    L = capi.load_library()
+    t = np.ascontiguousarray(terms, np.float64).reshape(32)
+    xi = np.zeros(6, np.float64)
+    dp = C.POINTER(C.c_double)
+    check(L.chisel_hip_align_solve(t.ctypes.data_as(dp), float(damping), xi.ctypes.data_as(dp)))
+    return xi
 
 
 def condition_depth(depth64, width=640, height=480, intrinsics=None):

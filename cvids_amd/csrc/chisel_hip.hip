@@ -37,6 +37,7 @@
 #include "kernels_mesh.h"
 #include "kernels_render.h"
 #include "kernels_query.h"
+#include "kernels_align.h"
 #include "kernels_cloud.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
@@ -302,6 +303,13 @@ struct chisel_hip_map {
     // scratch for queries
     DeviceBuffer<int> scratch_i;
     size_t scratch_i_elems = 0;
+    struct AlignMemory {                 // frame-to-model alignment (host_align.h), allocated on first use, grown on demand
+        DeviceBuffer<double> partials;   // the levels of the summation tree one behind the other: [ALIGN_SUMS][groups] each
+        size_t partials_elems = 0;
+        DeviceBuffer<double> terms;      // [ALIGN_TERMS]: where the tree ends when the caller's array is on the host
+        DeviceBuffer<float> depth;       // staging of a host frame
+        size_t depth_elems = 0;
+    } align_mem;
     // meshing state
     int update_meshes_calls = 0;                                       // Chisel.cpp:53 "static int cnt"
     std::unordered_map<uint64_t, MeshRef, IdHash> meshes;              // ChunkManager::allMeshes
@@ -3033,4 +3041,5 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 }  // extern "C"
 
 #include "host_query.h"
+#include "host_align.h"
 #include "host_selftest.h"

@@ -45,7 +45,8 @@ extern "C" {
  *      chisel_hip_frustum_from_vectors, chisel_hip_order_stream_after_map / _map_after_stream, the wait-free sharded recompute
  *      (chisel_hip_shell_plan_queue, _import_shells_fixed, _shell_commit), the stereo matcher (chisel_hip_stereo_*)
  *   3  chisel_hip_export_chunks, _import_ghost_chunks, _export_shells, _import_ghost_shells removed; later additions within 3 (nothing
- *      removed or re-typed): chisel_hip_render_view, chisel_hip_query_points, chisel_hip_cast_rays */
+ *      removed or re-typed): chisel_hip_render_view, chisel_hip_query_points, chisel_hip_cast_rays, chisel_hip_align_terms,
+ *      chisel_hip_align_solve, chisel_hip_align_depth */
 #define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -572,6 +573,55 @@ typedef struct {
  * NaN step or a null t_hit.  DESIGN.md "Querying points and rays" has the definition to the bit. */
 int chisel_hip_cast_rays(chisel_hip_map *map, const chisel_hip_ray *rays, int64_t n, float step, float *t_hit, uint8_t *status,
                          float *normals /* 3 n */, float *colors /* 3 n */, int on_device);
+/* Not in the reference: the normal equations of one Gauss-Newton step that aligns a depth frame to the map (point-to-surface against the
+ * TSDF; DESIGN.md "Aligning a frame to the map" has the definition to the bit).  frame->pose is the guess, camera -> world.  Pixel i
+ * with depth z is VALID when z is finite and near <= z <= far; its point p = o + z d lies on chisel_hip_render_view's ray of that pixel;
+ * ChunkManager::GetSDFAndGradient(p) (src/ChunkManager.cpp:449-474, called unchanged) gives the distance d0 at the centre c of p's
+ * voxel and the normalised gradient g; the residual is rho = d0 + g . (p - c); the pixel is USED when it is valid, the lookup succeeds
+ * and, with max_residual > 0, |rho| <= max_residual.  With J = (g, p x g) in double -- the left perturbation p' = p + v + w x p,
+ * xi = (v, w) -- terms[32] holds over the used pixels:
+ *   [0..20] the upper triangle of sum J J^T, row-major;  [21..26] sum J rho;  [27] sum rho^2;  [28] the number of used pixels;
+ *   [29] the number of valid pixels;  [30], [31] 0
+ * Every sum is taken in one fixed order (a pairwise tree over groups of 256 pixels in row-major order), without atomics: the 32 doubles
+ * are the same bits on every run.  frame->on_device as in chisel_hip_integrate_depth; terms_on_device: terms is a device pointer,
+ * written on the map's stream without a wait (behind the event of a chisel_hip_wait_event or chisel_hip_order_map_after_stream before
+ * it, which says that a device image is ready); otherwise a host array, complete on return.  The map is only read.
+ * CHISEL_HIP_ERR_UNSUPPORTED: a group or one shard of several (a point needs every owner's voxels).  Then CHISEL_HIP_ERR_INVALID for a
+ * null argument or image, or a non-positive size. */
+int chisel_hip_align_terms(chisel_hip_map *map, const chisel_hip_depth_frame *frame, float max_residual, double *terms /* 32 */, int terms_on_device);
+/* The step of those normal equations, on the host in double (no device is needed): A = the symmetric matrix of terms[0..20] with
+ * damping * terms[28] added to its diagonal (absolute Tikhonov damping per used pixel), Cholesky A = L L^T in which a pivot s is accepted
+ * iff s > 1e-12 max_j A_jj, then A xi = -terms[21..26] by forward and back substitution.  xi = (v, w).  CHISEL_HIP_ERR_UNSUPPORTED when
+ * a pivot is refused (the equations are degenerate; xi is left alone), CHISEL_HIP_ERR_INVALID for a null argument. */
+int chisel_hip_align_solve(const double terms[32], double damping, double xi[6]);
+typedef struct {
+    int max_iterations;      /* >= 1                                                                     */
+    int min_pixels;          /* fewer used pixels than this: CHISEL_HIP_ALIGN_TOO_FEW_PIXELS             */
+    float max_residual;      /* [m]; <= 0: every valid pixel whose lookup succeeds is used               */
+    float reserved;
+    double damping;          /* chisel_hip_align_solve's                                                  */
+    double min_translation;  /* [m] and ...                                                               */
+    double min_rotation;     /* ... [rad]: an update smaller than both ends the loop                      */
+} chisel_hip_align_params;  /* 40 bytes */
+typedef struct {
+    double pose[12];         /* the refined pose, camera -> world, row-major 3 x 4                        */
+    double xi_last[6];       /* the last update applied (zeros when there was none)                       */
+    double terms_first[32];  /* chisel_hip_align_terms at the guess ...                                   */
+    double terms_last[32];   /* ... and as last evaluated (at the pose before the last update)            */
+    int iterations;          /* updates applied                                                           */
+    int status;              /* CHISEL_HIP_ALIGN_*                                                        */
+} chisel_hip_align_result;  /* 664 bytes */
+#define CHISEL_HIP_ALIGN_CONVERGED 0       /* the last update was smaller than min_translation and min_rotation */
+#define CHISEL_HIP_ALIGN_ITERATION_LIMIT 1 /* max_iterations updates applied                                     */
+#define CHISEL_HIP_ALIGN_TOO_FEW_PIXELS 2  /* terms[28] < min_pixels: the pose is as before that iteration       */
+#define CHISEL_HIP_ALIGN_DEGENERATE 3      /* chisel_hip_align_solve refused a pivot: likewise                    */
+/* Gauss-Newton on the pose of a depth frame against the map: up to max_iterations times chisel_hip_align_terms at the current pose
+ * (kept in double, handed to the kernels rounded to float), chisel_hip_align_solve, and the update R <- R_d R, t <- R_d t + v with
+ * R_d = I + (sin th / th) K + ((1 - cos th) / th^2) K^2, K the cross-product matrix of w, th = |w| (R_d = I + K where th <= 1e-12).
+ * A host image is copied to the device once.  All four statuses are outcomes and return CHISEL_HIP_OK; the map is only read; complete on
+ * return.  Error codes as chisel_hip_align_terms; also CHISEL_HIP_ERR_INVALID for null params or result or max_iterations < 1. */
+int chisel_hip_align_depth(chisel_hip_map *map, const chisel_hip_depth_frame *frame, const chisel_hip_align_params *params,
+                           chisel_hip_align_result *result);
 /* ProjectionIntegrator::Integrate<DataType>(depthImage, camera, cameraPose, chunk) / IntegrateColor (ProjectionIntegrator.h:51-52,
  * :101-102): ONE frame into ONE resident chunk -- whether or not the frustum's id range holds it, as the reference's per-chunk call
  * knows nothing of frusta --; color may be NULL (the depth-only update rule).  *updated = the call's return value there ("some voxel
