@@ -66,6 +66,15 @@ int fail(int code, const std::string &msg) {
             return fail(CHISEL_HIP_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));         \
     } while (0)
 
+// `...` once for the map's chunk size, with N that size as a constant: the switch every launch of a kernel<N> goes through
+// (chisel_hip_create admits 8, 16 and 32 only)
+#define FOR_CHUNK_SIZE(n, ...)                                        \
+    switch (n) {                                                      \
+        case 8: { constexpr int N = 8; __VA_ARGS__; } break;          \
+        case 16: { constexpr int N = 16; __VA_ARGS__; } break;        \
+        case 32: { constexpr int N = 32; __VA_ARGS__; } break;        \
+    }
+
 struct IdHash {
     size_t operator()(uint64_t k) const { return (size_t)(k * 0x9E3779B97F4A7C15ull); }
 };
@@ -983,11 +992,8 @@ void launch_fixed_drop(chisel_hip_map *m, const int *latch) {
 int replay_deferred_set(chisel_hip_map *m, int set) {
     chisel_hip_map::BatchSet &bs = m->sets[set];
     m->launch_stats[LS_REPLAYED]++;
-    switch (m->N) {
-        case 8: return launch_back<8>(m, bs, bs.replay_ip, bs.replay_color, bs.replay_total, bs.replay_inline, true);
-        case 16: return launch_back<16>(m, bs, bs.replay_ip, bs.replay_color, bs.replay_total, bs.replay_inline, true);
-        default: return launch_back<32>(m, bs, bs.replay_ip, bs.replay_color, bs.replay_total, bs.replay_inline, true);
-    }
+    FOR_CHUNK_SIZE(m->N, return launch_back<N>(m, bs, bs.replay_ip, bs.replay_color, bs.replay_total, bs.replay_inline, true));
+    return fail(CHISEL_HIP_ERR_UNSUPPORTED, "chunk size");
 }
 
 int check_frame(chisel_hip_map *m, const chisel_hip_depth_frame *f, const chisel_hip_color_frame *c) {
@@ -1209,11 +1215,7 @@ int integrate_group(chisel_hip_map *m, int n, const chisel_hip_depth_frame *fram
         rc = maybe_grow(m, std::max<int64_t>(256, 2 * (int64_t)items_hint));
         if (rc) return rc;
     }
-    switch (m->N) {
-        case 8: return launch_group<8>(m, bs, PP, CP, IP, color);
-        case 16: return launch_group<16>(m, bs, PP, CP, IP, color);
-        case 32: return launch_group<32>(m, bs, PP, CP, IP, color);
-    }
+    FOR_CHUNK_SIZE(m->N, return launch_group<N>(m, bs, PP, CP, IP, color));
     return fail(CHISEL_HIP_ERR_UNSUPPORTED, "chunk size");
 }
 
@@ -2905,86 +2907,6 @@ int chisel_hip_candidates(const float corners[24], const float planes[24], const
     return CHISEL_HIP_OK;
 }
 
-int chisel_hip_shade_vertices(chisel_hip_map *m, const float *vertices, int64_t n, float *normals, float *colors, int stages) {
-    SETTLE(m);
-    if (m && m->is_group) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "chisel_hip_shade_vertices reads the voxels around every vertex: ask the shard that owns them (a group's meshes are shaded by chisel_hip_update_meshes)");
-    if (!m || n < 0 || (n > 0 && !vertices)) return fail(CHISEL_HIP_ERR_INVALID, "bad argument");
-    if (n == 0) return CHISEL_HIP_OK;
-    HIP_TRY(hipSetDevice(m->device));
-    {
-        int rc_m = check_mesh_totals(m);
-        if (rc_m) return rc_m;
-    }
-    DeviceBuffer<float> d;
-    const size_t f = (size_t)n * 3;
-    HIP_TRY(d.alloc(3 * f));
-    float *dv = d.get(), *dn = d.get() + f, *dc = d.get() + 2 * f;
-    HIP_TRY(hipMemcpyAsync(dv, vertices, f * sizeof(float), hipMemcpyHostToDevice, m->stream));
-    if (normals && (stages & 1)) HIP_TRY(hipMemcpyAsync(dn, normals, f * sizeof(float), hipMemcpyHostToDevice, m->stream));
-    const MeshParams P = mesh_params(m);
-    const dim3 grid((unsigned)((n + 255) / 256));
-    switch (m->N) {
-        case 8: hipLaunchKernelGGL(shade_vertices_kernel<8>, grid, dim3(256), 0, m->stream, m->view, P, dv, (long long)n, dn, dc, stages); break;
-        case 16: hipLaunchKernelGGL(shade_vertices_kernel<16>, grid, dim3(256), 0, m->stream, m->view, P, dv, (long long)n, dn, dc, stages); break;
-        case 32: hipLaunchKernelGGL(shade_vertices_kernel<32>, grid, dim3(256), 0, m->stream, m->view, P, dv, (long long)n, dn, dc, stages); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && normals && (stages & 1)) e = hipMemcpyAsync(normals, dn, f * sizeof(float), hipMemcpyDeviceToHost, m->stream);
-    if (e == hipSuccess && colors && (stages & 2) && m->view.rgbw) e = hipMemcpyAsync(colors, dc, f * sizeof(float), hipMemcpyDeviceToHost, m->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    if (e != hipSuccess) return fail(CHISEL_HIP_ERR_HIP, std::string("chisel_hip_shade_vertices: ") + hipGetErrorString(e));
-    return CHISEL_HIP_OK;
-}
-
-// One ray march per pixel over the voxels as they are (kernels_render.h; DESIGN.md "Rendering a view"): the map is only read.
-int chisel_hip_render_view(chisel_hip_map *m, const chisel_hip_view *view, float *depth, float *normals, float *colors, int on_device) {
-    SETTLE(m);
-    if (m && m->is_group) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "chisel_hip_render_view marches every ray through the voxels of all owners: a group's shards hold a part each (render a map of one shard)");
-    if (!m || !view || !depth) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
-    if (m->cfg.n_shards > 1) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "chisel_hip_render_view marches every ray through the voxels of all owners: this map is one shard of several");
-    if (view->width < 1 || view->height < 1) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_render_view: non-positive image size");
-    if (colors && !m->view.rgbw) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_render_view: colours asked of a map without colour voxels");
-    RenderCamera cam;
-    memcpy(cam.pose, view->pose, sizeof(cam.pose));
-    cam.fx = view->fx; cam.fy = view->fy; cam.cx = view->cx; cam.cy = view->cy;
-    cam.near_plane = view->near_plane;
-    cam.step = view->step > 0.0f ? view->step : m->cfg.voxel_resolution;
-    cam.width = view->width; cam.height = view->height;
-    const float last = floorf((view->far_plane - view->near_plane) / cam.step);  // K = (int)floorf((far - near) / step) + 1
-    if (!(last >= 0.0f) || last > (float)(RENDER_MAX_SAMPLES - 1)) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_render_view: (far - near) / step gives less than 1 or more than 65536 samples per ray");
-    cam.n_samples = (int)last + 1;
-    HIP_TRY(hipSetDevice(m->device));
-    {
-        int rc_m = check_mesh_totals(m);
-        if (rc_m) return rc_m;
-    }
-    const size_t px = (size_t)view->width * view->height;
-    DeviceBuffer<float> d;
-    float *dd = depth, *dn = normals, *dc = colors;
-    if (!on_device) {
-        HIP_TRY(d.alloc(7 * px));
-        dd = d.get();
-        dn = normals ? d.get() + px : nullptr;
-        dc = colors ? d.get() + 4 * px : nullptr;
-    }
-    const MeshParams P = mesh_params(m);
-    const dim3 grid((unsigned)((view->width + 15) / 16), (unsigned)((view->height + 15) / 16));
-    switch (m->N) {
-        case 8: hipLaunchKernelGGL(render_view_kernel<8>, grid, dim3(256), 0, m->stream, m->view, P, cam, dd, dn, dc); break;
-        case 16: hipLaunchKernelGGL(render_view_kernel<16>, grid, dim3(256), 0, m->stream, m->view, P, cam, dd, dn, dc); break;
-        case 32: hipLaunchKernelGGL(render_view_kernel<32>, grid, dim3(256), 0, m->stream, m->view, P, cam, dd, dn, dc); break;
-    }
-    hipError_t e = hipGetLastError();
-    if (!on_device) {  // (device outputs are left on the map's stream: nothing is waited for)
-        if (e == hipSuccess) e = hipMemcpyAsync(depth, dd, px * sizeof(float), hipMemcpyDeviceToHost, m->stream);
-        if (e == hipSuccess && normals) e = hipMemcpyAsync(normals, dn, 3 * px * sizeof(float), hipMemcpyDeviceToHost, m->stream);
-        if (e == hipSuccess && colors) e = hipMemcpyAsync(colors, dc, 3 * px * sizeof(float), hipMemcpyDeviceToHost, m->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    }
-    if (e != hipSuccess) return fail(CHISEL_HIP_ERR_HIP, std::string("chisel_hip_render_view: ") + hipGetErrorString(e));
-    return CHISEL_HIP_OK;
-}
-
 int chisel_hip_set_profiling(chisel_hip_map *m, int enable) {
     if (m && m->is_group) return group::for_all(m, [&](chisel_hip_map *s) { return chisel_hip_set_profiling(s, enable); });
     if (!m) return fail(CHISEL_HIP_ERR_INVALID, "null map");
@@ -3040,6 +2962,7 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 
 }  // extern "C"
 
+#include "host_render.h"
 #include "host_query.h"
 #include "host_align.h"
 #include "host_selftest.h"

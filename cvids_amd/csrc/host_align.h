@@ -109,8 +109,7 @@ int launch_terms(chisel_hip_map *m, const chisel_hip_depth_frame *f, const float
         A.partials_elems = need;
     }
     AlignCamera cam;
-    memcpy(cam.pose, pose, sizeof(cam.pose));
-    cam.fx = f->fx; cam.fy = f->fy; cam.cx = f->cx; cam.cy = f->cy;
+    cam.cam = pixel_camera(pose, f->fx, f->fy, f->cx, f->cy);
     cam.near_plane = f->near_plane; cam.far_plane = f->far_plane;
     cam.max_residual = max_residual;
     cam.width = f->width;
@@ -118,11 +117,7 @@ int launch_terms(chisel_hip_map *m, const chisel_hip_depth_frame *f, const float
     const MeshParams P = mesh_params(m);
     int groups = (n + 255) / 256;
     double *level = groups > 1 ? A.partials.get() : d_terms;
-    switch (m->N) {
-        case 8: hipLaunchKernelGGL(align_terms_kernel<8>, dim3((unsigned)groups), dim3(256), 0, m->stream, m->view, P, cam, d_depth, n, level, groups); break;
-        case 16: hipLaunchKernelGGL(align_terms_kernel<16>, dim3((unsigned)groups), dim3(256), 0, m->stream, m->view, P, cam, d_depth, n, level, groups); break;
-        case 32: hipLaunchKernelGGL(align_terms_kernel<32>, dim3((unsigned)groups), dim3(256), 0, m->stream, m->view, P, cam, d_depth, n, level, groups); break;
-    }
+    FOR_CHUNK_SIZE(m->N, hipLaunchKernelGGL(align_terms_kernel<N>, dim3((unsigned)groups), dim3(256), 0, m->stream, m->view, P, cam, d_depth, n, level, groups));
     HIP_TRY(hipGetLastError());
     while (groups > 1) {
         const int next = (groups + 255) / 256;

@@ -3,6 +3,7 @@
 // copies of get().  Move-only; alloc() frees what was held before, and holds nothing after a failure.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <assert.h>
 #include <stddef.h>
 #include <utility>
 
@@ -56,6 +57,69 @@ struct PinnedBuffer {
 
 private:
     T *p_ = nullptr, *dev_ = nullptr;
+};
+
+inline size_t round16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
+
+// The host arrays of one read-only call, staged through ONE device allocation that lives as long as this object.  The caller hands
+// over its own pointers: in() / out() / inout() give an array that is asked for (non-null) a 16-byte-rounded section, begin()
+// allocates, points each of them at its section and queues the copies in on `stream`, finish() queues the copies out.  With
+// on_device the pointers are the device's already and stay as they are: nothing is allocated, copied or waited for.  Whatever was
+// queued is waited for before the buffer dies -- in finish(), also after a failed copy, or else in the destructor.
+class Staging {
+public:
+    Staging(hipStream_t stream, bool on_device) : stream_(stream), on_device_(on_device) {}
+    ~Staging() {
+        if (queued_) (void)hipStreamSynchronize(stream_);
+    }
+    template <class T> void in(const T *&p, size_t bytes) { add(p, bytes, true, false); }
+    template <class T> void out(T *&p, size_t bytes) { add(p, bytes, false, true); }
+    template <class T> void inout(T *&p, size_t bytes) { add(p, bytes, true, true); }
+    hipError_t begin() {
+        if (n_ == 0) return hipSuccess;
+        hipError_t e = buf_.alloc(total_);
+        queued_ = e == hipSuccess;
+        for (int i = 0; i < n_ && e == hipSuccess; i++) {
+            Section &s = sec_[i];
+            s.dev = buf_.get() + s.at;
+            s.point(s.slot, s.dev);
+            if (s.copy_in) e = hipMemcpyAsync(s.dev, s.host, s.bytes, hipMemcpyHostToDevice, stream_);
+        }
+        return e;
+    }
+    // `e`: what the launch said; the first error of it, the copies out and the wait
+    hipError_t finish(hipError_t e) {
+        if (on_device_) return e;
+        for (int i = 0; i < n_; i++)
+            if (e == hipSuccess && sec_[i].copy_out) e = hipMemcpyAsync(const_cast<void *>(sec_[i].host), sec_[i].dev, sec_[i].bytes, hipMemcpyDeviceToHost, stream_);
+        const hipError_t e_sync = hipStreamSynchronize(stream_);
+        queued_ = false;
+        return e == hipSuccess ? e_sync : e;
+    }
+
+private:
+    struct Section {
+        const void *host;
+        size_t bytes, at;
+        bool copy_in, copy_out;
+        void *slot;                               // the caller's pointer variable ...
+        void (*point)(void *slot, unsigned char *dev);  // ... and how to set it
+        unsigned char *dev;
+    };
+    template <class T>
+    void add(T *&p, size_t bytes, bool copy_in, bool copy_out) {
+        if (on_device_ || !p) return;
+        assert(n_ < MAX_SECTIONS);
+        sec_[n_++] = Section{p, bytes, total_, copy_in, copy_out, &p, [](void *slot, unsigned char *dev) { *static_cast<T **>(slot) = reinterpret_cast<T *>(dev); }, nullptr};
+        total_ += round16(bytes);
+    }
+    static constexpr int MAX_SECTIONS = 8;
+    hipStream_t stream_;
+    bool on_device_, queued_ = false;
+    Section sec_[MAX_SECTIONS];
+    int n_ = 0;
+    size_t total_ = 0;
+    DeviceBuffer<unsigned char> buf_;
 };
 
 }  // namespace chisel_hip

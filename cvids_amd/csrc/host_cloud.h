@@ -144,11 +144,7 @@ extern "C" int chisel_hip_integrate_pointcloud(chisel_hip_map *m, const chisel_h
                        C.ctl + 1, C.pairs_capacity, m->view.error_flag);
     hipLaunchKernelGGL(cloud_bin_kernel<true>, dim3(tiles), dim3(CLOUD_TILE), 0, m->stream, P, C, m->view);
     hipLaunchKernelGGL(cloud_sort_kernel, dim3(CLOUD_GRID), dim3(256), 0, m->stream, P, C);
-    switch (m->N) {
-        case 8: launch_cloud_integrate<8>(m, P, C); break;
-        case 16: launch_cloud_integrate<16>(m, P, C); break;
-        case 32: launch_cloud_integrate<32>(m, P, C); break;
-    }
+    FOR_CHUNK_SIZE(m->N, launch_cloud_integrate<N>(m, P, C));
     HIP_TRY(hipGetLastError());
     HIP_TRY(note_map_mutation(m));
     // the staging buffers (host clouds) and the per-cloud lists are reused by the next cloud: same stream, so no wait here

@@ -27,11 +27,7 @@ void launch_mesh_triangles(chisel_hip_map *m, const MeshParams &P, float *arena,
     volatile int *host_flags = (volatile int *)m->mesh_totals_host.dev();
     const int max_jobs = std::min(MESH_INFO_PREFETCH, B.capacity), seq = m->mesh_seq, part = B.tri_capacity / MESH_PARTS;
     const dim3 grid(4096), block(MESH_TRI_BLOCK);  // persistent: the number of triangles (per partition of the list) is read on the device
-    switch (m->N) {
-        case 8: hipLaunchKernelGGL(mesh_triangle_kernel<8>, grid, block, 0, m->stream, m->view, P, B.jobs, bases, B.tris, B.corners, totals, B.cnt, part, arena, arena_floats, host_info, host_flags, max_jobs, seq, publish); break;
-        case 16: hipLaunchKernelGGL(mesh_triangle_kernel<16>, grid, block, 0, m->stream, m->view, P, B.jobs, bases, B.tris, B.corners, totals, B.cnt, part, arena, arena_floats, host_info, host_flags, max_jobs, seq, publish); break;
-        case 32: hipLaunchKernelGGL(mesh_triangle_kernel<32>, grid, block, 0, m->stream, m->view, P, B.jobs, bases, B.tris, B.corners, totals, B.cnt, part, arena, arena_floats, host_info, host_flags, max_jobs, seq, publish); break;
-    }
+    FOR_CHUNK_SIZE(m->N, hipLaunchKernelGGL(mesh_triangle_kernel<N>, grid, block, 0, m->stream, m->view, P, B.jobs, bases, B.tris, B.corners, totals, B.cnt, part, arena, arena_floats, host_info, host_flags, max_jobs, seq, publish));
 }
 
 int mesh_subjobs(const chisel_hip_map *m) { return m->N == 8 ? MeshGeom<8>::S : (m->N == 16 ? MeshGeom<16>::S : MeshGeom<32>::S); }
@@ -491,11 +487,7 @@ int query_sdf(chisel_hip_map *m, const float pos[3], int with_gradient, double *
     HIP_TRY(hipSetDevice(m->device));
     if (!m->mesh_buf.query) HIP_TRY(alloc_viewed(m->mesh_mem.query, m->mesh_buf.query, 8));
     const MeshParams P = mesh_params(m);
-    switch (m->N) {
-        case 8: hipLaunchKernelGGL(query_sdf_kernel<8>, dim3(1), dim3(1), 0, m->stream, m->view, P, pos[0], pos[1], pos[2], with_gradient, m->mesh_buf.query); break;
-        case 16: hipLaunchKernelGGL(query_sdf_kernel<16>, dim3(1), dim3(1), 0, m->stream, m->view, P, pos[0], pos[1], pos[2], with_gradient, m->mesh_buf.query); break;
-        case 32: hipLaunchKernelGGL(query_sdf_kernel<32>, dim3(1), dim3(1), 0, m->stream, m->view, P, pos[0], pos[1], pos[2], with_gradient, m->mesh_buf.query); break;
-    }
+    FOR_CHUNK_SIZE(m->N, hipLaunchKernelGGL(query_sdf_kernel<N>, dim3(1), dim3(1), 0, m->stream, m->view, P, pos[0], pos[1], pos[2], with_gradient, m->mesh_buf.query));
     double out[5];
     HIP_TRY(hipMemcpyAsync(out, m->mesh_buf.query, sizeof(out), hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));
@@ -657,11 +649,7 @@ int chisel_hip_mesh_cube(chisel_hip_map *m, const int id[3], const int voxel[3],
     if (!m->mesh_buf.cube) HIP_TRY(alloc_viewed(m->mesh_mem.cube, m->mesh_buf.cube, 92));
     const MeshParams P = mesh_params(m);
     float *out = m->mesh_buf.cube;
-    switch (m->N) {
-        case 8: hipLaunchKernelGGL(mesh_one_cube_kernel<8>, dim3(1), dim3(1), 0, m->stream, m->view, P, id[0], id[1], id[2], voxel[0], voxel[1], voxel[2], coords[0], coords[1], coords[2], out); break;
-        case 16: hipLaunchKernelGGL(mesh_one_cube_kernel<16>, dim3(1), dim3(1), 0, m->stream, m->view, P, id[0], id[1], id[2], voxel[0], voxel[1], voxel[2], coords[0], coords[1], coords[2], out); break;
-        case 32: hipLaunchKernelGGL(mesh_one_cube_kernel<32>, dim3(1), dim3(1), 0, m->stream, m->view, P, id[0], id[1], id[2], voxel[0], voxel[1], voxel[2], coords[0], coords[1], coords[2], out); break;
-    }
+    FOR_CHUNK_SIZE(m->N, hipLaunchKernelGGL(mesh_one_cube_kernel<N>, dim3(1), dim3(1), 0, m->stream, m->view, P, id[0], id[1], id[2], voxel[0], voxel[1], voxel[2], coords[0], coords[1], coords[2], out));
     float host[92];
     HIP_TRY(hipMemcpyAsync(host, out, sizeof(host), hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));

@@ -3,7 +3,7 @@
 // Not kernels of the reference.  DESIGN.md "Aligning a frame to the map" is the definition; in short, per pixel i = row W + col with
 // z = depth[i], fp32 in the order written, no FMA:
 //     valid    z finite and near <= z <= far
-//     p        o + z d, with o and d chisel_hip_render_view's ray of the pixel (kernels_render.h)
+//     p        o + z d, with o and d chisel_hip_render_view's ray of the pixel (kernels_render.h: pixel_ray)
 //     ok, d0, g  get_sdf_and_gradient<N>(p), called unchanged (a p with a non-finite component is not looked up: not ok)
 //     rho      d0 + ((g.x e.x + g.y e.y) + g.z e.z),  e = p - c,  c = floorf(p / r) r + r / 2 (the voxel centre the distance is read at)
 //     used     valid and ok and (max_residual <= 0 or |rho| <= max_residual)
@@ -27,8 +27,7 @@ constexpr int ALIGN_ROW = 320;    // doubles per sum in the LDS: 256 values, two
                                   // are read as four 16-byte words: with rows of 80 bytes the 16 lanes of a read hit 16 different slots)
 
 struct AlignCamera {
-    float pose[12];  // camera -> world, row-major 3 x 4
-    float fx, fy, cx, cy;
+    PixelCamera cam;
     float near_plane, far_plane, max_residual;
     int width;
 };
@@ -55,9 +54,9 @@ __global__ __launch_bounds__(256) void align_terms_kernel(MapView M, MeshParams 
     const float z = inside ? depth[i] : __builtin_nanf("");
     const bool valid = __builtin_isfinite(z) && C.near_plane <= z && z <= C.far_plane;
     const int row = i / C.width, col = i - row * C.width;
-    const float xc = ((float)col + 0.5f - C.cx) / C.fx, yc = ((float)row + 0.5f - C.cy) / C.fy;
-    const f3v d = mk3((C.pose[0] * xc + C.pose[1] * yc) + C.pose[2], (C.pose[4] * xc + C.pose[5] * yc) + C.pose[6], (C.pose[8] * xc + C.pose[9] * yc) + C.pose[10]);
-    const f3v p = mk3(C.pose[3] + z * d.x, C.pose[7] + z * d.y, C.pose[11] + z * d.z);
+    f3v o;
+    const f3v d = pixel_ray(C.cam, col, row, o);
+    const f3v p = mk3(o.x + z * d.x, o.y + z * d.y, o.z + z * d.z);
     bool used = false;
     float rho = 0.0f;
     f3v g = mk3(0.0f, 0.0f, 0.0f);

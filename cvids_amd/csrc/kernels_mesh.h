@@ -177,6 +177,22 @@ __device__ inline bool get_sdf_and_gradient(const MapView &M, const MeshParams &
     return true;
 }
 
+// ChunkManager::ComputeNormalsFromGradients' normal at `p` (ChunkManager.cpp:609-626): gradient / |gradient| where GetSDFAndGradient
+// succeeds and |gradient| > 1e-12; false otherwise, `nrm` left as it is (what stands there instead is the caller's)
+template <int N>
+__device__ inline bool gradient_normal(const MapView &M, const MeshParams &P, f3v p, int hx, int hy, int hz, const int *nb, f3v &nrm) {
+    double dist;
+    f3v grad;
+    if (get_sdf_and_gradient<N>(M, P, p, hx, hy, hz, nb, dist, grad)) {
+        const float mag = sqrtf(sum3f(grad.x * grad.x, grad.y * grad.y, grad.z * grad.z));
+        if ((double)mag > 1e-12) {
+            nrm = scl3(grad, 1.0f / mag);
+            return true;
+        }
+    }
+    return false;
+}
+
 // ChunkManager::GetColorVoxel (ChunkManager.cpp:588-607): packed RGBW of the voxel containing `pos`
 template <int N>
 __device__ inline bool get_color_voxel(const MapView &M, const MeshParams &P, f3v pos, int hx, int hy, int hz, const int *nb, uchar4 &out) {
@@ -843,6 +859,7 @@ __global__ __launch_bounds__(MESH_TRI_BLOCK, MESH_TRI_WAVES) void mesh_triangle_
     f3v nrm = fn;
     double dist;
     f3v grad;
+    // (gradient_normal<N>, written out: through the call this kernel compiles to other registers, and its times were taken with these)
     if ((P.stages & 1) && get_sdf_and_gradient<N>(M, P, pv, jx, jy, jz, nb, dist, grad)) {
         const float mag = sqrtf(sum3f(grad.x * grad.x, grad.y * grad.y, grad.z * grad.z));
         if ((double)mag > 1e-12) nrm = scl3(grad, 1.0f / mag);
@@ -985,16 +1002,11 @@ __global__ void shade_vertices_kernel(MapView M, MeshParams P, const float *__re
     if (i >= n) return;
     const f3v pv = mk3(verts[3 * i], verts[3 * i + 1], verts[3 * i + 2]);
     if ((stages & 1) && normals) {
-        double dist;
-        f3v grad;
-        if (get_sdf_and_gradient<N>(M, P, pv, 0, 0, 0, nullptr, dist, grad)) {
-            const float mag = sqrtf(sum3f(grad.x * grad.x, grad.y * grad.y, grad.z * grad.z));
-            if ((double)mag > 1e-12) {
-                const f3v nrm = scl3(grad, 1.0f / mag);
-                normals[3 * i] = nrm.x;
-                normals[3 * i + 1] = nrm.y;
-                normals[3 * i + 2] = nrm.z;
-            }
+        f3v nrm;
+        if (gradient_normal<N>(M, P, pv, 0, 0, 0, nullptr, nrm)) {
+            normals[3 * i] = nrm.x;
+            normals[3 * i + 1] = nrm.y;
+            normals[3 * i + 2] = nrm.z;
         }
     }
     if ((stages & 2) && colors && M.rgbw) {

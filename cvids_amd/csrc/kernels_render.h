@@ -33,9 +33,19 @@ namespace chisel_hip {
 #endif
 constexpr int RENDER_MAX_SAMPLES = 65536;
 
-struct RenderCamera {
+// a pinhole camera at a pose, and the ray of a pixel as the header states it: the one text render_view_kernel and align_terms_kernel share
+struct PixelCamera {
     float pose[12];  // camera -> world, row-major 3 x 4
     float fx, fy, cx, cy;
+};
+__device__ inline f3v pixel_ray(const PixelCamera &C, int col, int row, f3v &o) {
+    const float xc = ((float)col + 0.5f - C.cx) / C.fx, yc = ((float)row + 0.5f - C.cy) / C.fy;
+    o = mk3(C.pose[3], C.pose[7], C.pose[11]);
+    return mk3((C.pose[0] * xc + C.pose[1] * yc) + C.pose[2], (C.pose[4] * xc + C.pose[5] * yc) + C.pose[6], (C.pose[8] * xc + C.pose[9] * yc) + C.pose[10]);
+}
+
+struct RenderCamera {
+    PixelCamera cam;
     float near_plane, step;
     int width, height;
     int n_samples;   // K
@@ -62,108 +72,157 @@ __device__ inline bool render_locate(const MapView &M, const MeshParams &P, f3v 
     return true;
 }
 
+__device__ inline bool finite3(f3v a) { return __builtin_isfinite(a.x) && __builtin_isfinite(a.y) && __builtin_isfinite(a.z); }
+
+// the box of every chunk id ever created (MC_BBOX: a superset of what is resident); every id where the map keeps none
+__device__ inline void load_chunk_box(const MapView &M, int bb[6]) {
+#pragma unroll
+    for (int i = 0; i < 6; i++) bb[i] = i < 3 ? -ID_BIAS : ID_BIAS;
+    if (M.mesh_ctl) {
+#pragma unroll
+        for (int i = 0; i < 6; i++) bb[i] = M.mesh_ctl[MC_BBOX + i];
+    }
+}
+
+// The march for one ray: t_k = t_near + (float)k step (from k, never accumulated), p_k = o + t_k d, the direction as given.  The state
+// of a lane, so that the loop around it is free to hand a lane its ray whenever it likes.
+struct RayMarch {
+    f3v o, d, inv;  // inv: for the estimate of a chunk's far side only (never for a result): 1 / d_i
+    float t_near;
+    int K, k;
+    int cix, ciy, ciz, cslot;  // the chunk this lane was last in (-2: nothing looked up yet)
+    bool prev_obs;
+    float prev_s;
+    int status;   // CHISEL_HIP_RAY_*: 0 no end, 1 hit, 2 ended behind a surface
+    float t_hit;
+};
+
+// a ray of K samples, none taken yet
+__device__ inline void ray_reset(RayMarch &R, f3v o, f3v d, float t_near, int K) {
+    R.o = o;
+    R.d = d;
+    const float big = 3.0e38f;
+    R.inv = mk3(d.x != 0.0f ? __frcp_rn(d.x) : big, d.y != 0.0f ? __frcp_rn(d.y) : big, d.z != 0.0f ? __frcp_rn(d.z) : big);
+    R.t_near = t_near;
+    R.K = K;
+    R.k = 0;
+    R.cix = R.ciy = R.ciz = 0;
+    R.cslot = -2;
+    R.prev_obs = false;
+    R.prev_s = 0.0f;
+    R.status = 0;
+    R.t_hit = 0.0f;
+}
+
+// one sample (or one jump over the samples of an absent chunk); true when the ray has ended or taken all its samples.  The argument
+// of the header for the jump holds for any o, d.  NONFINITE_UNOBSERVED: a sample with a non-finite component is unobserved and no chunk
+// id is taken from it (DESIGN.md "Querying points and rays"; not part of "Rendering a view").
+template <int N, bool NONFINITE_UNOBSERVED>
+__device__ inline bool ray_step(RayMarch &R, const MapView &M, const MeshParams &P, float step, float inv_step, const int *bb) {
+    const int K = R.K;
+    if (R.k >= K) return true;
+    const f3v o = R.o, d = R.d;
+    const float t_near = R.t_near;
+    auto t_of = [&](int k) -> float { return t_near + (float)k * step; };
+    auto p_of = [&](float t) -> f3v { return mk3(o.x + t * d.x, o.y + t * d.y, o.z + t * d.z); };
+    const int k = R.k;
+    const f3v p = p_of(t_of(k));
+    if (NONFINITE_UNOBSERVED && !finite3(p)) {  // (t_k d overflowed: no voxel contains the sample)
+        R.prev_obs = false;
+        R.k = k + 1;
+        return k + 1 >= K;
+    }
+    size_t off;
+    const bool ok = render_locate<N>(M, P, p, R.cix, R.ciy, R.ciz, R.cslot, off);
+    if (R.cslot < 0) {
+        // an absent chunk: this sample is unobserved, and so is every sample up to the last one that has this chunk id
+        R.prev_obs = false;
+        int next = k + 1;
+#if RENDER_SKIP
+        const int cix = R.cix, ciy = R.ciy, ciz = R.ciz;
+        const float big = 3.0e38f, edge = (float)N * P.res;
+        // beyond the box of all chunks on an axis along which the ray moves further out (the coordinate is monotone in k): absent
+        // chunks from here on, the ray never ends
+        if ((cix > bb[3] && d.x >= 0.0f) || (cix < bb[0] && d.x <= 0.0f) || (ciy > bb[4] && d.y >= 0.0f) || (ciy < bb[1] && d.y <= 0.0f) ||
+            (ciz > bb[5] && d.z >= 0.0f) || (ciz < bb[2] && d.z <= 0.0f))
+            next = K;
+        const float tx = d.x > 0.0f ? ((float)(cix + 1) * edge - p.x) * R.inv.x : (d.x < 0.0f ? ((float)cix * edge - p.x) * R.inv.x : big);
+        const float ty = d.y > 0.0f ? ((float)(ciy + 1) * edge - p.y) * R.inv.y : (d.y < 0.0f ? ((float)ciy * edge - p.y) * R.inv.y : big);
+        const float tz = d.z > 0.0f ? ((float)(ciz + 1) * edge - p.z) * R.inv.z : (d.z < 0.0f ? ((float)ciz * edge - p.z) * R.inv.z : big);
+        const float far_side = fminf(fminf(tx, ty), tz) * inv_step - 1.0f;  // samples to the chunk's far side, one held back (an estimate)
+        const int jump = far_side > 1.0f ? (int)fminf(far_side, (float)(K - 1 - k)) : 0;
+        if (next < K && jump > 0) {
+            int jx, jy, jz;
+            id_at(P, p_of(t_of(k + jump)), jx, jy, jz);
+            if (jx == cix && jy == ciy && jz == ciz) next = k + jump + 1;  // samples k .. k + jump share the chunk (monotone in k): exact
+        }
+#endif
+        R.k = next;
+        return next >= K;  // the ray never ends
+    }
+    const float w = M.wgt[off], s = M.sdf[off];
+    const bool obs = ok && (double)w > 1e-12;
+    if (obs && s <= 0.0f) {
+        R.status = 2;
+        if (R.prev_obs && R.prev_s > 0.0f) {
+            R.status = 1;
+            R.t_hit = t_of(k - 1) + step * (R.prev_s / (R.prev_s - s));
+        }
+        return true;
+    }
+    R.prev_obs = obs;
+    R.prev_s = s;
+    R.k = k + 1;
+    return k + 1 >= K;  // the ray never ends
+}
+
+// what a finished ray writes: t_hit, status (where asked for) and, at p* = o + t_hit d, shade_vertices_kernel's normal and colour
+// (NaN without a hit)
+template <int N>
+__device__ inline void ray_write(const RayMarch &R, const MapView &M, const MeshParams &P, long long i, float *__restrict__ t_hit,
+                                 unsigned char *__restrict__ status, float *__restrict__ normals, float *__restrict__ colors) {
+    const float nan = __builtin_nanf("");
+    const bool hit = R.status == 1;
+    t_hit[i] = hit ? R.t_hit : nan;
+    if (status) status[i] = (unsigned char)R.status;
+    f3v nrm = mk3(nan, nan, nan), rgb = mk3(nan, nan, nan);
+    if (hit && (normals || colors)) {
+        const f3v ps = mk3(R.o.x + R.t_hit * R.d.x, R.o.y + R.t_hit * R.d.y, R.o.z + R.t_hit * R.d.z);
+        if (normals) gradient_normal<N>(M, P, ps, 0, 0, 0, nullptr, nrm);
+        if (colors) rgb = interpolate_color<N>(M, P, ps, 0, 0, 0, nullptr);
+    }
+    if (normals) {
+        normals[3 * i] = nrm.x;
+        normals[3 * i + 1] = nrm.y;
+        normals[3 * i + 2] = nrm.z;
+    }
+    if (colors) {
+        colors[3 * i] = rgb.x;
+        colors[3 * i + 1] = rgb.y;
+        colors[3 * i + 2] = rgb.z;
+    }
+}
+
+// One pixel per lane in the tiles of the header: the pixel's ray, then the march and the shading every ray gets.  z is the march's t.
 template <int N>
 __global__ __launch_bounds__(256) void render_view_kernel(MapView M, MeshParams P, RenderCamera C, float *__restrict__ depth, float *__restrict__ normals,
                                                           float *__restrict__ colors) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int col = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7), row = (int)blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
     const bool inside = col < C.width && row < C.height;
-    const float xc = ((float)col + 0.5f - C.cx) / C.fx, yc = ((float)row + 0.5f - C.cy) / C.fy;
-    const f3v d = mk3((C.pose[0] * xc + C.pose[1] * yc) + C.pose[2], (C.pose[4] * xc + C.pose[5] * yc) + C.pose[6], (C.pose[8] * xc + C.pose[9] * yc) + C.pose[10]);
-    const f3v o = mk3(C.pose[3], C.pose[7], C.pose[11]);
-    const int K = C.n_samples;
-    const float step = C.step, near_plane = C.near_plane;
-    auto z_of = [&](int k) -> float { return near_plane + (float)k * step; };
-    auto p_of = [&](float z) -> f3v { return mk3(o.x + z * d.x, o.y + z * d.y, o.z + z * d.z); };
-    // for the estimate of a chunk's far side only (never for a result): 1 / d_i, the chunk's edge
-    const float big = 3.0e38f;
-    const f3v inv = mk3(d.x != 0.0f ? __frcp_rn(d.x) : big, d.y != 0.0f ? __frcp_rn(d.y) : big, d.z != 0.0f ? __frcp_rn(d.z) : big);
-    const float edge = (float)N * P.res, inv_step = __frcp_rn(step);
-
-    // the box of every chunk id ever created (MC_BBOX: a superset of what is resident); every id where the map keeps none
-    int bb[6] = {-ID_BIAS, -ID_BIAS, -ID_BIAS, ID_BIAS, ID_BIAS, ID_BIAS};
-    if (M.mesh_ctl) {
-#pragma unroll
-        for (int i = 0; i < 6; i++) bb[i] = M.mesh_ctl[MC_BBOX + i];
-    }
-
-    bool done = !inside, hit = false;
-    bool prev_obs = false;
-    float prev_s = 0.0f, z_hit = 0.0f;
-    int k = 0;
-    int cix = 0, ciy = 0, ciz = 0, cslot = -2;  // -2: nothing looked up yet
+    f3v o;
+    const f3v d = pixel_ray(C.cam, col, row, o);
+    int bb[6];
+    load_chunk_box(M, bb);
+    const float step = C.step, inv_step = __frcp_rn(step);
+    RayMarch R;
+    ray_reset(R, o, d, C.near_plane, C.n_samples);
+    bool done = !inside;
     while (__any(!done)) {
         if (done) continue;
-        const f3v p = p_of(z_of(k));
-        size_t off;
-        const bool ok = render_locate<N>(M, P, p, cix, ciy, ciz, cslot, off);
-        if (cslot < 0) {
-            // an absent chunk: this sample is unobserved, and so is every sample up to the last one that has this chunk id
-            prev_obs = false;
-            int next = k + 1;
-#if RENDER_SKIP
-            // beyond the box of all chunks on an axis along which the ray moves further out (the coordinate is monotone in k): absent
-            // chunks from here on, the ray never ends
-            if ((cix > bb[3] && d.x >= 0.0f) || (cix < bb[0] && d.x <= 0.0f) || (ciy > bb[4] && d.y >= 0.0f) || (ciy < bb[1] && d.y <= 0.0f) ||
-                (ciz > bb[5] && d.z >= 0.0f) || (ciz < bb[2] && d.z <= 0.0f))
-                next = K;
-            const float tx = d.x > 0.0f ? ((float)(cix + 1) * edge - p.x) * inv.x : (d.x < 0.0f ? ((float)cix * edge - p.x) * inv.x : big);
-            const float ty = d.y > 0.0f ? ((float)(ciy + 1) * edge - p.y) * inv.y : (d.y < 0.0f ? ((float)ciy * edge - p.y) * inv.y : big);
-            const float tz = d.z > 0.0f ? ((float)(ciz + 1) * edge - p.z) * inv.z : (d.z < 0.0f ? ((float)ciz * edge - p.z) * inv.z : big);
-            const float far_side = fminf(fminf(tx, ty), tz) * inv_step - 1.0f;  // samples to the chunk's far side, one held back
-            const int jump = far_side > 1.0f ? (int)fminf(far_side, (float)(K - 1 - k)) : 0;
-            if (next < K && jump > 0) {
-                int jx, jy, jz;
-                id_at(P, p_of(z_of(k + jump)), jx, jy, jz);
-                if (jx == cix && jy == ciy && jz == ciz) next = k + jump + 1;  // samples k .. k + jump share the chunk (monotone in k)
-            }
-#endif
-            k = next;
-            done = k >= K;  // the ray never ends
-            continue;
-        }
-        const float w = M.wgt[off], s = M.sdf[off];
-        const bool obs = ok && (double)w > 1e-12;
-        if (obs && s <= 0.0f) {
-            done = true;
-            if (prev_obs && prev_s > 0.0f) {
-                hit = true;
-                z_hit = z_of(k - 1) + step * (prev_s / (prev_s - s));
-            }
-            continue;
-        }
-        prev_obs = obs;
-        prev_s = s;
-        k++;
-        done = k >= K;  // the ray never ends
+        done = ray_step<N, false>(R, M, P, step, inv_step, bb);
     }
-    if (!inside) return;
-    const float nan = __builtin_nanf("");
-    const size_t px = (size_t)row * C.width + col;
-    depth[px] = hit ? z_hit : nan;
-    f3v nrm = mk3(nan, nan, nan), rgb = mk3(nan, nan, nan);
-    if (hit && (normals || colors)) {
-        const f3v ps = p_of(z_hit);
-        if (normals) {  // shade_vertices_kernel's normal for p*
-            double dist;
-            f3v grad;
-            if (get_sdf_and_gradient<N>(M, P, ps, 0, 0, 0, nullptr, dist, grad)) {
-                const float mag = sqrtf(sum3f(grad.x * grad.x, grad.y * grad.y, grad.z * grad.z));
-                if ((double)mag > 1e-12) nrm = scl3(grad, 1.0f / mag);
-            }
-        }
-        if (colors) rgb = interpolate_color<N>(M, P, ps, 0, 0, 0, nullptr);
-    }
-    if (normals) {
-        normals[3 * px] = nrm.x;
-        normals[3 * px + 1] = nrm.y;
-        normals[3 * px + 2] = nrm.z;
-    }
-    if (colors) {
-        colors[3 * px] = rgb.x;
-        colors[3 * px + 1] = rgb.y;
-        colors[3 * px + 2] = rgb.z;
-    }
+    if (inside) ray_write<N>(R, M, P, (long long)row * C.width + col, depth, nullptr, normals, colors);
 }
 
 }  // namespace chisel_hip
