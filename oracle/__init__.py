@@ -72,6 +72,9 @@ def lib(variant=None):
     L.oc_has_chunk.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.oc_get_chunk.argtypes = [vp, C.c_int, C.c_int, C.c_int, f32p, f32p, u8p]
     L.oc_remove_chunk.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.oc_put_chunk.argtypes = [vp, C.c_int, C.c_int, C.c_int, f32p, f32p, u8p]
+    L.oc_recompute_meshes.argtypes = [vp, i32p, C.c_int]
+    L.oc_query_points.argtypes = [vp, f32p, C.c_int, u8p, C.POINTER(C.c_double), f32p]
     L.oc_num_meshes_to_update.argtypes = [vp]
     L.oc_list_meshes_to_update.argtypes = [vp, i32p]
     L.oc_update_meshes.argtypes = [vp, C.c_int]
@@ -215,6 +218,18 @@ class OracleMap:
             return None
         return sdf, w, (rgbw if self.use_color else None)
 
+    def put_chunk(self, cid, sdf, weight, rgbw=None):
+        """ChunkManager::AddChunk (ChunkManager.h:89-92) with the caller's voxels: sdf, weight (V,), rgbw (V, 4) or None.  Like the
+        reference it leaves meshes_to_update() alone."""
+        s, sp = _f32(np.asarray(sdf).reshape(-1))
+        w, wp = _f32(np.asarray(weight).reshape(-1))
+        assert s.size == self.V and w.size == self.V
+        cp = None
+        if rgbw is not None and self.use_color:
+            c, cp = _u8(np.asarray(rgbw).reshape(-1))
+            assert c.size == 4 * self.V
+        self.L.oc_put_chunk(self.h, int(cid[0]), int(cid[1]), int(cid[2]), sp, wp, cp)
+
     def remove_chunk(self, cid):
         return bool(self.L.oc_remove_chunk(self.h, int(cid[0]), int(cid[1]), int(cid[2])))
 
@@ -227,6 +242,11 @@ class OracleMap:
 
     def update_meshes(self, force=True):
         self.L.oc_update_meshes(self.h, int(force))
+
+    def recompute_meshes(self, ids):
+        """ChunkManager::RecomputeMeshes (ChunkManager.cpp:130-169) over exactly these ids (n, 3); meshes_to_update() stays as it is"""
+        ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1, 3))
+        self.L.oc_recompute_meshes(self.h, ids.ctypes.data_as(C.POINTER(C.c_int)), len(ids))
 
     def mesh_ids(self):
         n = self.L.oc_num_meshes(self.h)
@@ -261,6 +281,18 @@ class OracleMap:
         ok = self.L.oc_get_sdf_and_gradient(self.h, float(pos[0]), float(pos[1]), float(pos[2]), C.byref(d),
                                             g.ctypes.data_as(C.POINTER(C.c_float)))
         return (bool(ok), d.value, g)
+
+    def query_points(self, positions, gradient=True):
+        """get_sdf / get_sdf_and_gradient at n positions in one call -> (found (n,) uint8: bit 0 GetSDF, bit 1 GetSDFAndGradient;
+        sdf (n,) float64; gradient (n, 3) float32 or None), NaN where the bit is not set"""
+        p, pp = _f32(np.asarray(positions).reshape(-1, 3))
+        n = len(p)
+        found = np.zeros(n, np.uint8)
+        sdf = np.full(n, np.nan, np.float64)
+        grad = np.full((n, 3), np.nan, np.float32) if gradient else None
+        self.L.oc_query_points(self.h, pp, n, found.ctypes.data_as(C.POINTER(C.c_uint8)), sdf.ctypes.data_as(C.POINTER(C.c_double)),
+                               grad.ctypes.data_as(C.POINTER(C.c_float)) if gradient else None)
+        return found, sdf, grad
 
     def candidates(self, pose, intr, W, H, near=0.05, far=5.0, max_ids=4_000_000):
         p, pp = _f32(np.asarray(pose)[:3, :4])

@@ -1432,6 +1432,24 @@ int oc_get_chunk(const oc_map *m, int x, int y, int z, float *sdf, float *weight
     return 1;
 }
 int oc_remove_chunk(oc_map *m, int x, int y, int z) { return m->chunks.erase(I3(x, y, z)) ? 1 : 0; }
+// ChunkManager::AddChunk (ChunkManager.h:89-92) with the caller's voxels: the chunk is created (Chunk.cpp:33-63) unless the id is
+// resident already -- insert() keeps the resident one --, then every voxel is overwritten.  Chisel's meshesToUpdate is not
+// touched: AddChunk belongs to the ChunkManager, which does not know the set (Chisel.h:227).
+void oc_put_chunk(oc_map *m, int x, int y, int z, const float *sdf, const float *weight, const uint8_t *rgbw) {
+    Chunk &c = *m->CreateChunk(I3(x, y, z))->second;
+    size_t n = c.voxels.size();
+    for (size_t i = 0; i < n; i++) {
+        c.voxels[i].sdf = sdf[i];
+        c.voxels[i].weight = weight[i];
+    }
+    for (size_t i = 0; i < c.colors.size(); i++) {
+        ColorVoxel v;  // (no colours given: ColorVoxel's defaults, ColorVoxel.cpp:27-31)
+        if (rgbw) {
+            v.red = rgbw[4 * i + 0]; v.green = rgbw[4 * i + 1]; v.blue = rgbw[4 * i + 2]; v.weight = rgbw[4 * i + 3];
+        }
+        c.colors[i] = v;
+    }
+}
 
 int oc_num_meshes_to_update(const oc_map *m) { return (int)m->meshesToUpdate.size(); }
 void oc_list_meshes_to_update(const oc_map *m, int *ids) {
@@ -1441,6 +1459,13 @@ void oc_list_meshes_to_update(const oc_map *m, int *ids) {
     }
 }
 void oc_update_meshes(oc_map *m, int force) { m->UpdateMeshes(force != 0); }
+// ChunkManager::RecomputeMeshes (ChunkManager.cpp:130-169) over exactly the listed ids, as a caller that holds a ChunkSet of its own
+// would call it; Chisel::UpdateMeshes (Chisel.cpp:50-59) is not involved, so meshesToUpdate stays as it is.
+void oc_recompute_meshes(oc_map *m, const int *ids_xyz, int n) {
+    ChunkSet listed;
+    for (int i = 0; i < n; i++) listed[I3(ids_xyz[3 * i], ids_xyz[3 * i + 1], ids_xyz[3 * i + 2])] = true;
+    m->RecomputeMeshes(listed);
+}
 int oc_num_meshes(const oc_map *m) { return (int)m->allMeshes.size(); }
 void oc_list_meshes(const oc_map *m, int *ids) {
     int i = 0;
@@ -1475,6 +1500,29 @@ int oc_get_sdf_and_gradient(const oc_map *m, float x, float y, float z, double *
     bool ok = m->GetSDFAndGradient(V3(x, y, z), dist, &grad);
     if (ok) { g[0] = grad.x; g[1] = grad.y; g[2] = grad.z; }
     return ok ? 1 : 0;
+}
+
+// ChunkManager::GetSDF (ChunkManager.cpp:476-499) and GetSDFAndGradient (:449-474) at n positions, one call each per position.
+// found[i]: bit 0 GetSDF true, bit 1 GetSDFAndGradient true; sdf (n doubles) and grad (3 n floats) are written where the bit is set,
+// either may be NULL.
+void oc_query_points(const oc_map *m, const float *pos_xyz, int n, uint8_t *found, double *sdf, float *grad) {
+    for (int i = 0; i < n; i++) {
+        V3 p(pos_xyz[3 * i], pos_xyz[3 * i + 1], pos_xyz[3 * i + 2]);
+        double d = 0.0;
+        uint8_t f = 0;
+        if (m->GetSDF(p, &d)) {
+            f |= 1;
+            if (sdf) sdf[i] = d;
+        }
+        if (grad) {
+            V3 g;
+            if (m->GetSDFAndGradient(p, &d, &g)) {
+                f |= 2;
+                grad[3 * i] = g.x; grad[3 * i + 1] = g.y; grad[3 * i + 2] = g.z;
+            }
+        }
+        found[i] = f;
+    }
 }
 
 float oc_truncation(int kind, float param, float depth) { return Truncator(kind, param).GetTruncationDistance(depth); }

@@ -84,11 +84,16 @@ int oc_has_chunk(const oc_map *m, int x, int y, int z);
 /* returns 0 when absent; arrays are N^3 long, rgbw may be NULL */
 int oc_get_chunk(const oc_map *m, int x, int y, int z, float *sdf, float *weight, uint8_t *rgbw);
 int oc_remove_chunk(oc_map *m, int x, int y, int z);
+/* ChunkManager::AddChunk (ChunkManager.h:89-92) with the caller's voxels: create or find the chunk, overwrite all N^3 voxels
+ * (rgbw NULL: default colour voxels).  meshesToUpdate is not touched. */
+void oc_put_chunk(oc_map *m, int x, int y, int z, const float *sdf, const float *weight, const uint8_t *rgbw);
 
 int oc_num_meshes_to_update(const oc_map *m);
 void oc_list_meshes_to_update(const oc_map *m, int *ids_xyz);
 /* Chisel::UpdateMeshes: recompute on every 10th call unless force != 0 */
 void oc_update_meshes(oc_map *m, int force);
+/* ChunkManager::RecomputeMeshes over exactly these ids (absent ones are passed over); meshesToUpdate stays as it is */
+void oc_recompute_meshes(oc_map *m, const int *ids_xyz, int n);
 int oc_num_meshes(const oc_map *m);
 void oc_list_meshes(const oc_map *m, int *ids_xyz);
 int oc_mesh_size(const oc_map *m, int x, int y, int z, int *n_vertices, int *n_grids);
@@ -97,6 +102,9 @@ int oc_get_mesh(const oc_map *m, int x, int y, int z, float *vertices, float *no
 int oc_save_ply(const oc_map *m, const char *path);
 int oc_get_sdf(const oc_map *m, float x, float y, float z, double *dist);
 int oc_get_sdf_and_gradient(const oc_map *m, float x, float y, float z, double *dist, float *grad3);
+/* the two above at n positions: found[i] bit 0 GetSDF, bit 1 GetSDFAndGradient (only with grad); sdf / grad (NULL = not wanted)
+ * are written where the bit is set */
+void oc_query_points(const oc_map *m, const float *pos_xyz, int n, uint8_t *found, double *sdf, float *grad3);
 
 /* ---- scalar known-answer entry points ---- */
 float oc_truncation(int kind, float param, float depth);

@@ -30,7 +30,11 @@ def compare_fields(ref, got, V, use_color, atol=0.0, what=""):
         if gs is None:
             gs, gw = np.full(V, DEFAULT_SDF), np.zeros(V, np.float32)
             gc = np.zeros((V, 4), np.uint8)
-        # NaN-aware comparison (the reference can produce NaN/inf, e.g. depth 0 with the inverse truncator)
+        # NaN-aware comparison, for voxels that did not come from depth images (AddChunk / put_chunk take whatever the caller holds).
+        # ProjectionIntegrator.h:51-99 itself cannot store a NaN: a NaN depth fails `depth > 50`, both band tests and the carving test
+        # (:74-88), depth 0 with the inverse truncator gives truncation 1 / (inf * inf) = 0, not NaN (InverseTruncator.h:42-46), and
+        # DistVoxel::Integrate only averages finite updates from weight 0 on.  An infinite distance is possible (a huge negative depth
+        # under an infinite truncation sums to -inf).
         same_nan_s = np.isnan(rs) == np.isnan(gs)
         same_nan_w = np.isnan(rw) == np.isnan(gw)
         assert same_nan_s.all() and same_nan_w.all(), "%s chunk %s: NaN pattern differs" % (what, cid)
@@ -51,11 +55,15 @@ def compare_fields(ref, got, V, use_color, atol=0.0, what=""):
 
 
 def triangle_multiset(vertices, decimals=5):
-    """mesh -> sorted array of triangles, each triangle's 3 vertices rotated to a canonical start."""
+    """mesh -> its triangles as a multiset, in a form that compares equal exactly when the multisets do: every triangle's 3 vertices
+    (rounded) rotated to a canonical start -- the lexicographically smallest vertex, the first of them where two are equal --, the
+    triangles sorted (by their bytes: any total order serves) and packed into one bytes object."""
     v = np.asarray(vertices, np.float64).reshape(-1, 3, 3).round(decimals) + 0.0
-    out = []
-    for tri in v:
-        keys = [tuple(p) for p in tri]
-        k = keys.index(min(keys))
-        out.append(tuple(keys[k:] + keys[:k]))
-    return sorted(out)
+    rows = np.arange(len(v))
+    k = np.zeros(len(v), np.int64)
+    for j in (1, 2):
+        a, b = v[:, j], v[rows, k]
+        less = (a[:, 0] < b[:, 0]) | ((a[:, 0] == b[:, 0]) & ((a[:, 1] < b[:, 1]) | ((a[:, 1] == b[:, 1]) & (a[:, 2] < b[:, 2]))))
+        k = np.where(less, j, k)
+    tri = np.ascontiguousarray(v[rows[:, None], (k[:, None] + np.arange(3)) % 3].reshape(-1, 9))
+    return np.sort(tri.view(np.dtype((np.void, 72))).ravel()).tobytes()
