@@ -618,6 +618,17 @@ class Chisel:
                 "xi_last": np.array(r.xi_last, np.float64), "terms_first": np.array(r.terms_first, np.float64),
                 "terms_last": np.array(r.terms_last, np.float64)}
 
+    def MergeMap(self, other, src_to_dst, stats=True):
+        """chisel_hip_merge_map: `other`, moved by the rigid transform src_to_dst (3 x 4 or 4 x 4), is fused into this map on the
+        device; `other` is only read.  -> {"src_chunks", "dst_chunks_created", "dst_chunks_updated", "voxels_updated"}; stats=False:
+        the call does not wait for its own end and returns None"""
+        if not stats:
+            check(self.L.chisel_hip_merge_map(self.h, other.h, _pose12(src_to_dst), None))
+            return None
+        st = capi.MergeStats()
+        check(self.L.chisel_hip_merge_map(self.h, other.h, _pose12(src_to_dst), C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in capi.MergeStats._fields_}
+
     def MemoryStatistics(self):
         """ChunkManager::PrintMemoryStatistics (ChunkManager.cpp:641-678) as numbers: the voxel census of Chunk::ComputeStatistics over
         the resident chunks, the weight sum, the bounds of the chunk boxes and the two memory figures the reference prints (it

@@ -39,6 +39,7 @@
 #include "kernels_query.h"
 #include "kernels_align.h"
 #include "kernels_cloud.h"
+#include "kernels_merge.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
 #include "kernels_stereo_prep.h"
@@ -384,6 +385,13 @@ struct chisel_hip_map {
         CloudView view{};                                              // (what follows: what it points at)
         DeviceBuffer<CloudRay> rays; DeviceBuffer<unsigned> rgb; DeviceBuffer<int> tile_prefix, table_vals, pairs, sorted; DeviceBuffer<uint64_t> listed;
     } cloud;
+    struct MergeMemory {                                               // chisel_hip_merge_map with this map as the destination (host_merge.h), allocated on first use
+        DeviceBuffer<unsigned long long> table, list, stats;           // key table of the candidate ids | the unique ids | the merge's results
+        DeviceBuffer<int> slots, ctl;
+        PinnedBuffer<int> host;                                        // [16] where the control words and the results reach the host
+        MergeView view{};                                              // (what the kernels take: copies of the pointers above)
+        int64_t chunks_hint = 0;                                       // chunks of the latest source (sizes the table of the next merge)
+    } merge_mem;
     // profiling
     bool profiling = false;
     std::vector<ProfEvent> prof_live;
@@ -2965,4 +2973,5 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 #include "host_render.h"
 #include "host_query.h"
 #include "host_align.h"
+#include "host_merge.h"
 #include "host_selftest.h"

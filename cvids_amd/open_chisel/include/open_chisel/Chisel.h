@@ -865,6 +865,17 @@ class Chisel {  // Chisel.h:38-230
             return meshesToUpdate;
         }
     }
+    // Not in the reference: `other`, moved by the rigid transform srcToDst, fused into this map on the device (chisel_hip_merge_map) --
+    // an agent's map joined to the common one after an inter-agent loop closure has moved its trajectory.  `other` is only read.
+    // Returns with every voxel update visible; throws as the other calls do (maps of different chunk size or resolution, a transform
+    // that is not rigid, a fixed pool without room for the new chunks).
+    chisel_hip_merge_stats MergeMap(const Chisel &other, const Transform &srcToDst) {
+        float pose[12];
+        Pose12(srcToDst, pose);
+        chisel_hip_merge_stats stats;
+        hip_check(chisel_hip_merge_map(map, other.map, pose, &stats));
+        return stats;
+    }
     chisel_hip_map *HipMap() const { return map; }
 
   protected:

@@ -46,7 +46,7 @@ extern "C" {
  *      (chisel_hip_shell_plan_queue, _import_shells_fixed, _shell_commit), the stereo matcher (chisel_hip_stereo_*)
  *   3  chisel_hip_export_chunks, _import_ghost_chunks, _export_shells, _import_ghost_shells removed; later additions within 3 (nothing
  *      removed or re-typed): chisel_hip_render_view, chisel_hip_query_points, chisel_hip_cast_rays, chisel_hip_align_terms,
- *      chisel_hip_align_solve, chisel_hip_align_depth */
+ *      chisel_hip_align_solve, chisel_hip_align_depth, chisel_hip_merge_map (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
 #define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -622,6 +622,28 @@ typedef struct {
  * return.  Error codes as chisel_hip_align_terms; also CHISEL_HIP_ERR_INVALID for null params or result or max_iterations < 1. */
 int chisel_hip_align_depth(chisel_hip_map *map, const chisel_hip_depth_frame *frame, const chisel_hip_align_params *params,
                            chisel_hip_align_result *result);
+/* Not in the reference: the map `src`, moved by the rigid transform src_to_dst (row-major 3 x 4, as every pose here), fused into `dst` --
+ * what a pose-graph server needs when an inter-agent loop closure moves a whole agent's trajectory and the frames that built its map
+ * are gone (ServerKeyFrame::FreeSpace); also a map dump brought into a live map at an offset, and the shards of a map collected into
+ * one.  DESIGN.md "Merging maps" has the definition to the bit; in short, with M the inverse of src_to_dst taken as rigid (R^T, -R^T t,
+ * formed in double, rounded to fp32): every voxel of `dst` whose centre c (ChunkManager.cpp:50-66) has an observed source voxel
+ * ChunkManager::GetSDF(M c) (nearest voxel, weight > 1e-12) takes DistVoxel::Integrate(source distance, source weight) and, when both
+ * maps hold colour and the source voxel's colour weight is > 0, ColorVoxel::Integrate(source colour, source colour weight).  Afterwards
+ * `dst` holds a chunk iff it held it before or one of its voxels was updated (the rule of Chisel::IntegrateDepthScan, Chisel.h:59-213),
+ * and every updated chunk is left as an integration leaves it: in meshesToUpdate with its 27-neighbourhood, counted in
+ * CHISEL_HIP_CNT_SDF / _COL / _NEW_CHUNKS / _UPDATED_CHUNKS.  `src` is only read.
+ * The work runs on dst's stream, behind everything queued on src's stream so far; what src is given next starts behind it: no
+ * synchronisation by the caller before or after.  The host waits once, for the number of chunks `dst` may have to create.  stats may be
+ * NULL; otherwise the call also waits for its own end and reports src_chunks = resident chunks of `src`, dst_chunks_created = chunks
+ * `dst` did not hold before, dst_chunks_updated = chunks with at least one updated voxel (old or new), voxels_updated.
+ * Refused with neither map touched: CHISEL_HIP_ERR_INVALID for a null argument, dst == src, maps on different devices, of different
+ * chunk size or voxel resolution, an entry of src_to_dst that is not finite, a rotation part with max |R^T R - I| > 1e-4;
+ * CHISEL_HIP_ERR_UNSUPPORTED for a group or one shard of several; CHISEL_HIP_ERR_POOL_FULL when a fixed pool (max_chunks > 0) cannot take
+ * the chunks the merge may create -- decided before the first one is created (a growing pool grows). */
+typedef struct {
+    int64_t src_chunks, dst_chunks_created, dst_chunks_updated, voxels_updated;
+} chisel_hip_merge_stats;   /* 32 bytes */
+int chisel_hip_merge_map(chisel_hip_map *dst, chisel_hip_map *src, const float src_to_dst[12], chisel_hip_merge_stats *stats);
 /* ProjectionIntegrator::Integrate<DataType>(depthImage, camera, cameraPose, chunk) / IntegrateColor (ProjectionIntegrator.h:51-52,
  * :101-102): ONE frame into ONE resident chunk -- whether or not the frustum's id range holds it, as the reference's per-chunk call
  * knows nothing of frusta --; color may be NULL (the depth-only update rule).  *updated = the call's return value there ("some voxel
