@@ -629,6 +629,43 @@ class Chisel:
         check(self.L.chisel_hip_merge_map(self.h, other.h, _pose12(src_to_dst), C.byref(st)))
         return {n: int(getattr(st, n)) for n, _ in capi.MergeStats._fields_}
 
+    def DeintegrateDepthScan(self, integrator, depth_image, extrinsic, camera, color_rules=False, stats=True, collect=False):
+        """chisel_hip_deintegrate_depth: the depth frame (numpy, or a torch CUDA tensor used in place) that was integrated at `extrinsic`
+        with `integrator` is taken out of the distance voxels again; color_rules: it went in through IntegrateDepthScanColor.  ->
+        {"chunks_tested", "chunks_touched", "chunks_emptied", "voxels_updated", "voxels_cleared", "voxels_skipped", "emptied_ids": (k, 3)
+        int32, the chunks left without any weight}; collect=True hands those to GarbageCollect.  stats=False: the call does not wait
+        for its own end and returns None"""
+        self._use(integrator)
+        f, keep = depth_frame(depth_image, extrinsic, camera)
+        if not stats:
+            assert not collect, "collect=True needs the ids, which stats=False does not wait for"
+            check(self.L.chisel_hip_deintegrate_depth(self.h, C.byref(f), int(bool(color_rules)), None, None, 0))
+            self._keep = [keep]
+            return None
+        st = capi.DeintegrateStats()
+        ids = np.zeros((max(1, self.NumChunks()), 3), np.int32)  # (no chunk is created: the resident ones bound the emptied ones)
+        check(self.L.chisel_hip_deintegrate_depth(self.h, C.byref(f), int(bool(color_rules)), C.byref(st), ids.ctypes.data_as(C.POINTER(C.c_int)), len(ids)))
+        out = {n: int(getattr(st, n)) for n, _ in capi.DeintegrateStats._fields_}
+        out["emptied_ids"] = ids[:min(out["chunks_emptied"], len(ids))].copy()
+        if collect and len(out["emptied_ids"]):
+            self.GarbageCollect(out["emptied_ids"])
+        return out
+
+    def ReintegrateDepthScan(self, integrator, depth_image, old_extrinsic, new_extrinsic, camera, color_image=None, color_camera=None,
+                             stats=True, collect=False):
+        """a keyframe whose pose was corrected after it was fused: DeintegrateDepthScan at the pose it went in with, then the same
+        integration at the corrected one.  Without color_image the frame went in through IntegrateDepthScan and goes back that way
+        (the depth rules); with it, through IntegrateDepthScanColor (the colour rules), the colour camera (default: `camera`)
+        riding on the depth camera's pose -- the distance voxels follow the correction, the colour voxels only gain the second
+        look.  -> what DeintegrateDepthScan returns"""
+        colour = color_image is not None
+        out = self.DeintegrateDepthScan(integrator, depth_image, old_extrinsic, camera, colour, stats, collect)
+        if colour:
+            self.IntegrateDepthScanColor(integrator, depth_image, new_extrinsic, camera, color_image, new_extrinsic, color_camera or camera)
+        else:
+            self.IntegrateDepthScan(integrator, depth_image, new_extrinsic, camera)
+        return out
+
     def MemoryStatistics(self):
         """ChunkManager::PrintMemoryStatistics (ChunkManager.cpp:641-678) as numbers: the voxel census of Chunk::ComputeStatistics over
         the resident chunks, the weight sum, the bounds of the chunk boxes and the two memory figures the reference prints (it

@@ -40,6 +40,7 @@
 #include "kernels_align.h"
 #include "kernels_cloud.h"
 #include "kernels_merge.h"
+#include "kernels_deintegrate.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
 #include "kernels_stereo_prep.h"
@@ -392,6 +393,13 @@ struct chisel_hip_map {
         MergeView view{};                                              // (what the kernels take: copies of the pointers above)
         int64_t chunks_hint = 0;                                       // chunks of the latest source (sizes the table of the next merge)
     } merge_mem;
+    struct DeintegrateMemory {                                         // chisel_hip_deintegrate_depth (host_deintegrate.h), allocated on first use
+        DeviceBuffer<int> list, ids;                                   // the listed slots | the ids of the emptied chunks
+        DeviceBuffer<unsigned long long> stats;
+        PinnedBuffer<unsigned long long> host;                         // [DS_WORDS] where the stats reach the host
+        DeintegrateView view{};                                        // (what the kernels take: copies of the pointers above)
+        int list_capacity = 0, ids_capacity = 0;
+    } deintegrate_mem;
     // profiling
     bool profiling = false;
     std::vector<ProfEvent> prof_live;
@@ -2974,4 +2982,5 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 #include "host_query.h"
 #include "host_align.h"
 #include "host_merge.h"
+#include "host_deintegrate.h"
 #include "host_selftest.h"

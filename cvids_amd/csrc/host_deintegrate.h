@@ -1,0 +1,106 @@
+// host_deintegrate.h -- chisel_hip_deintegrate_depth (included by chisel_hip.hip; the kernels and the definition: kernels_deintegrate.h,
+// DESIGN.md 3.10).  Everything runs on the map's stream: the list kernel, then the apply kernel, whose fixed grid reads the list's length
+// from the device -- no host wait between them, and none at all when the caller asks for neither stats nor ids.  The scratch lives in the
+// map (chisel_hip_map::deintegrate_mem), is reused by the next call and freed with the map; a host image goes through the staging
+// buffer of the alignment entries (align::stage_depth).
+#pragma once
+
+namespace {
+namespace deintegrate {
+
+// room for one entry per committed slot, the stats and `max_ids` ids
+int ensure_scratch(chisel_hip_map *m, int max_ids) {
+    chisel_hip_map::DeintegrateMemory &O = m->deintegrate_mem;
+    if (!O.host) {
+        HIP_TRY(O.host.alloc(DS_WORDS));
+        HIP_TRY(alloc_viewed(O.stats, O.view.stats, (size_t)DS_WORDS));
+    }
+    if (O.list_capacity < std::max(m->view.committed, 1)) {
+        HIP_TRY(hipStreamSynchronize(m->stream));  // (a launch chain before this one may still read the list)
+        O.list_capacity = 0;
+        HIP_TRY(alloc_viewed(O.list, O.view.list, (size_t)std::max(m->view.committed, 1)));
+        O.list_capacity = std::max(m->view.committed, 1);
+    }
+    if (O.ids_capacity < max_ids) {
+        HIP_TRY(hipStreamSynchronize(m->stream));
+        O.ids_capacity = 0;
+        HIP_TRY(O.ids.alloc((size_t)3 * max_ids));
+        O.ids_capacity = max_ids;
+    }
+    return CHISEL_HIP_OK;
+}
+
+}  // namespace deintegrate
+}  // namespace
+
+extern "C" int chisel_hip_deintegrate_depth(chisel_hip_map *m, const chisel_hip_depth_frame *frame, int color_rules, chisel_hip_deintegrate_stats *stats,
+                                            int *emptied_ids_xyz, int max_ids) {
+    static_assert(sizeof(chisel_hip_deintegrate_stats) == 48, "chisel_hip_deintegrate_stats is six 64-bit counts");
+    static_assert(sizeof(chisel_hip_deintegrate_stats) <= DS_WORDS * sizeof(unsigned long long), "the stats travel in the report words");
+    const char *name = "chisel_hip_deintegrate_depth";
+    // ---- refusals: nothing is touched by a refused call
+    if (m && m->is_group) return fail(CHISEL_HIP_ERR_UNSUPPORTED, std::string(name) + " rewrites the voxels of all owners: a group's shards hold a part each, and ghost chunks would need a rule of their own");
+    if (!m || !frame || !frame->depth) return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": null map, frame or depth image");
+    if (m->cfg.n_shards > 1) return fail(CHISEL_HIP_ERR_UNSUPPORTED, std::string(name) + " rewrites the voxels of all owners: this map is one shard of several");
+    if (const char *why = deintegrate_refusal(frame->depth, frame->width, frame->height, frame->pose, frame->fx, frame->fy, frame->cx, frame->cy,
+                                              stats != nullptr, emptied_ids_xyz != nullptr, max_ids))
+        return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": " + why);
+    SETTLE(m);
+    HIP_TRY(hipSetDevice(m->device));
+    int rc = check_mesh_totals(m);  // a recompute in flight reads the voxels as they are
+    if (rc) return rc;
+    const int want_ids = emptied_ids_xyz ? max_ids : 0;
+    rc = deintegrate::ensure_scratch(m, want_ids);
+    if (rc) return rc;
+    const float *d_depth = nullptr;
+    rc = align::stage_depth(m, frame, &d_depth);
+    if (rc) return rc;
+    rc = wait_for_input(m, m->stream);  // chisel_hip_wait_event / _order_map_after_stream: a device image is ready behind it
+    if (rc) return rc;
+
+    // ---- the two launches
+    chisel_hip_map::DeintegrateMemory &O = m->deintegrate_mem;
+    DeintegrateView G = O.view;
+    G.emptied = want_ids ? O.ids.get() : nullptr;
+    G.max_ids = want_ids;
+    DeintegrateFrame F;
+    fill_camera(F.cam, frame->pose, frame->fx, frame->fy, frame->cx, frame->cy, frame->width, frame->height);
+    F.depth = d_depth;
+    F.trunc_kind = m->integ.truncator_kind;
+    F.trunc_param = m->integ.truncator_param;
+    F.weight = m->integ.weight;
+    F.res = m->cfg.voxel_resolution;
+    F.half_res = m->cfg.voxel_resolution * 0.5f;                                          // ChunkManager.cpp:52
+    F.diag = (float)(2.0 * ::sqrt((double)3.0f) * (double)m->cfg.voxel_resolution);       // ProjectionIntegrator.h:58,109
+    F.color_rules = color_rules ? 1 : 0;
+    F.max_depth = color_rules ? 100.0f : 50.0f;
+    DeintegratePyramid Y;
+    deintegrate_pyramid(frame->pose, frame->fx, frame->fy, frame->cx, frame->cy, frame->width, frame->height, m->N, m->cfg.voxel_resolution, Y);
+    HIP_TRY(hipMemsetAsync(G.stats, 0, DS_WORDS * sizeof(unsigned long long), m->stream));
+    hipLaunchKernelGGL(deintegrate_list_kernel, dim3((unsigned)std::max(1, (m->view.committed + 255) / 256)), dim3(256), 0, m->stream, m->view, G, Y);
+    const unsigned grid = (unsigned)std::max(1, std::min(m->view.committed, DEINTEGRATE_GRID));
+    FOR_CHUNK_SIZE(m->N, hipLaunchKernelGGL(deintegrate_apply_kernel<N>, dim3(grid), dim3(256), 0, m->stream, m->view, G, F));
+    HIP_TRY(hipGetLastError());
+
+    // ---- the bookkeeping
+    m->mesh_mark_needed = true;  // (slots dirtied without their neighbourhoods listed: the next recompute runs mesh_mark_kernel)
+    HIP_TRY(note_map_mutation(m));
+    if (!stats) {
+        if (!frame->on_device) HIP_TRY(hipStreamSynchronize(m->stream));  // (the copy of the caller's image is over on return)
+        return CHISEL_HIP_OK;
+    }
+    hipLaunchKernelGGL(deintegrate_report_kernel, dim3(1), dim3(1), 0, m->stream, G, O.host.dev());
+    HIP_TRY(hipGetLastError());
+    rc = check_device_error(m);  // the one wait
+    if (rc) return rc;
+    const volatile unsigned long long *res = O.host.get();
+    stats->chunks_tested = (int64_t)res[DS_TESTED];
+    stats->chunks_touched = (int64_t)res[DS_TOUCHED];
+    stats->chunks_emptied = (int64_t)res[DS_EMPTIED];
+    stats->voxels_updated = (int64_t)res[DS_UPDATED];
+    stats->voxels_cleared = (int64_t)res[DS_CLEARED];
+    stats->voxels_skipped = (int64_t)res[DS_SKIPPED];
+    const int64_t n_ids = std::min<int64_t>(stats->chunks_emptied, want_ids);
+    if (n_ids > 0) HIP_TRY(hipMemcpy(emptied_ids_xyz, O.ids.get(), (size_t)n_ids * 3 * sizeof(int), hipMemcpyDeviceToHost));
+    return CHISEL_HIP_OK;
+}

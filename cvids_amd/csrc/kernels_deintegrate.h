@@ -1,0 +1,217 @@
+// kernels_deintegrate.h -- one depth frame taken back out of the map (chisel_hip_deintegrate_depth; DESIGN.md 3.10 "Taking a frame out
+// again" is the definition).
+//
+// Not a kernel of the reference: a pose graph moves keyframe poses after their depth maps were fused, and DistVoxel::Integrate is a
+// weighted running mean that can be inverted per voxel.  A voxel is SELECTED when the frame's integration sent it down the in-band
+// branch -- ProjectionIntegrator::Integrate / IntegrateColor (ProjectionIntegrator.h:51-99 / :101-183), all in fp32, one rounding per
+// operation, no FMA:
+//     c  = ((float)i res + half_res) + (float)(N id) res                    the reference's centroid (ChunkManager.cpp:50-66, Chunk.cpp:43)
+//     q  = R^T (c - t), each row as r0 dx + (r3 dy + r6 dz);  u = fx qx (1 / qz) + cx, v likewise       (color_pixel's order)
+//     on the image (0 <= u < W, 0 <= v < H) and qz >= 0;  depth = D[(int)v][(int)u], not NaN, not above max_depth (50 / 100)
+//     sd = depth - qz,  |sd| < truncation(depth) + diag
+// which depends on the frame and the geometry only.  With wu the weight of that update (1, or weight / (5 truncation) under the colour
+// rules) a selected voxel (s, w) becomes
+//     !(w > 0)                      left alone                                  (skipped)
+//     w2 = w - wu, !(w2 > w 2^-16)  DistVoxel::Reset(): (99999, 0)              (cleared: an exact zero, a residue of rounding, a negative
+//                                                                                remainder after a carve, NaN)
+//     else                          ((w s - wu sd) / w2, w2)                    (updated)
+// The carve branch is not undone and colour voxels are never written.  Two kernels on the map's stream (host_deintegrate.h), no host
+// wait between them:
+//   deintegrate_list_kernel      one thread per committed slot: the resident chunks whose bounding sphere reaches into the image pyramid,
+//                                compacted into a list, one append per wave
+//   deintegrate_apply_kernel<N>  a fixed grid of workgroups strides over the list (its length is read from the device): the rule above,
+//                                then the chunk's bookkeeping
+#pragma once
+#include "chisel_device.h"
+#include "deintegrate_host.h"
+
+namespace chisel_hip {
+
+// results of a de-integration (device 64-bit words): chisel_hip_deintegrate_stats in its order, then the length of the list
+constexpr int DS_TESTED = 0, DS_TOUCHED = 1, DS_EMPTIED = 2, DS_UPDATED = 3, DS_CLEARED = 4, DS_SKIPPED = 5, DS_LISTED = 6, DS_WORDS = 8;
+constexpr int DEINTEGRATE_GRID = 2048;  // workgroups of the apply kernel: what is resident at once
+
+struct DeintegrateView {
+    int *list;                  // [committed slots] the listed slots
+    unsigned long long *stats;  // [DS_WORDS]
+    int *emptied;               // [3 max_ids] ids of the emptied chunks, or null
+    int max_ids;
+};
+// the frame, the integrator's settings and the map's constants
+struct DeintegrateFrame {
+    CameraParams cam;
+    const float *depth;         // W x H on the device
+    int trunc_kind;
+    float trunc_param, weight;
+    float res, half_res, diag, max_depth;
+    int color_rules;            // IntegrateColor's rules: NaN depth skipped, max_depth 100, wu = constant_weight
+};
+__global__ __launch_bounds__(256) void deintegrate_list_kernel(MapView M, DeintegrateView G, DeintegratePyramid Y) {
+    const int slot = blockIdx.x * blockDim.x + threadIdx.x;
+    bool resident = false, keep = false;
+    if (slot < M.committed) {
+        const uint64_t key = M.slot_key[slot];
+        if (key != KEY_EMPTY) {
+            resident = true;
+            int x, y, z;
+            unpack_id(key, x, y, z);
+            keep = deintegrate_keeps(Y, x, y, z);
+        }
+    }
+    // one append per wave with a survivor; the lanes of a wave keep their order
+    const unsigned long long tested = __ballot(resident), kept = __ballot(keep);
+    if (tested == 0ull) return;
+    const int lane = threadIdx.x & 63;
+    int base = 0;
+    if (lane == 0) {
+        atomicAdd(&G.stats[DS_TESTED], (unsigned long long)__popcll(tested));
+        if (kept) base = (int)atomicAdd(&G.stats[DS_LISTED], (unsigned long long)__popcll(kept));
+    }
+    base = __shfl(base, 0);
+    if (keep) G.list[base + __popcll(kept & ((1ull << lane) - 1ull))] = slot;  // (at most one entry per committed slot: the list holds them all)
+}
+
+// the frame's verdict on the voxel centred at (cx, cy, cz): selected -> sd and wu
+__device__ inline bool deintegrate_select(const DeintegrateFrame &F, float cx, float cy, float cz, float &sd, float &wu) {
+    const CameraParams &K = F.cam;
+    const float dx = cx - K.t[0], dy = cy - K.t[1], dz = cz - K.t[2];
+    const float qx = K.R[0] * dx + (K.R[3] * dy + K.R[6] * dz);
+    const float qy = K.R[1] * dx + (K.R[4] * dy + K.R[7] * dz);
+    const float qz = K.R[2] * dx + (K.R[5] * dy + K.R[8] * dz);
+    const float iq = 1.0f / qz;
+    const float u = K.fx * qx * iq + K.cx;
+    const float v = K.fy * qy * iq + K.cy;
+    if (!((u >= 0.0f) && (v >= 0.0f) && (u < (float)K.W) && (v < (float)K.H)) || qz < 0.0f) return false;
+    const int iu = (int)u, iv = (int)v;
+    if (iu >= K.W || iv >= K.H) return false;  // ((float)W rounds up from 2^24 on: no pixel there)
+    const float depth = F.depth[(size_t)iv * K.W + iu];
+    if (depth > F.max_depth || (F.color_rules && isnan(depth))) return false;
+    const float tau = truncation_distance(F.trunc_kind, F.trunc_param, depth);
+    sd = depth - qz;
+    if (!(fabsf(sd) < tau + F.diag)) return false;
+    wu = F.color_rules ? constant_weight(F.weight, tau) : 1.0f;
+    return true;
+}
+
+// One workgroup per listed chunk at a time; a lane owns 4 consecutive x voxels (the map's lane layout: 16-byte accesses of sdf and wgt),
+// quads q = thread, thread + 256, ...  The depth image is gathered directly.
+template <int N>
+__global__ __launch_bounds__(256) void deintegrate_apply_kernel(MapView M, DeintegrateView G, DeintegrateFrame F) {
+    constexpr int V = N * N * N;
+    __shared__ unsigned s_upd, s_clr, s_skip, s_signs, s_live;
+    const int n = (int)G.stats[DS_LISTED];  // block-uniform: written by the list kernel, which is over
+    unsigned long long t_touched = 0, t_upd = 0, t_clr = 0, t_skip = 0;  // thread 0: this workgroup's share of the stats
+    for (int item = blockIdx.x; item < n; item += gridDim.x) {
+        const int slot = G.list[item];  // block-uniform
+        int idx, idy, idz;
+        unpack_id(M.slot_key[slot], idx, idy, idz);
+        if (threadIdx.x == 0) s_upd = s_clr = s_skip = s_signs = s_live = 0u;
+        __syncthreads();
+        const float ox = (float)(N * idx) * F.res, oy = (float)(N * idy) * F.res, oz = (float)(N * idz) * F.res;
+        const size_t base = (size_t)slot * V;
+        unsigned n_upd = 0, n_clr = 0, n_skip = 0;
+        bool pos = false, neg = false;
+        for (int q = threadIdx.x; q < V / 4; q += 256) {
+            const int v0 = 4 * q, x0 = v0 % N, y = (v0 / N) % N, z = v0 / (N * N);
+            const float cy = ((float)y * F.res + F.half_res) + oy, cz = ((float)z * F.res + F.half_res) + oz;
+            float4 s4, w4;
+            bool loaded = false, changed = false;
+            float *sv = &s4.x, *wv = &w4.x;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const float cx = ((float)(x0 + j) * F.res + F.half_res) + ox;
+                float sd, wu;
+                if (!deintegrate_select(F, cx, cy, cz, sd, wu)) continue;
+                if (!loaded) {  // (most quads of most listed chunks lie outside the band: the voxels are read on demand)
+                    s4 = *reinterpret_cast<const float4 *>(M.sdf + base + v0);
+                    w4 = *reinterpret_cast<const float4 *>(M.wgt + base + v0);
+                    loaded = true;
+                }
+                const float w = wv[j];
+                if (!(w > 0.0f)) {
+                    n_skip++;
+                    continue;
+                }
+                const float w2 = w - wu;
+                if (!(w2 > w * 0x1p-16f)) {
+                    sv[j] = 99999.0f;  // DistVoxel::Reset (DistVoxel.cpp:27-31)
+                    wv[j] = 0.0f;
+                    n_clr++;
+                } else {
+                    sv[j] = (w * sv[j] - wu * sd) / w2;
+                    wv[j] = w2;
+                    n_upd++;
+                    if (w2 > 0.5f) {
+                        if (sv[j] < 0.0f) neg = true;
+                        else pos = true;
+                    }
+                }
+                changed = true;
+            }
+            if (changed) {
+                *reinterpret_cast<float4 *>(M.sdf + base + v0) = s4;
+                *reinterpret_cast<float4 *>(M.wgt + base + v0) = w4;
+            }
+        }
+        // the chunk's figures: across the wave first, then one LDS atomic per wave
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            n_upd += __shfl_down(n_upd, o);
+            n_clr += __shfl_down(n_clr, o);
+            n_skip += __shfl_down(n_skip, o);
+        }
+        const unsigned signs = (__any(pos) ? SUM_POS : 0u) | (__any(neg) ? SUM_NEG : 0u);
+        if ((threadIdx.x & 63) == 0) {
+            if (n_upd) atomicAdd(&s_upd, n_upd);
+            if (n_clr) atomicAdd(&s_clr, n_clr);
+            if (n_skip) atomicAdd(&s_skip, n_skip);
+            if (signs) atomicOr(&s_signs, signs);
+        }
+        __syncthreads();
+        const bool touched = (s_upd | s_clr) != 0u;  // block-uniform
+        if (touched) {
+            // emptied?  Every weight of the chunk, each lane the quads it owns (what it stored itself, or nobody did)
+            bool live = false;
+            for (int q = threadIdx.x; q < V / 4; q += 256) {
+                const float4 w4 = *reinterpret_cast<const float4 *>(M.wgt + base + 4 * q);
+                live = live || w4.x > 0.0f || w4.y > 0.0f || w4.z > 0.0f || w4.w > 0.0f;
+            }
+            if (__any(live) && (threadIdx.x & 63) == 0) atomicOr(&s_live, 1u);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            t_skip += s_skip;
+            if (touched) {
+                // what integrate_kernel's epilogue leaves for a chunk it updated; the 27-neighbourhood joins the job list through
+                // mesh_mark_kernel at the next recompute (the host sets mesh_mark_needed)
+                mark_slot_dirty(M, slot);
+                if (s_signs) atomicOr(&slot_summary(M)[slot], s_signs);
+                t_touched++;
+                t_upd += s_upd;
+                t_clr += s_clr;
+                if (!s_live) {
+                    const unsigned long long at = atomicAdd(&G.stats[DS_EMPTIED], 1ull);
+                    if (G.emptied && at < (unsigned long long)G.max_ids) {
+                        G.emptied[3 * at] = idx;
+                        G.emptied[3 * at + 1] = idy;
+                        G.emptied[3 * at + 2] = idz;
+                    }
+                }
+            }
+        }
+        // (thread 0 resets the LDS words for the next round behind its own reads; everybody else's were in front of the barrier above)
+    }
+    if (threadIdx.x == 0) {
+        if (t_touched) atomicAdd(&G.stats[DS_TOUCHED], t_touched);
+        if (t_upd) atomicAdd(&G.stats[DS_UPDATED], t_upd);
+        if (t_clr) atomicAdd(&G.stats[DS_CLEARED], t_clr);
+        if (t_skip) atomicAdd(&G.stats[DS_SKIPPED], t_skip);
+    }
+}
+
+// the stats into pinned memory (one thread)
+__global__ void deintegrate_report_kernel(DeintegrateView G, unsigned long long *host_words) {
+    for (int i = 0; i < DS_WORDS; i++) host_words[i] = G.stats[i];
+}
+
+}  // namespace chisel_hip

@@ -876,6 +876,23 @@ class Chisel {  // Chisel.h:38-230
         hip_check(chisel_hip_merge_map(map, other.map, pose, &stats));
         return stats;
     }
+    // Not in the reference: the depth frame that was integrated at `extrinsic` with `integrator` taken out of the distance voxels again
+    // (chisel_hip_deintegrate_depth) -- a keyframe whose pose a loop closure has moved: take it out at the old pose, IntegrateDepthScan
+    // it at the new one.  colorRules: it went in through IntegrateDepthScanColor.  Carves and colour voxels are not undone.
+    // collectEmptied: the chunks left without any weight are handed to GarbageCollect.  Returns with every voxel update visible.
+    chisel_hip_deintegrate_stats DeintegrateDepthScan(const ProjectionIntegrator &integrator, const std::shared_ptr<const DepthImage<float>> &depthImage,
+                                                      const Transform &extrinsic, const PinholeCamera &camera, bool colorRules, bool collectEmptied = true) {
+        const chisel_hip_integrator in = integrator.HipStruct();
+        hip_check(chisel_hip_set_integrator(map, &in));
+        const chisel_hip_depth_frame f = hipfacade::DepthFrame(*depthImage, extrinsic, camera);
+        int64_t resident = 0;
+        hip_check(chisel_hip_num_chunks(map, &resident));
+        std::vector<int> ids(collectEmptied ? 3 * (size_t)resident : 0);  // (no chunk is created: the resident ones bound the emptied ones)
+        chisel_hip_deintegrate_stats stats;
+        hip_check(chisel_hip_deintegrate_depth(map, &f, colorRules ? 1 : 0, &stats, ids.empty() ? nullptr : ids.data(), (int)(ids.size() / 3)));
+        if (collectEmptied && stats.chunks_emptied > 0) hip_check(chisel_hip_garbage_collect(map, ids.data(), (int)stats.chunks_emptied));
+        return stats;
+    }
     chisel_hip_map *HipMap() const { return map; }
 
   protected:

@@ -46,7 +46,8 @@ extern "C" {
  *      (chisel_hip_shell_plan_queue, _import_shells_fixed, _shell_commit), the stereo matcher (chisel_hip_stereo_*)
  *   3  chisel_hip_export_chunks, _import_ghost_chunks, _export_shells, _import_ghost_shells removed; later additions within 3 (nothing
  *      removed or re-typed): chisel_hip_render_view, chisel_hip_query_points, chisel_hip_cast_rays, chisel_hip_align_terms,
- *      chisel_hip_align_solve, chisel_hip_align_depth, chisel_hip_merge_map (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
+ *      chisel_hip_align_solve, chisel_hip_align_depth, chisel_hip_merge_map, chisel_hip_deintegrate_depth (no slot in the hipEvent profiler:
+ *      CHISEL_HIP_NUM_KERNELS stays) */
 #define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -644,6 +645,35 @@ typedef struct {
     int64_t src_chunks, dst_chunks_created, dst_chunks_updated, voxels_updated;
 } chisel_hip_merge_stats;   /* 32 bytes */
 int chisel_hip_merge_map(chisel_hip_map *dst, chisel_hip_map *src, const float src_to_dst[12], chisel_hip_merge_stats *stats);
+/* Not in the reference: one depth frame taken back out of the map -- what a pose-graph server needs when a loop closure moves a keyframe
+ * whose depth map is already fused: take it out at the pose it went in with, integrate it again at the corrected one.  DESIGN.md "Taking
+ * a frame out again" has the definition to the bit; in short: a voxel is selected when the frame's integration under the map's current
+ * integrator settings (chisel_hip_set_integrator; the caller sees to it that they are the ones the frame went in with) sent it down the
+ * in-band branch -- ProjectionIntegrator::Integrate (color_rules == 0: depth <= 50, update weight wu = 1) or IntegrateColor
+ * (color_rules != 0: NaN depth skipped, depth <= 100, wu = weight / (5 truncation)) -- which depends on the frame and the geometry only.
+ * With sd = depth - camera z, a selected voxel (s, w):
+ *   !(w > 0)                          is left alone                                  (voxels_skipped)
+ *   w2 = w - wu, !(w2 > w * 2^-16)    becomes DistVoxel::Reset(), (99999, 0)         (voxels_cleared: the frame was the voxel's only one, or
+ *                                     what is left is a residue of rounding, negative -- the voxel was carved since -- or NaN)
+ *   otherwise                         becomes ((w s - wu sd) / w2, w2)               (voxels_updated)
+ * each product, sum and quotient rounded separately in fp32.  NOT undone: the carve branch (Carve() and the weight decay destroy what they
+ * act on) and colour voxels, which this call never writes -- so integrating the same frame again restores the distance field up to
+ * rounding, and only where nothing was carved in between.
+ * No chunk is created or removed.  A chunk with an updated or cleared voxel (chunks_touched) is left as an integration leaves an updated
+ * chunk, in meshesToUpdate with its 27-neighbourhood; of those, the chunks in which no voxel has a weight > 0 afterwards are counted in
+ * chunks_emptied and the ids of the first max_ids of them, in any order, written to emptied_ids_xyz (3 ints each; NULL and 0 are allowed):
+ * hand them to chisel_hip_garbage_collect to be rid of them.  chunks_tested: the resident chunks, each tested against the frame's image
+ * pyramid.  The CHISEL_HIP_CNT_* counters are not touched: they count forward executions.
+ * frame->on_device as in chisel_hip_integrate_depth.  The work is queued on the map's stream; with stats == NULL (and a device image) the
+ * call waits for nothing, otherwise once, at its end.
+ * Refused with nothing touched: CHISEL_HIP_ERR_INVALID for a null map, frame or depth image, a non-positive size or more than 2^31 - 1
+ * pixels, a pose entry or an intrinsic that is not finite, max_ids < 0, emptied_ids_xyz without stats; CHISEL_HIP_ERR_UNSUPPORTED for a
+ * group or one shard of several (ghost chunks would need a rule of their own). */
+typedef struct {
+    int64_t chunks_tested, chunks_touched, chunks_emptied, voxels_updated, voxels_cleared, voxels_skipped;
+} chisel_hip_deintegrate_stats;   /* 48 bytes */
+int chisel_hip_deintegrate_depth(chisel_hip_map *map, const chisel_hip_depth_frame *frame, int color_rules, chisel_hip_deintegrate_stats *stats,
+                                 int *emptied_ids_xyz, int max_ids);
 /* ProjectionIntegrator::Integrate<DataType>(depthImage, camera, cameraPose, chunk) / IntegrateColor (ProjectionIntegrator.h:51-52,
  * :101-102): ONE frame into ONE resident chunk -- whether or not the frustum's id range holds it, as the reference's per-chunk call
  * knows nothing of frusta --; color may be NULL (the depth-only update rule).  *updated = the call's return value there ("some voxel
