@@ -149,6 +149,13 @@ __device__ inline bool mark_slot_dirty(const MapView &M, int slot) {
     }
     return false;
 }
+// A chunk was updated by something other than integrate_kernel (one thread of the workgroup that did it; signs: SUM_* of the observed
+// voxels it wrote): what integrate_kernel's epilogue leaves for a chunk it updated.  The 27-neighbourhood joins the job list through
+// mesh_mark_kernel at the next recompute: the host sets mesh_mark_needed.
+__device__ inline void note_slot_updated(const MapView &M, int slot, unsigned signs) {
+    mark_slot_dirty(M, slot);
+    if (signs) atomicOr(&slot_summary(M)[slot], signs);
+}
 
 // depth min/max pyramid: level l (PYR_L0 <= l <= PYR_L1) has ceil(W/2^l) x ceil(H/2^l) texels of
 // (min, max) over the valid pixels of a 2^l x 2^l block; (+inf, -inf) when the block has none.

@@ -313,13 +313,10 @@ struct chisel_hip_map {
     size_t color_stage_bytes = 0;
     // scratch for queries
     DeviceBuffer<int> scratch_i;
-    size_t scratch_i_elems = 0;
+    DeviceBuffer<float> frame_stage;     // a host frame's image on its way to the entries outside the integration path (stage_depth), grown on demand
     struct AlignMemory {                 // frame-to-model alignment (host_align.h), allocated on first use, grown on demand
         DeviceBuffer<double> partials;   // the levels of the summation tree one behind the other: [ALIGN_SUMS][groups] each
-        size_t partials_elems = 0;
         DeviceBuffer<double> terms;      // [ALIGN_TERMS]: where the tree ends when the caller's array is on the host
-        DeviceBuffer<float> depth;       // staging of a host frame
-        size_t depth_elems = 0;
     } align_mem;
     // meshing state
     int update_meshes_calls = 0;                                       // Chisel.cpp:53 "static int cnt"
@@ -393,12 +390,11 @@ struct chisel_hip_map {
         MergeView view{};                                              // (what the kernels take: copies of the pointers above)
         int64_t chunks_hint = 0;                                       // chunks of the latest source (sizes the table of the next merge)
     } merge_mem;
-    struct DeintegrateMemory {                                         // chisel_hip_deintegrate_depth (host_deintegrate.h), allocated on first use
+    struct DeintegrateMemory {                                         // chisel_hip_deintegrate_depth (host_deintegrate.h), allocated on first use, grown on demand
         DeviceBuffer<int> list, ids;                                   // the listed slots | the ids of the emptied chunks
         DeviceBuffer<unsigned long long> stats;
         PinnedBuffer<unsigned long long> host;                         // [DS_WORDS] where the stats reach the host
         DeintegrateView view{};                                        // (what the kernels take: copies of the pointers above)
-        int list_capacity = 0, ids_capacity = 0;
     } deintegrate_mem;
     // profiling
     bool profiling = false;
@@ -560,13 +556,31 @@ hipError_t alloc_viewed(DeviceBuffer<T> &buf, T *&p, size_t n) {
     return e;
 }
 
+// ... grown on demand: at least n elements.  A buffer that is replaced may still be read by what `stream` holds, which is waited for
+// first; one that is large enough costs nothing.  `view`: the copy of buf.get() the kernels are given, as alloc_viewed keeps it.
+template <class T>
+int grow_buffer(DeviceBuffer<T> &buf, size_t n, hipStream_t stream, T **view = nullptr) {
+    if (n <= buf.size()) return CHISEL_HIP_OK;
+    HIP_TRY(hipStreamSynchronize(stream));
+    const hipError_t e = buf.alloc(n);
+    if (view) *view = buf.get();
+    HIP_TRY(e);
+    return CHISEL_HIP_OK;
+}
+
 int ensure_scratch(chisel_hip_map *m, size_t elems) {
-    if (elems <= m->scratch_i_elems) return CHISEL_HIP_OK;
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    m->scratch_i_elems = 0;
-    size_t n = std::max<size_t>(elems, 1024);
-    HIP_TRY(m->scratch_i.alloc(n));
-    m->scratch_i_elems = n;
+    return grow_buffer(m->scratch_i, std::max<size_t>(elems, 1024), m->stream);  // (never fewer than 1024)
+}
+
+// a frame's image on the device for the entries outside the integration path (alignment, de-integration): the caller's own, or a copy
+// in the map's staging buffer, queued on the map's stream
+int stage_depth(chisel_hip_map *m, const chisel_hip_depth_frame *f, const float **d_depth) {
+    *d_depth = f->depth;
+    if (f->on_device) return CHISEL_HIP_OK;
+    const size_t n = (size_t)f->width * f->height;
+    if (const int rc = grow_buffer(m->frame_stage, n, m->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(m->frame_stage.get(), f->depth, n * sizeof(float), hipMemcpyHostToDevice, m->stream));
+    *d_depth = m->frame_stage.get();
     return CHISEL_HIP_OK;
 }
 
@@ -1343,6 +1357,7 @@ inline chisel_hip_map *owner_map(chisel_hip_map *g, const int id[3]) {
 }  // namespace
 
 #include "host_mesh.h"
+#include "host_rewrite.h"
 #include "host_cloud.h"
 #include "host_group.h"
 

@@ -74,25 +74,7 @@ int refusal(chisel_hip_map *m, const chisel_hip_depth_frame *f, const char *name
     const int rc = query_refusal(m, name, "reads the voxels around every pixel's point");
     if (rc) return rc;
     if (!f || !f->depth) return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": null frame or depth image");
-    if (f->width < 1 || f->height < 1) return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": non-positive image size");
-    if ((int64_t)f->width * f->height > (int64_t)INT32_MAX) return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": more than 2^31 - 1 pixels");
-    return CHISEL_HIP_OK;
-}
-
-// the frame's image on the device: the caller's own, or a copy in the map's staging buffer (queued on the map's stream)
-int stage_depth(chisel_hip_map *m, const chisel_hip_depth_frame *f, const float **d_depth) {
-    *d_depth = f->depth;
-    if (f->on_device) return CHISEL_HIP_OK;
-    const size_t n = (size_t)f->width * f->height;
-    auto &A = m->align_mem;
-    if (A.depth_elems < n) {
-        HIP_TRY(hipStreamSynchronize(m->stream));  // (a launch chain before this one may still read the buffer)
-        A.depth_elems = 0;
-        HIP_TRY(A.depth.alloc(n));
-        A.depth_elems = n;
-    }
-    HIP_TRY(hipMemcpyAsync(A.depth.get(), f->depth, n * sizeof(float), hipMemcpyHostToDevice, m->stream));
-    *d_depth = A.depth.get();
+    if (const char *why = frame_image_refusal(f->depth, f->width, f->height)) return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": " + why);
     return CHISEL_HIP_OK;
 }
 
@@ -102,12 +84,7 @@ int launch_terms(chisel_hip_map *m, const chisel_hip_depth_frame *f, const float
     auto &A = m->align_mem;
     size_t need = 0;
     for (int g = (n + 255) / 256; g > 1; g = (g + 255) / 256) need += (size_t)ALIGN_SUMS * g;
-    if (A.partials_elems < need) {
-        HIP_TRY(hipStreamSynchronize(m->stream));
-        A.partials_elems = 0;
-        HIP_TRY(A.partials.alloc(need));
-        A.partials_elems = need;
-    }
+    if (const int rc = grow_buffer(A.partials, need, m->stream)) return rc;
     AlignCamera cam;
     cam.cam = pixel_camera(pose, f->fx, f->fy, f->cx, f->cy);
     cam.near_plane = f->near_plane; cam.far_plane = f->far_plane;
@@ -154,7 +131,7 @@ int chisel_hip_align_terms(chisel_hip_map *m, const chisel_hip_depth_frame *fram
     }
     const float *d_depth = nullptr;
     {
-        int rc_s = align::stage_depth(m, frame, &d_depth);
+        int rc_s = stage_depth(m, frame, &d_depth);
         if (rc_s) return rc_s;
         if (!terms_on_device && (rc_s = align::ensure_terms(m))) return rc_s;
         if ((rc_s = wait_for_input(m, m->stream))) return rc_s;  // chisel_hip_wait_event / _order_map_after_stream: the image is ready behind it
@@ -196,7 +173,7 @@ int chisel_hip_align_depth(chisel_hip_map *m, const chisel_hip_depth_frame *fram
     }
     const float *d_depth = nullptr;
     {
-        int rc_s = align::stage_depth(m, frame, &d_depth);  // once for all iterations
+        int rc_s = stage_depth(m, frame, &d_depth);  // once for all iterations
         if (rc_s) return rc_s;
         if ((rc_s = align::ensure_terms(m))) return rc_s;
         if ((rc_s = wait_for_input(m, m->stream))) return rc_s;

@@ -1,6 +1,7 @@
 // host_buffer.h -- who frees what (included by chisel_hip.hip, host side only): a buffer is freed by the object that holds its
 // owner, in that object's destructor, and nowhere else.  The views the kernels take (MapView, StereoView, ...) keep raw pointers:
-// copies of get().  Move-only; alloc() frees what was held before, and holds nothing after a failure.
+// copies of get().  Move-only; alloc() frees what was held before, and holds nothing after a failure.  A DeviceBuffer knows its element
+// count (size(): 0 while it holds nothing), so that a buffer grown on demand needs no capacity field beside it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <assert.h>
@@ -13,24 +14,28 @@ namespace chisel_hip {
 template <class T>
 struct DeviceBuffer {
     DeviceBuffer() = default;
-    DeviceBuffer(DeviceBuffer &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
-    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept { std::swap(p_, o.p_); return *this; }  // (o frees what this held)
+    DeviceBuffer(DeviceBuffer &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept { std::swap(p_, o.p_); std::swap(n_, o.n_); return *this; }  // (o frees what this held)
     ~DeviceBuffer() { reset(); }
     hipError_t alloc(size_t n) {
         reset();
         const hipError_t e = hipMalloc(&p_, n * sizeof(T));
         if (e != hipSuccess) p_ = nullptr;
+        else n_ = n;
         return e;
     }
     void reset() {
         if (p_) (void)hipFree(p_);
         p_ = nullptr;
+        n_ = 0;
     }
     T *get() const { return p_; }
+    size_t size() const { return n_; }  // elements
     explicit operator bool() const { return p_ != nullptr; }
 
 private:
     T *p_ = nullptr;
+    size_t n_ = 0;
 };
 
 // n elements of page-locked host memory (hipHostMalloc / hipHostFree) that the device addresses too: dev() is get() as the kernels see it

@@ -1,6 +1,7 @@
-// deintegrate_host.h -- the host-side pieces of chisel_hip_deintegrate_depth that call nothing of HIP (included by kernels_deintegrate.h
-// and, on its own, by tests/deintegrate_host_check.cpp, which runs them under the address and undefined-behaviour sanitizers on the
-// CPU): what the entry refuses about a frame, and the planes the list kernel rejects chunks by.
+// host_checks.h -- the host-side pieces of the side entries (chisel_hip_align_terms / _align_depth, chisel_hip_deintegrate_depth) that
+// call nothing of HIP (included by kernels_deintegrate.h and, on its own, by tests/host_checks_check.cpp, which runs them under the
+// address and undefined-behaviour sanitizers on the CPU): what the entries refuse about a frame's image, what de-integration refuses
+// about its other arguments, and the planes its list kernel rejects chunks by.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -63,12 +64,19 @@ CHISEL_HOST_DEVICE inline bool deintegrate_keeps(const DeintegratePyramid &Y, in
     return keep;
 }
 
-// what the entry refuses about its arguments other than the map; null = go on
-inline const char *deintegrate_refusal(const float *depth, int width, int height, const float pose[12], float fx, float fy, float cx, float cy,
-                                       bool want_stats, bool want_ids, int max_ids) {
+// what the entries that take a depth frame outside the integration path refuse about its image (check_frame of the integration path
+// has limits of its own); null = go on
+inline const char *frame_image_refusal(const float *depth, int width, int height) {
     if (!depth) return "null depth image";
     if (width < 1 || height < 1) return "non-positive image size";
     if ((int64_t)width * height > (int64_t)INT32_MAX) return "more than 2^31 - 1 pixels";
+    return nullptr;
+}
+
+// what chisel_hip_deintegrate_depth refuses about its arguments other than the map; null = go on
+inline const char *deintegrate_refusal(const float *depth, int width, int height, const float pose[12], float fx, float fy, float cx, float cy,
+                                       bool want_stats, bool want_ids, int max_ids) {
+    if (const char *why = frame_image_refusal(depth, width, height)) return why;
     for (int i = 0; i < 12; i++)
         if (!isfinite(pose[i])) return "the pose has an entry that is not finite";
     if (!isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy)) return "intrinsics that are not finite";

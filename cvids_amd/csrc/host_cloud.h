@@ -54,7 +54,6 @@ int ensure_cloud_buffers(chisel_hip_map *m, int64_t n) {
 
 template <int N>
 void launch_cloud_integrate(chisel_hip_map *m, const CloudParams &P, const CloudView &C) {
-    m->mesh_mark_needed = true;  // (this kernel dirties slots without listing their neighbourhoods: the next recompute runs mesh_mark_kernel)
     if (m->cfg.use_color)
         hipLaunchKernelGGL((cloud_integrate_kernel<N, true>), dim3(CLOUD_GRID), dim3(64 * CloudGeom<N>::WAVES), 0, m->stream, P, m->view, m->view_dev.get(), C);
     else
@@ -118,8 +117,7 @@ extern "C" int chisel_hip_integrate_pointcloud(chisel_hip_map *m, const chisel_h
     if (cloud->n_points > (int64_t)(0x7fffffff / (CLOUD_PAIRS_PER_POINT * 2)))
         return fail(CHISEL_HIP_ERR_UNSUPPORTED, "more than 2^26 points in one cloud");
     if (cloud->n_points == 0) return CHISEL_HIP_OK;  // no chunk is listed: Chisel.cpp:112-113
-    HIP_TRY(hipSetDevice(m->device));
-    int rc = check_mesh_totals(m);  // a recompute in flight reads the voxels as they are
+    int rc = rewrite_begin(m);  // (its settling is over: done above, in front of the group's branch)
     if (rc) return rc;
     rc = ensure_free_exact(m, CLOUD_MAX_LISTED);  // (a growable pool: a cloud creates at most the chunks it can list)
     if (rc) return rc;
@@ -146,9 +144,8 @@ extern "C" int chisel_hip_integrate_pointcloud(chisel_hip_map *m, const chisel_h
     hipLaunchKernelGGL(cloud_sort_kernel, dim3(CLOUD_GRID), dim3(256), 0, m->stream, P, C);
     FOR_CHUNK_SIZE(m->N, launch_cloud_integrate<N>(m, P, C));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(note_map_mutation(m));
     // the staging buffers (host clouds) and the per-cloud lists are reused by the next cloud: same stream, so no wait here
-    return CHISEL_HIP_OK;
+    return rewrite_end(m);  // (cloud_integrate_kernel dirties slots without listing their neighbourhoods)
 }
 
 // ChunkManager::GetChunkIDsIntersecting(cloud, cameraTransform, truncation, maxDist, chunkList) (ChunkManager.cpp:214-257): the chunks

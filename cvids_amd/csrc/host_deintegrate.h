@@ -1,8 +1,9 @@
 // host_deintegrate.h -- chisel_hip_deintegrate_depth (included by chisel_hip.hip; the kernels and the definition: kernels_deintegrate.h,
 // DESIGN.md 3.10).  Everything runs on the map's stream: the list kernel, then the apply kernel, whose fixed grid reads the list's length
 // from the device -- no host wait between them, and none at all when the caller asks for neither stats nor ids.  The scratch lives in the
-// map (chisel_hip_map::deintegrate_mem), is reused by the next call and freed with the map; a host image goes through the staging
-// buffer of the alignment entries (align::stage_depth).
+// map (chisel_hip_map::deintegrate_mem), is reused by the next call and freed with the map; a host image goes through the map's
+// staging buffer (stage_depth).  The frame it shares with the other entries that rewrite a map: host_rewrite.h; what it refuses about
+// its arguments, and the planes of the list kernel: host_checks.h.
 #pragma once
 
 namespace {
@@ -15,19 +16,9 @@ int ensure_scratch(chisel_hip_map *m, int max_ids) {
         HIP_TRY(O.host.alloc(DS_WORDS));
         HIP_TRY(alloc_viewed(O.stats, O.view.stats, (size_t)DS_WORDS));
     }
-    if (O.list_capacity < std::max(m->view.committed, 1)) {
-        HIP_TRY(hipStreamSynchronize(m->stream));  // (a launch chain before this one may still read the list)
-        O.list_capacity = 0;
-        HIP_TRY(alloc_viewed(O.list, O.view.list, (size_t)std::max(m->view.committed, 1)));
-        O.list_capacity = std::max(m->view.committed, 1);
-    }
-    if (O.ids_capacity < max_ids) {
-        HIP_TRY(hipStreamSynchronize(m->stream));
-        O.ids_capacity = 0;
-        HIP_TRY(O.ids.alloc((size_t)3 * max_ids));
-        O.ids_capacity = max_ids;
-    }
-    return CHISEL_HIP_OK;
+    const int rc = grow_buffer(O.list, (size_t)std::max(m->view.committed, 1), m->stream, &O.view.list);  // (a launch chain before this one may still read the list)
+    if (rc) return rc;
+    return grow_buffer(O.ids, (size_t)3 * max_ids, m->stream);
 }
 
 }  // namespace deintegrate
@@ -45,15 +36,13 @@ extern "C" int chisel_hip_deintegrate_depth(chisel_hip_map *m, const chisel_hip_
     if (const char *why = deintegrate_refusal(frame->depth, frame->width, frame->height, frame->pose, frame->fx, frame->fy, frame->cx, frame->cy,
                                               stats != nullptr, emptied_ids_xyz != nullptr, max_ids))
         return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": " + why);
-    SETTLE(m);
-    HIP_TRY(hipSetDevice(m->device));
-    int rc = check_mesh_totals(m);  // a recompute in flight reads the voxels as they are
+    int rc = rewrite_begin(m);
     if (rc) return rc;
     const int want_ids = emptied_ids_xyz ? max_ids : 0;
     rc = deintegrate::ensure_scratch(m, want_ids);
     if (rc) return rc;
     const float *d_depth = nullptr;
-    rc = align::stage_depth(m, frame, &d_depth);
+    rc = stage_depth(m, frame, &d_depth);
     if (rc) return rc;
     rc = wait_for_input(m, m->stream);  // chisel_hip_wait_event / _order_map_after_stream: a device image is ready behind it
     if (rc) return rc;
@@ -83,13 +72,13 @@ extern "C" int chisel_hip_deintegrate_depth(chisel_hip_map *m, const chisel_hip_
     HIP_TRY(hipGetLastError());
 
     // ---- the bookkeeping
-    m->mesh_mark_needed = true;  // (slots dirtied without their neighbourhoods listed: the next recompute runs mesh_mark_kernel)
-    HIP_TRY(note_map_mutation(m));
+    rc = rewrite_end(m);
+    if (rc) return rc;
     if (!stats) {
         if (!frame->on_device) HIP_TRY(hipStreamSynchronize(m->stream));  // (the copy of the caller's image is over on return)
         return CHISEL_HIP_OK;
     }
-    hipLaunchKernelGGL(deintegrate_report_kernel, dim3(1), dim3(1), 0, m->stream, G, O.host.dev());
+    hipLaunchKernelGGL(report_words_kernel<unsigned long long>, dim3(1), dim3(1), 0, m->stream, (const unsigned long long *)G.stats, O.host.dev(), DS_WORDS);
     HIP_TRY(hipGetLastError());
     rc = check_device_error(m);  // the one wait
     if (rc) return rc;

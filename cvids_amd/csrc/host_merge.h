@@ -1,4 +1,5 @@
-// host_merge.h -- chisel_hip_merge_map (included by chisel_hip.hip; the kernels and the definition: kernels_merge.h).
+// host_merge.h -- chisel_hip_merge_map (included by chisel_hip.hip; the kernels and the definition: kernels_merge.h; the
+// frame it shares with the other entries that rewrite a map: host_rewrite.h).
 // Everything runs on the destination's stream, ordered behind what the source has queued and in front of what it queues next, with the
 // events behind chisel_hip_order_stream_after_map.  One host wait: the number of candidate chunks and how many of them the destination
 // lacks, from which the pool and the grids are sized -- and from which a fixed pool that cannot take them refuses, before the first
@@ -29,9 +30,9 @@ int ensure_merge_scratch(chisel_hip_map *dst, int64_t chunks) {
     while (want < 2ull * 27ull * (uint64_t)std::max<int64_t>(chunks, 1)) want *= 2;
     if (want > (1ull << 30)) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "chisel_hip_merge_map: the source holds more chunks than one merge lists");
     if (want <= G.table_capacity) return CHISEL_HIP_OK;
-    HIP_TRY(hipStreamSynchronize(dst->stream));
     G.table_capacity = 0;
-    HIP_TRY(alloc_viewed(O.table, G.table, (size_t)want));
+    const int rc = grow_buffer(O.table, (size_t)want, dst->stream, &G.table);  // (waits for the stream: nothing reads the other two any more)
+    if (rc) return rc;
     HIP_TRY(alloc_viewed(O.list, G.list, (size_t)want / 2));
     HIP_TRY(alloc_viewed(O.slots, G.slots, (size_t)want / 2));
     G.table_capacity = (unsigned)want;
@@ -98,12 +99,9 @@ extern "C" int chisel_hip_merge_map(chisel_hip_map *dst, chisel_hip_map *src, co
             }
         if (!(worst <= 1e-4)) return fail(CHISEL_HIP_ERR_INVALID, "chisel_hip_merge_map: the rotation part of src_to_dst is not a rotation (max |R^T R - I| > 1e-4)");
     }
-    SETTLE(dst);
-    SETTLE(src);
-    HIP_TRY(hipSetDevice(dst->device));
-    int rc = check_mesh_totals(dst);  // a recompute in flight reads the voxels as they are
+    int rc = rewrite_begin(dst);
     if (rc) return rc;
-    rc = check_mesh_totals(src);
+    rc = rewrite_begin(src);  // (the source is only read; the same holds for it)
     if (rc) return rc;
 
     // ---- the candidates (read-only for both maps)
@@ -127,7 +125,7 @@ extern "C" int chisel_hip_merge_map(chisel_hip_map *dst, chisel_hip_map *src, co
         HIP_TRY(hipMemsetAsync(G.stats, 0, MS_WORDS * sizeof(unsigned long long), dst->stream));
         hipLaunchKernelGGL(merge_candidates_kernel, dim3((src->view.committed + 255) / 256), dim3(256), 0, dst->stream, src->view, G, T, edge);
         hipLaunchKernelGGL(merge_classify_kernel, dim3(G.table_capacity / 2 / 256), dim3(256), 0, dst->stream, dst->view, G);
-        hipLaunchKernelGGL(merge_report_kernel, dim3(1), dim3(1), 0, dst->stream, G, O.host.dev());
+        hipLaunchKernelGGL(report_words_kernel<int>, dim3(1), dim3(1), 0, dst->stream, (const int *)G.ctl, O.host.dev(), MG_INTS);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(dst->stream));  // the one wait of a merge
         note_stream_idle(dst);
@@ -173,12 +171,13 @@ extern "C" int chisel_hip_merge_map(chisel_hip_map *dst, chisel_hip_map *src, co
     const MeshParams P = mesh_params(dst);
     FOR_CHUNK_SIZE(dst->N, launch_merge_gather<N>(dst, src, P, G, T, n_unique));
     HIP_TRY(hipGetLastError());
-    dst->mesh_mark_needed = true;  // (slots dirtied without their neighbourhoods listed: the next recompute runs mesh_mark_kernel)
-    HIP_TRY(note_map_mutation(dst));
+    rc = rewrite_end(dst);
+    if (rc) return rc;
     rc = release_source();
     if (rc) return rc;
     if (!stats) return CHISEL_HIP_OK;
-    hipLaunchKernelGGL(merge_stats_kernel, dim3(1), dim3(1), 0, dst->stream, G, reinterpret_cast<unsigned long long *>(O.host.dev() + 8));
+    hipLaunchKernelGGL(report_words_kernel<unsigned long long>, dim3(1), dim3(1), 0, dst->stream, (const unsigned long long *)G.stats,
+                       reinterpret_cast<unsigned long long *>(O.host.dev() + 8), MS_WORDS);
     HIP_TRY(hipGetLastError());
     rc = check_device_error(dst);  // waits
     if (rc) return rc;

@@ -19,11 +19,11 @@
 // wait between them:
 //   deintegrate_list_kernel      one thread per committed slot: the resident chunks whose bounding sphere reaches into the image pyramid,
 //                                compacted into a list, one append per wave
-//   deintegrate_apply_kernel<N>  a fixed grid of workgroups strides over the list (its length is read from the device): the rule above,
-//                                then the chunk's bookkeeping
+//   deintegrate_apply_kernel<N>  a fixed grid of workgroups strides over the list (its length is read from the device; the chunk pass
+//                                of kernels_rewrite.h): the rule above, then the chunk's bookkeeping
 #pragma once
-#include "chisel_device.h"
-#include "deintegrate_host.h"
+#include "host_checks.h"
+#include "kernels_rewrite.h"
 
 namespace chisel_hip {
 
@@ -93,8 +93,8 @@ __device__ inline bool deintegrate_select(const DeintegrateFrame &F, float cx, f
     return true;
 }
 
-// One workgroup per listed chunk at a time; a lane owns 4 consecutive x voxels (the map's lane layout: 16-byte accesses of sdf and wgt),
-// quads q = thread, thread + 256, ...  The depth image is gathered directly.
+// A fixed grid strides over the list, one workgroup per listed chunk at a time, as the chunk pass of kernels_rewrite.h.  The depth image
+// is gathered directly.
 template <int N>
 __global__ __launch_bounds__(256) void deintegrate_apply_kernel(MapView M, DeintegrateView G, DeintegrateFrame F) {
     constexpr int V = N * N * N;
@@ -107,66 +107,44 @@ __global__ __launch_bounds__(256) void deintegrate_apply_kernel(MapView M, Deint
         unpack_id(M.slot_key[slot], idx, idy, idz);
         if (threadIdx.x == 0) s_upd = s_clr = s_skip = s_signs = s_live = 0u;
         __syncthreads();
-        const float ox = (float)(N * idx) * F.res, oy = (float)(N * idy) * F.res, oz = (float)(N * idz) * F.res;
+        const ChunkCentres<N> C(F.res, F.half_res, idx, idy, idz);
         const size_t base = (size_t)slot * V;
         unsigned n_upd = 0, n_clr = 0, n_skip = 0;
         bool pos = false, neg = false;
         for (int q = threadIdx.x; q < V / 4; q += 256) {
-            const int v0 = 4 * q, x0 = v0 % N, y = (v0 / N) % N, z = v0 / (N * N);
-            const float cy = ((float)y * F.res + F.half_res) + oy, cz = ((float)z * F.res + F.half_res) + oz;
-            float4 s4, w4;
-            bool loaded = false, changed = false;
-            float *sv = &s4.x, *wv = &w4.x;
+            const QuadIndex<N> Q(q);
+            const float cy = C.y(Q.y), cz = C.z(Q.z);
+            VoxelQuad<false> vox;
+            bool changed = false;
 #pragma unroll
             for (int j = 0; j < 4; j++) {
-                const float cx = ((float)(x0 + j) * F.res + F.half_res) + ox;
                 float sd, wu;
-                if (!deintegrate_select(F, cx, cy, cz, sd, wu)) continue;
-                if (!loaded) {  // (most quads of most listed chunks lie outside the band: the voxels are read on demand)
-                    s4 = *reinterpret_cast<const float4 *>(M.sdf + base + v0);
-                    w4 = *reinterpret_cast<const float4 *>(M.wgt + base + v0);
-                    loaded = true;
-                }
-                const float w = wv[j];
+                if (!deintegrate_select(F, C.x(Q.x0 + j), cy, cz, sd, wu)) continue;
+                vox.need(M, base, Q.v0);  // (most quads of most listed chunks lie outside the band)
+                const float w = vox.weight(j);
                 if (!(w > 0.0f)) {
                     n_skip++;
                     continue;
                 }
                 const float w2 = w - wu;
                 if (!(w2 > w * 0x1p-16f)) {
-                    sv[j] = 99999.0f;  // DistVoxel::Reset (DistVoxel.cpp:27-31)
-                    wv[j] = 0.0f;
+                    vox.sdf(j) = 99999.0f;  // DistVoxel::Reset (DistVoxel.cpp:27-31)
+                    vox.weight(j) = 0.0f;
                     n_clr++;
                 } else {
-                    sv[j] = (w * sv[j] - wu * sd) / w2;
-                    wv[j] = w2;
+                    vox.sdf(j) = (w * vox.sdf(j) - wu * sd) / w2;
+                    vox.weight(j) = w2;
                     n_upd++;
-                    if (w2 > 0.5f) {
-                        if (sv[j] < 0.0f) neg = true;
-                        else pos = true;
-                    }
+                    note_sign(vox.sdf(j), w2, pos, neg);
                 }
                 changed = true;
             }
-            if (changed) {
-                *reinterpret_cast<float4 *>(M.sdf + base + v0) = s4;
-                *reinterpret_cast<float4 *>(M.wgt + base + v0) = w4;
-            }
+            vox.store(M, base, Q.v0, changed, false);
         }
-        // the chunk's figures: across the wave first, then one LDS atomic per wave
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            n_upd += __shfl_down(n_upd, o);
-            n_clr += __shfl_down(n_clr, o);
-            n_skip += __shfl_down(n_skip, o);
-        }
-        const unsigned signs = (__any(pos) ? SUM_POS : 0u) | (__any(neg) ? SUM_NEG : 0u);
-        if ((threadIdx.x & 63) == 0) {
-            if (n_upd) atomicAdd(&s_upd, n_upd);
-            if (n_clr) atomicAdd(&s_clr, n_clr);
-            if (n_skip) atomicAdd(&s_skip, n_skip);
-            if (signs) atomicOr(&s_signs, signs);
-        }
+        tally_count(n_upd, &s_upd);
+        tally_count(n_clr, &s_clr);
+        tally_count(n_skip, &s_skip);
+        tally_signs(pos, neg, &s_signs);
         __syncthreads();
         const bool touched = (s_upd | s_clr) != 0u;  // block-uniform
         if (touched) {
@@ -182,10 +160,7 @@ __global__ __launch_bounds__(256) void deintegrate_apply_kernel(MapView M, Deint
         if (threadIdx.x == 0) {
             t_skip += s_skip;
             if (touched) {
-                // what integrate_kernel's epilogue leaves for a chunk it updated; the 27-neighbourhood joins the job list through
-                // mesh_mark_kernel at the next recompute (the host sets mesh_mark_needed)
-                mark_slot_dirty(M, slot);
-                if (s_signs) atomicOr(&slot_summary(M)[slot], s_signs);
+                note_slot_updated(M, slot, s_signs);
                 t_touched++;
                 t_upd += s_upd;
                 t_clr += s_clr;
@@ -207,11 +182,6 @@ __global__ __launch_bounds__(256) void deintegrate_apply_kernel(MapView M, Deint
         if (t_clr) atomicAdd(&G.stats[DS_CLEARED], t_clr);
         if (t_skip) atomicAdd(&G.stats[DS_SKIPPED], t_skip);
     }
-}
-
-// the stats into pinned memory (one thread)
-__global__ void deintegrate_report_kernel(DeintegrateView G, unsigned long long *host_words) {
-    for (int i = 0; i < DS_WORDS; i++) host_words[i] = G.stats[i];
 }
 
 }  // namespace chisel_hip

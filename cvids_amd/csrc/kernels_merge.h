@@ -15,14 +15,16 @@
 //                             the very fp32 matrix the gather applies, so the argument does not depend on how good a rotation it is),
 //                             its bounding box padded, the chunk ids the box meets entered ONCE into a scratch key table -> unique list
 //   merge_classify_kernel     one thread per listed id: its slot in the destination, or "absent"; the absent ones are counted
-//   (the host reads the two counts here -- the one wait of a merge -- and sizes the pool: a fixed pool that cannot take the absent ids
+//   (the host reads the two counts here, through report_words_kernel -- the one wait of a merge -- and sizes the pool: a fixed pool that cannot take the absent ids
 //    refuses before anything is created)
 //   merge_create_kernel       one thread per absent id: create_chunk (safe for concurrent DISTINCT keys: the list is unique)
-//   merge_gather_kernel<N, COLOR>  one workgroup per listed id: the update above, then the chunk's bookkeeping -- or, for a chunk this
-//                             merge created and did not touch, its removal (it still holds default voxels: nothing was stored)
+//   merge_gather_kernel<N, COLOR>  one workgroup per listed id (the chunk pass of kernels_rewrite.h): the update above, then the chunk's
+//                             bookkeeping -- or, for a chunk this merge created and did not touch, its removal (it still holds default
+//                             voxels: nothing was stored)
 #pragma once
 #include "kernels_integrate.h"
 #include "kernels_render.h"
+#include "kernels_rewrite.h"
 
 namespace chisel_hip {
 
@@ -115,13 +117,6 @@ __global__ __launch_bounds__(256) void merge_classify_kernel(MapView D, MergeVie
     G.slots[i] = slot;
     if (slot < 0) atomicAdd(&G.ctl[MG_ABSENT], 1);
 }
-// ... and what the host reads of it (one thread): the control words into pinned memory
-__global__ void merge_report_kernel(MergeView G, int *host_words) {
-    for (int i = 0; i < MG_INTS; i++) host_words[i] = G.ctl[i];
-}
-__global__ void merge_stats_kernel(MergeView G, unsigned long long *host_words) {
-    for (int i = 0; i < MS_WORDS; i++) host_words[i] = G.stats[i];
-}
 
 __global__ __launch_bounds__(256) void merge_create_kernel(const MapView *__restrict__ Dc, MergeView G, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -132,9 +127,9 @@ __global__ __launch_bounds__(256) void merge_create_kernel(const MapView *__rest
     G.slots[i] = slot >= 0 ? (slot | MERGE_CREATED) : -1;
 }
 
-// One workgroup per listed destination chunk; a lane owns 4 consecutive x voxels (the map's lane layout: 16-byte accesses of sdf, wgt and
-// rgbw on the destination side), quads q = thread, thread + 256, ...  The source side is a gather: the lane keeps the source chunk it was
-// last in (render_locate's cix ... cslot), so a hash probe is paid when a voxel's position enters another source chunk, not per voxel.
+// One workgroup per listed destination chunk, as the chunk pass of kernels_rewrite.h.  The source side is a gather: the lane keeps the
+// source chunk it was last in (render_locate's cix ... cslot), so a hash probe is paid when a voxel's position enters another source
+// chunk, not per voxel.
 template <int N, bool COLOR>
 __global__ __launch_bounds__(256) void merge_gather_kernel(MapView D, MapView S, MeshParams P, MergeView G, MergeTransform T, int n) {
     constexpr int V = N * N * N;
@@ -149,22 +144,19 @@ __global__ __launch_bounds__(256) void merge_gather_kernel(MapView D, MapView S,
     unpack_id(G.list[item], idx, idy, idz);
     if (threadIdx.x == 0) s_upd = s_col = s_signs = 0u;
     __syncthreads();
-    const f3v origin = mk3((float)(N * idx) * P.res, (float)(N * idy) * P.res, (float)(N * idz) * P.res);
+    const ChunkCentres<N> C(P.res, P.half_res, idx, idy, idz);
     const size_t base = (size_t)slot * V;
     int cix = 0, ciy = 0, ciz = 0, cslot = -2;
     unsigned n_upd = 0, n_col = 0;
     bool pos = false, neg = false;
     for (int q = threadIdx.x; q < V / 4; q += 256) {
-        const int v0 = 4 * q, x0 = v0 % N, y = (v0 / N) % N, z = v0 / (N * N);
-        const float cy = ((float)y * P.res + P.half_res) + origin.y, cz = ((float)z * P.res + P.half_res) + origin.z;
-        float4 s4, w4;
-        uint4 c4 = make_uint4(0u, 0u, 0u, 0u);
-        bool loaded = false, touched = false, painted = false;
-        float *sv = &s4.x, *wv = &w4.x;
-        unsigned *cv = &c4.x;
+        const QuadIndex<N> Q(q);
+        const float cy = C.y(Q.y), cz = C.z(Q.z);
+        VoxelQuad<COLOR> vox;
+        bool touched = false, painted = false;
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            const float cx = ((float)(x0 + j) * P.res + P.half_res) + origin.x;
+            const float cx = C.x(Q.x0 + j);
             const f3v p = mk3(((T.m[0] * cx + T.m[1] * cy) + T.m[2] * cz) + T.m[3], ((T.m[4] * cx + T.m[5] * cy) + T.m[6] * cz) + T.m[7],
                               ((T.m[8] * cx + T.m[9] * cy) + T.m[10] * cz) + T.m[11]);
             if (!finite3(p)) continue;
@@ -173,57 +165,34 @@ __global__ __launch_bounds__(256) void merge_gather_kernel(MapView D, MapView S,
             const float w = S.wgt[off];
             if (!((double)w > 1e-12)) continue;
             const float s = S.sdf[off];
-            if (!loaded) {  // (most lanes of most chunks of a rotated map meet no source voxel: the destination is read on demand)
-                s4 = *reinterpret_cast<const float4 *>(D.sdf + base + v0);
-                w4 = *reinterpret_cast<const float4 *>(D.wgt + base + v0);
-                if (COLOR) c4 = *reinterpret_cast<const uint4 *>(D.rgbw + base + v0);
-                loaded = true;
-            }
-            dist_integrate(sv[j], wv[j], s, w);
+            vox.need(D, base, Q.v0);  // (most lanes of most chunks of a rotated map meet no source voxel)
+            dist_integrate(vox.sdf(j), vox.weight(j), s, w);
             touched = true;
             n_upd++;
-            if (wv[j] > 0.5f) {
-                if (sv[j] < 0.0f) neg = true;
-                else pos = true;
-            }
+            note_sign(vox.sdf(j), vox.weight(j), pos, neg);
             if (COLOR) {
                 const uchar4 sc = S.rgbw[off];
                 if (sc.w > 0) {
+                    unsigned &c = vox.rgbw(j);
                     uchar4 dc;
-                    dc.x = (uint8_t)(cv[j] & 0xffu); dc.y = (uint8_t)((cv[j] >> 8) & 0xffu); dc.z = (uint8_t)((cv[j] >> 16) & 0xffu); dc.w = (uint8_t)(cv[j] >> 24);
+                    dc.x = (uint8_t)(c & 0xffu); dc.y = (uint8_t)((c >> 8) & 0xffu); dc.z = (uint8_t)((c >> 16) & 0xffu); dc.w = (uint8_t)(c >> 24);
                     dc = color_integrate(dc, sc.x, sc.y, sc.z, sc.w);
-                    cv[j] = (unsigned)dc.x | ((unsigned)dc.y << 8) | ((unsigned)dc.z << 16) | ((unsigned)dc.w << 24);
+                    c = (unsigned)dc.x | ((unsigned)dc.y << 8) | ((unsigned)dc.z << 16) | ((unsigned)dc.w << 24);
                     painted = true;
                     n_col++;
                 }
             }
         }
-        if (touched) {
-            *reinterpret_cast<float4 *>(D.sdf + base + v0) = s4;
-            *reinterpret_cast<float4 *>(D.wgt + base + v0) = w4;
-        }
-        if (COLOR && painted) *reinterpret_cast<uint4 *>(D.rgbw + base + v0) = c4;
+        vox.store(D, base, Q.v0, touched, painted);
     }
-    // the chunk's figures: across the wave first, then one LDS atomic per wave
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        n_upd += __shfl_down(n_upd, o);
-        n_col += __shfl_down(n_col, o);
-    }
-    const unsigned signs = (__any(pos) ? SUM_POS : 0u) | (__any(neg) ? SUM_NEG : 0u);
-    if ((threadIdx.x & 63) == 0) {
-        if (n_upd) atomicAdd(&s_upd, n_upd);
-        if (n_col) atomicAdd(&s_col, n_col);
-        if (signs) atomicOr(&s_signs, signs);
-    }
+    tally_count(n_upd, &s_upd);
+    tally_count(n_col, &s_col);
+    tally_signs(pos, neg, &s_signs);
     __syncthreads();
     if (threadIdx.x != 0) return;
     const unsigned upd = s_upd;
     if (upd) {
-        // what integrate_kernel's epilogue leaves for a chunk it updated; the 27-neighbourhood joins the job list through
-        // mesh_mark_kernel at the next recompute (the host sets mesh_mark_needed)
-        mark_slot_dirty(D, slot);
-        if (s_signs) atomicOr(&slot_summary(D)[slot], s_signs);
+        note_slot_updated(D, slot, s_signs);
         unsigned long long *row = D.block_counters + (size_t)(blockIdx.x & (INTEGRATE_MAX_GRID - 1)) * 16;
         atomicAdd(&row[CHISEL_HIP_CNT_SDF], (unsigned long long)upd);
         if (s_col) atomicAdd(&row[CHISEL_HIP_CNT_COL], (unsigned long long)s_col);

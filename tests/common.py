@@ -67,3 +67,48 @@ def triangle_multiset(vertices, decimals=5):
         k = np.where(less, j, k)
     tri = np.ascontiguousarray(v[rows[:, None], (k[:, None] + np.arange(3)) % 3].reshape(-1, 9))
     return np.sort(tri.view(np.dtype((np.void, 72))).ravel()).tobytes()
+
+
+def compare_meshes(om, gm, color):
+    """the oracle's meshes against the map's: the same chunk ids, every array bit for bit -> (chunks, vertices)"""
+    oids = sorted(map(tuple, om.mesh_ids().tolist()))
+    gids = sorted(map(tuple, gm.GetMeshIDs().tolist()))
+    assert oids == gids, "mesh id sets differ: %d vs %d" % (len(oids), len(gids))
+    nv = 0
+    for cid in oids:
+        a, b = om.get_mesh(cid), gm.GetMesh(cid)
+        for key in ("vertices", "normals", "grids") + (("colors",) if color else ()):
+            x, y = np.asarray(a[key]), np.asarray(b[key])
+            assert x.shape == y.shape, "chunk %s %s: %s vs %s" % (cid, key, x.shape, y.shape)
+            assert np.array_equal(x.view(np.uint32), y.view(np.uint32)), "chunk %s: %s differ (max %g)" % (
+                cid, key, np.abs(x - y).max() if x.size else 0)
+        assert triangle_multiset(a["vertices"]) == triangle_multiset(b["vertices"])
+        nv += len(a["vertices"])
+    return len(oids), nv
+
+
+def same_bits(got, want, what):
+    """NaN masks equal, uint32 views equal elsewhere, no pixel left out"""
+    assert got.shape == want.shape and got.dtype == want.dtype == np.float32
+    gn, wn = np.isnan(got), np.isnan(want)
+    assert np.array_equal(gn, wn), "%s: NaN masks differ at %d places" % (what, int((gn != wn).sum()))
+    g, w = got.view(np.uint32)[~gn], want.view(np.uint32)[~wn]
+    assert np.array_equal(g, w), "%s: %d of %d values differ in their bits (max |d| %g)" % (
+        what, int((g != w).sum()), g.size, float(np.abs(got[~gn].astype(np.float64) - want[~wn].astype(np.float64)).max()))
+
+
+def upload(gm, field):
+    """a field (dict id -> (sdf, w, rgbw)) into a map, chunk by chunk; the colours only where the map keeps any"""
+    for cid, (s, w, c) in field.items():
+        gm.AddChunk(cid, s, w, c if gm.use_color else None)
+
+
+def fields_of(gm, N):
+    """Chisel.fields() with a zero colour array where the map has none, so that both kinds compare alike"""
+    return {cid: (s, w, c if c is not None else np.zeros((N ** 3, 4), np.uint8)) for cid, (s, w, c) in gm.fields().items()}
+
+
+def free_bytes():
+    import torch
+    torch.cuda.synchronize(0)
+    return torch.cuda.mem_get_info(0)[0]

@@ -1,13 +1,14 @@
-// Stand-alone check of cvids_amd/csrc/deintegrate_host.h, built with -fsanitize=address,undefined and run on the CPU by
-// tests/test_deintegrate_host.py: the planes the list kernel rejects chunks by must keep every chunk that holds a voxel the per-voxel
+// Stand-alone check of cvids_amd/csrc/host_checks.h, built with -fsanitize=address,undefined and run on the CPU by
+// tests/test_host_checks.py: the planes the list kernel rejects chunks by must keep every chunk that holds a voxel the per-voxel
 // rule can select (a voxel that projects onto the image in front of the camera, in the kernel's own fp32 arithmetic), for ordinary
-// and for hostile cameras and poses; and the refusals must say no to what the header says they refuse.
+// and for hostile cameras and poses; and the refusals -- the image check the alignment entries share with de-integration, and
+// de-integration's own -- must say no to what the header says they refuse.
 #include <initializer_list>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include "deintegrate_host.h"
+#include "host_checks.h"
 
 using namespace chisel_hip;
 
@@ -89,6 +90,16 @@ int main() {
     float depth[4] = {1, 1, 1, 1}, pose[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
     const float inf = INFINITY, nan = NAN;
     int bad = 0;
+    // the image check on its own, as the alignment entries call it: its verdicts, and that de-integration's refusal gives the same ones
+    struct Image { const float *depth; int W, H; bool refused; };
+    const Image images[] = {{depth, 2, 2, false}, {depth, 1, 1, false}, {depth, 46340, 46341, false}, {depth, INT32_MAX, 1, false},
+                            {nullptr, 2, 2, true}, {depth, 0, 2, true}, {depth, 2, 0, true}, {depth, -3, -3, true}, {depth, INT32_MIN, 1, true},
+                            {depth, 46341, 46341, true}, {depth, 1 << 16, 1 << 15, true}, {depth, INT32_MAX, INT32_MAX, true}};
+    for (const Image &I : images) {
+        const char *why = frame_image_refusal(I.depth, I.W, I.H);
+        bad += (why != nullptr) != I.refused;
+        bad += why != deintegrate_refusal(I.depth, I.W, I.H, pose, 1, 1, 1, 1, true, true, 4);  // (the same literal, or both null)
+    }
     bad += deintegrate_refusal(depth, 2, 2, pose, 1, 1, 1, 1, true, true, 4) != nullptr;
     bad += deintegrate_refusal(depth, 2, 2, pose, 1, 1, 1, 1, false, false, 0) != nullptr;
     bad += deintegrate_refusal(nullptr, 2, 2, pose, 1, 1, 1, 1, true, true, 4) == nullptr;

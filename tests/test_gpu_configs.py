@@ -14,8 +14,7 @@ import numpy as np
 import pytest
 
 from cvids_amd import synth
-from tests.common import compare_fields, make_frames, small_camera
-from tests.test_gpu_mesh import _compare_meshes
+from tests.common import compare_fields, compare_meshes, make_frames, small_camera
 from tests.test_gpu_parity import _mk
 
 pytestmark = pytest.mark.gpu
@@ -98,7 +97,7 @@ def test_config3_full_size_voxels_and_meshes(oracle_mod):
                           [(c_dev, frames[i][1], cam) for i in range(lo, lo + 10)])
         om.update_meshes(force=True)
         gm.UpdateMeshes(force=True)
-        n_meshes, n_vertices = _compare_meshes(om, gm, True)
+        n_meshes, n_vertices = compare_meshes(om, gm, True)
         assert n_meshes > 200 and n_vertices > 100000, (n_meshes, n_vertices)
     gc = gm.counters()
     for k in tot_o:
@@ -244,7 +243,7 @@ def test_config5_hd_half_centimetre_against_the_oracle(oracle_mod):
     assert gm.NumChunks() == om.num_chunks() and gm.NumChunks() > 150
     om.update_meshes(force=True)
     gm.UpdateMeshes(force=True)
-    n_meshes, n_vertices = _compare_meshes(om, gm, True)
+    n_meshes, n_vertices = compare_meshes(om, gm, True)
     assert n_meshes > 100 and n_vertices > 100000, (n_meshes, n_vertices)
     gm.close()
 

@@ -9,8 +9,8 @@ import pytest
 
 from tests import deintegrate_restated as dr
 from tests import merge_restated as mr
-from tests.test_gpu_merge import fields_of, free_bytes, upload
-from tests.test_gpu_mesh import _compare_meshes
+from tests.common import compare_meshes as _compare_meshes
+from tests.common import fields_of, free_bytes, upload
 
 pytestmark = pytest.mark.gpu
 MAX_CHUNKS = {8: 4096, 16: 4096, 32: 1024}

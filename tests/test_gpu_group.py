@@ -10,8 +10,7 @@ import numpy as np
 import pytest
 
 from cvids_amd import synth
-from tests.common import compare_fields, make_frames, small_camera
-from tests.test_gpu_mesh import _compare_meshes
+from tests.common import compare_fields, compare_meshes, make_frames, small_camera
 from tests.test_gpu_parity import _mk
 
 pytestmark = pytest.mark.gpu
@@ -47,7 +46,7 @@ def test_group_equals_oracle_and_single_map(oracle_mod, tmp_path, n_shards):
         om.update_meshes(force=True)
         single.UpdateMeshes(force=True)
         grp.UpdateMeshes(force=True)
-        _compare_meshes(om, grp, True)
+        compare_meshes(om, grp, True)
     # voxels, counters, listings
     compare_fields(om.fields(), grp.fields(), om.V, True, what="group of %d" % n_shards)
     assert grp.NumChunks() == om.num_chunks() == single.NumChunks()
@@ -202,7 +201,7 @@ def test_group_workers_sleep_and_wake_between_calls(oracle_mod):
         assert grp.NumChunks() == single.NumChunks()
         time.sleep(pause)
     compare_fields(om.fields(), grp.fields(), om.V, True, what="group with sleeping workers")
-    _compare_meshes(om, grp, True)
+    compare_meshes(om, grp, True)
     cg, cs = grp.counters(), single.counters()
     for k in ("sdf", "col", "col_sat", "probe", "carved", "new_chunks", "updated_chunks", "frames"):
         assert cg[k] == cs[k], (k, cg[k], cs[k])

@@ -9,8 +9,8 @@ import pytest
 from cvids_amd import synth
 from tests import merge_restated as mr
 from tests import voxel_fields as vf
-from tests.common import compare_fields, small_camera
-from tests.test_gpu_mesh import _compare_meshes
+from tests.common import compare_fields, fields_of, free_bytes, small_camera, upload
+from tests.common import compare_meshes as _compare_meshes
 
 pytestmark = pytest.mark.gpu
 MAX_CHUNKS = 512
@@ -22,18 +22,8 @@ def new_map(N, res, color=True, max_chunks=MAX_CHUNKS, **kw):
     return ch.Chisel((N, N, N), res, color, max_chunks=max_chunks, **kw)
 
 
-def upload(gm, field):
-    for cid, (s, w, c) in field.items():
-        gm.AddChunk(cid, s, w, c if gm.use_color else None)
-
-
 def no_colour(field):
     return {cid: (s, w, np.zeros_like(c)) for cid, (s, w, c) in field.items()}
-
-
-def fields_of(gm, N):
-    """Chisel.fields() with a zero colour array where the map has none, so that both kinds compare alike"""
-    return {cid: (s, w, c if c is not None else np.zeros((N ** 3, 4), np.uint8)) for cid, (s, w, c) in gm.fields().items()}
 
 
 def run_case(N, name, kind, dst_color=True, src_color=True, **dst_kw):
@@ -258,12 +248,6 @@ def test_refusals_leave_both_maps_alone():
 
 
 # ---- g. lifetime --------------------------------------------------------------------------------------------------------------------------
-def free_bytes():
-    import torch
-    torch.cuda.synchronize(0)
-    return torch.cuda.mem_get_info(0)[0]
-
-
 def test_merge_cycles_return_their_memory():
     """tests/test_gpu_lifetime.py's pattern: two maps created, merged and destroyed four times; the free device memory after the first
     cycle against that after the fourth, within half the footprint of one map's voxel pool.  And a second merge into the same

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from cvids_amd import synth
-from tests.common import make_frames, small_camera, triangle_multiset
+from tests.common import compare_meshes, make_frames, small_camera
 from tests.test_gpu_parity import _mk
 
 pytestmark = pytest.mark.gpu
@@ -25,23 +25,6 @@ def _integrate(om, gm, integ, frames, cam, color_img):
             gm.IntegrateDepthScanColor(integ, depth, pose, cam, color_img, pose, cam)
 
 
-def _compare_meshes(om, gm, color):
-    oids = sorted(map(tuple, om.mesh_ids().tolist()))
-    gids = sorted(map(tuple, gm.GetMeshIDs().tolist()))
-    assert oids == gids, "mesh id sets differ: %d vs %d" % (len(oids), len(gids))
-    nv = 0
-    for cid in oids:
-        a, b = om.get_mesh(cid), gm.GetMesh(cid)
-        for key in ("vertices", "normals", "grids") + (("colors",) if color else ()):
-            x, y = np.asarray(a[key]), np.asarray(b[key])
-            assert x.shape == y.shape, "chunk %s %s: %s vs %s" % (cid, key, x.shape, y.shape)
-            assert np.array_equal(x.view(np.uint32), y.view(np.uint32)), "chunk %s: %s differ (max %g)" % (
-                cid, key, np.abs(x - y).max() if x.size else 0)
-        assert triangle_multiset(a["vertices"]) == triangle_multiset(b["vertices"])
-        nv += len(a["vertices"])
-    return len(oids), nv
-
-
 @pytest.mark.parametrize("scene,color", [("wall", False), ("sphere_room", True), ("box_room", True)])
 def test_mesh_parity(oracle_mod, scene, color):
     om, gm, integ = _mk(oracle_mod, 8, 0.05, color, max_chunks=8192)
@@ -50,14 +33,14 @@ def test_mesh_parity(oracle_mod, scene, color):
     _integrate(om, gm, integ, make_frames(scene, 4, 64, 48), cam, cimg)
     om.update_meshes(force=True)
     gm.UpdateMeshes(force=True)
-    n, nv = _compare_meshes(om, gm, color)
+    n, nv = compare_meshes(om, gm, color)
     assert n > 20 and nv > 3000
     assert len(gm.GetMeshesToUpdate()) == 0 and len(om.meshes_to_update()) == 0
     # second round: more frames, meshes of touched chunks are regenerated in place
     _integrate(om, gm, integ, make_frames(scene, 3, 64, 48, start=4), cam, cimg)
     om.update_meshes(force=True)
     gm.UpdateMeshes(force=True)
-    _compare_meshes(om, gm, color)
+    compare_meshes(om, gm, color)
 
 
 @pytest.mark.parametrize("N,res,W,H", [(16, 0.04, 96, 72), (32, 0.02, 64, 48)])
@@ -67,7 +50,7 @@ def test_mesh_chunk_sizes(oracle_mod, N, res, W, H):
     _integrate(om, gm, integ, make_frames("box_room", 3, W, H), cam, synth.render_color(W, H, 3))
     om.update_meshes(force=True)
     gm.UpdateMeshes(force=True)
-    n, nv = _compare_meshes(om, gm, True)
+    n, nv = compare_meshes(om, gm, True)
     assert n > 0 and nv > 0
 
 
@@ -111,7 +94,7 @@ def test_sharded_map_meshes_equal_the_unsharded_map(oracle_mod, n_shards, wait_f
         if wait_free:
             assert (st is None) if turn == 0 else (st[0] == (4 if turn == 2 else 0) and st[3] > 0 and st[4] > 0 and st[2] > 64)
             assert getattr(group, "wait_free_aborts", 0) == (1 if turn == 2 else 0)
-        n, nv = _compare_meshes(om, Union(), True)
+        n, nv = compare_meshes(om, Union(), True)
         assert n > 20 and nv > 3000
         assert [s_.NumChunks() for s_ in shards] == before  # ghosts dropped
         assert sum(before) == om.num_chunks()
@@ -211,7 +194,7 @@ def test_stream_with_keyframe_meshing_no_waits(oracle_mod):
         done += len(part)
     from tests.common import compare_fields
     compare_fields(om.fields(), gm.fields(), om.V, True)
-    n, nv = _compare_meshes(om, gm, True)
+    n, nv = compare_meshes(om, gm, True)
     assert n > 10 and nv > 1000
 
 
@@ -235,7 +218,7 @@ def test_recompute_that_outgrows_its_buffers(oracle_mod, monkeypatch):
         gm.UpdateMeshes(force=True)
     from tests.common import compare_fields
     compare_fields(om.fields(), gm.fields(), om.V, True)
-    n, nv = _compare_meshes(om, gm, True)
+    n, nv = compare_meshes(om, gm, True)
     assert n > 10 and nv > 1000
 
 
@@ -261,12 +244,12 @@ def test_integration_queued_behind_an_unseen_recompute_is_replayed(oracle_mod, m
         om.update_meshes(force=True)
         gm.UpdateMeshes(force=True)
         if lo == 10:
-            _compare_meshes(om, gm, True)  # (a reader in the middle: settles what is queued, then reads)
+            compare_meshes(om, gm, True)  # (a reader in the middle: settles what is queued, then reads)
     st = gm.launch_stats()
     assert st["behind_unseen_recompute"] >= 2 and st["replayed"] >= 2, st  # (steps 2 and 3; step 4 follows a reader, which settled everything)
     from tests.common import compare_fields
     compare_fields(om.fields(), gm.fields(), om.V, True)
-    n, nv = _compare_meshes(om, gm, True)
+    n, nv = compare_meshes(om, gm, True)
     assert n > 10 and nv > 1000
     # the same stream with the totals looked at before every launch gives the same map (and no replays)
     monkeypatch.setenv("CHISEL_HIP_DEFER_TOTALS", "0")
@@ -288,7 +271,7 @@ def test_mesh_color_lookup_near_origin(oracle_mod):
     _integrate(om, gm, integ, frames, cam, cimg)
     om.update_meshes(force=True)
     gm.UpdateMeshes(force=True)
-    _compare_meshes(om, gm, True)
+    compare_meshes(om, gm, True)
 
 
 def test_update_meshes_cadence_and_carved_mesh(oracle_mod):
@@ -304,11 +287,11 @@ def test_update_meshes_cadence_and_carved_mesh(oracle_mod):
         assert len(om.meshes_to_update()) == len(gm.GetMeshesToUpdate()), "call %d" % call
         if call == 0:
             assert len(gm.GetMeshIDs()) > 0
-            _compare_meshes(om, gm, False)
+            compare_meshes(om, gm, False)
             _integrate(om, gm, integ, [(np.full((48, 64), 2.4, np.float32), pose)] * 4, cam, None)
         if call == 5:
             assert len(gm.GetMeshesToUpdate()) > 0  # calls 1..9 do not recompute
-    _compare_meshes(om, gm, False)
+    compare_meshes(om, gm, False)
 
 
 def test_sdf_queries(oracle_mod):

@@ -5,7 +5,7 @@ crossing edge with a difference below 6.8e-5, no -0.0, no denormal, a few dozen 
 origin (DESIGN.md "What the mesh tests cover").  Here the same arrays go into the GPU map (Chisel.AddChunk) and into the oracle
 (OracleMap.put_chunk), the listed chunks are meshed on both sides (UpdateMeshesOf / recompute_meshes) and the meshes are held to the
 mesher's existing contract: identical id sets, vertices, normals, colours and grid entries equal as uint32, element for element
-(tests.test_gpu_mesh._compare_meshes).  Every condition on a field is asserted on the very field that is meshed, from the field and
+(tests.common.compare_meshes).  Every condition on a field is asserted on the very field that is meshed, from the field and
 the oracle's output alone; the GPU is never asked what a test covers.
 """
 import time
@@ -17,9 +17,7 @@ from cvids_amd import synth
 from tests import query_restated as qr
 from tests import render_restated as rr
 from tests import voxel_fields as vf
-from tests.common import compare_fields, small_camera
-from tests.test_gpu_mesh import _compare_meshes
-from tests.test_gpu_render import same_bits
+from tests.common import compare_fields, compare_meshes, same_bits, small_camera, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -33,11 +31,6 @@ def absent_ids(B, base):
     """ids that are not resident: next to the block, and far away"""
     b = np.asarray(base)
     return [tuple(int(v) for v in b + (B, 0, 0)), tuple(int(v) for v in b - (1, 1, 1)), tuple(int(v) for v in b + (500, -500, 500))]
-
-
-def upload(gm, field):
-    for cid, (s, w, c) in field.items():
-        gm.AddChunk(cid, s, w, c)
 
 
 def new_gpu_map(N, res):
@@ -116,7 +109,7 @@ def test_every_configuration_through_both_kernels(sides, oracle_mod, vertex_coun
     the partition cursors are nearest their limits"""
     field, ids, om, cubes, seconds = sides.oracle_side("dense", N, RES[N])
     gm = sides.gpu_side("dense", N, RES[N])
-    n, nv = _compare_meshes(om, gm, True)
+    n, nv = compare_meshes(om, gm, True)
     assert n == BLOCKS[N] ** 3
     total = triangle_totals(om, cubes, vertex_counts)
     assert 3 * total == nv and total > 2 * (BLOCKS[N] * N) ** 3, total
@@ -130,7 +123,7 @@ def test_thresholds(sides, oracle_mod, vertex_counts, N):
     origin as their cube: normals and colours from chunks far outside the job's neighbourhood), -0.0 and denormal corners"""
     field, ids, om, cubes, seconds = sides.oracle_side("thresholds", N, RES[N])
     gm = sides.gpu_side("thresholds", N, RES[N])
-    n, nv = _compare_meshes(om, gm, True)
+    n, nv = compare_meshes(om, gm, True)
     assert n == BLOCKS[N] ** 3
     total = triangle_totals(om, cubes, vertex_counts)
     assert 3 * total == nv and total > 0
@@ -147,7 +140,7 @@ def test_placement(sides, oracle_mod):
     for res, base in ((RES[N], (-2, -2, -2)), (RES[N], (1000, -1000, 37)), (1.0, (-1, -1, -1))):
         field, ids, om, _, _ = sides.oracle_side("thresholds", N, res, base)
         gm = sides.gpu_side("thresholds", N, res, base)
-        n, nv = _compare_meshes(om, gm, True)
+        n, nv = compare_meshes(om, gm, True)
         assert n == BLOCKS[N] ** 3 and nv > 0
         index = rr.VoxelIndex(field, N, res)
         verts = np.concatenate([om.get_mesh(cid)["vertices"] for cid in sorted(field)])
@@ -175,7 +168,7 @@ def test_in_place_twice(sides, oracle_mod):
             om.put_chunk(cid, s, w, c)
         gm.UpdateMeshesOf(ids)
         om.recompute_meshes(ids)
-        assert _compare_meshes(om, gm, True)[0] == B ** 3
+        assert compare_meshes(om, gm, True)[0] == B ** 3
     reseeded, emptied, same = (1, 1, 1), (0, 0, 0), (2, 2, 2)
     changes = {reseeded: other[reseeded], emptied: (field[emptied][0], np.zeros(N ** 3, np.float32), field[emptied][2]), same: field[same]}
     upload(gm, changes)
@@ -184,7 +177,7 @@ def test_in_place_twice(sides, oracle_mod):
     before = om.get_mesh(reseeded)["vertices"].copy()
     gm.UpdateMeshesOf(ids)
     om.recompute_meshes(ids)
-    assert _compare_meshes(om, gm, True)[0] == B ** 3
+    assert compare_meshes(om, gm, True)[0] == B ** 3
     assert before.tobytes() != om.get_mesh(reseeded)["vertices"].tobytes()
     for side in (om.get_mesh(emptied), gm.GetMesh(emptied)):
         assert len(side["vertices"]) == 0 and len(side["grids"]) == 0
@@ -210,7 +203,7 @@ def test_dense_recompute_that_outgrows_its_buffers(sides, oracle_mod, monkeypatc
         upload(gm, field)
         gm.set_profiling(True)
         gm.UpdateMeshesOf(ids)
-        assert _compare_meshes(om, gm, True)[0] == BLOCKS[N] ** 3
+        assert compare_meshes(om, gm, True)[0] == BLOCKS[N] ** 3
         steps[tiny] = gm.profile()["mesh"]["launches"]
         gm.close()
     print("profiled mesh steps: %d with buffers too small, %d without the switch" % (steps[True], steps[False]))
@@ -324,7 +317,7 @@ def test_dump_and_restore(sides, oracle_mod, tmp_path):
         for x, y, z in zip(a[cid], b[cid], field[cid]):
             assert x.tobytes() == y.tobytes() == z.tobytes(), cid
     g2.UpdateMeshesOf(ids)
-    assert _compare_meshes(om, g2, True)[0] == BLOCKS[N] ** 3
+    assert compare_meshes(om, g2, True)[0] == BLOCKS[N] ** 3
 
 
 # ---- i. surface on a chunk face, by integration -----------------------------------------------------------------------------------------
@@ -353,7 +346,7 @@ def test_surface_on_a_chunk_face(sides, oracle_mod):
     assert seen[2] > 1000 and seen[3] > 1000, seen
     om.update_meshes(force=True)
     gm.UpdateMeshes(force=True)
-    n, nv = _compare_meshes(om, gm, False)
+    n, nv = compare_meshes(om, gm, False)
     r = np.float32(res)
     top = (np.float32(N - 1) * r + r * np.float32(0.5)) + np.float32(N * 2) * r  # centroid of the chunk's last z-layer (ChunkManager.cpp:50-66)
     # the z-id-2 chunks in view, from the voxels alone: a cube of the max-z plane away from the chunk's x and y faces has its eight

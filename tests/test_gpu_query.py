@@ -1,6 +1,6 @@
 """chisel_hip_query_points and chisel_hip_cast_rays on the GPU against their definition (DESIGN.md "Querying points and rays").
 
-Every comparison is BIT FOR BIT over every element with equal NaN masks (same_bits of tests/test_gpu_render.py; integer outputs with
+Every comparison is BIT FOR BIT over every element with equal NaN masks (same_bits of tests/common.py; integer outputs with
 array_equal): against the numpy restatement (tests/query_restated.py) run over the map as GetChunkIDs / GetChunk read it back,
 against the single-point entries, chisel_hip_shade_vertices and chisel_hip_render_view.  A stated share only keeps a comparison from
 passing on an empty case.  The maps are built once and only read, but where a test changes them."""
@@ -13,12 +13,11 @@ from cvids_amd import synth
 from tests import query_restated as qr
 from tests import render_restated as rr
 from tests import test_gpu_render as tgr
-from tests.common import compare_fields
+from tests.common import compare_fields, same_bits
 
 pytestmark = pytest.mark.gpu
 W, H = tgr.W, tgr.H
 NEAR, FAR = tgr.NEAR, tgr.FAR
-same_bits = tgr.same_bits
 
 # scene, chunk edge, resolution, truncator, frames, carving, colour voxels, pose of "the map's own view"
 MAPS = [tgr.MAPS[0], tgr.MAPS[2], tgr.MAPS[3], tgr.MAPS[1]]

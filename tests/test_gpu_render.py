@@ -11,7 +11,7 @@ import pytest
 
 from cvids_amd import synth
 from tests import render_restated as rr
-from tests.common import compare_fields
+from tests.common import compare_fields, same_bits
 
 pytestmark = pytest.mark.gpu
 W, H = 160, 120
@@ -41,16 +41,6 @@ def gpu_map(scene, N, res, trunc, n_frames, carving=True, color=False, nan_fract
         else:
             gm.IntegrateDepthScan(integ, depth, pose, cam)
     return gm
-
-
-def same_bits(got, want, what):
-    """NaN masks equal, uint32 views equal elsewhere, no pixel left out"""
-    assert got.shape == want.shape and got.dtype == want.dtype == np.float32
-    gn, wn = np.isnan(got), np.isnan(want)
-    assert np.array_equal(gn, wn), "%s: NaN masks differ at %d places" % (what, int((gn != wn).sum()))
-    g, w = got.view(np.uint32)[~gn], want.view(np.uint32)[~wn]
-    assert np.array_equal(g, w), "%s: %d of %d values differ in their bits (max |d| %g)" % (
-        what, int((g != w).sum()), g.size, float(np.abs(got[~gn].astype(np.float64) - want[~wn].astype(np.float64)).max()))
 
 
 def check_depth(gm, index, pose, cam, step, what):
