@@ -666,6 +666,55 @@ class Chisel:
             self.IntegrateDepthScan(integrator, depth_image, new_extrinsic, camera)
         return out
 
+    def DeintegrateDepthScans(self, integrator, frames, color_rules=False, stats=True, collect=False):
+        """chisel_hip_deintegrate_batch: the frames -- a list of (depth, pose, camera) as IntegrateBatch takes them, numpy images or
+        torch CUDA tensors used in place, of any mix of sizes and cameras -- are taken out of the distance voxels in one call; the
+        map is left, bit for bit, as DeintegrateDepthScan on each of them in list order would leave it, and a voxel under several
+        frames of a launch set of 16 is read and written once.  -> what DeintegrateDepthScan returns, the six counts summed over the
+        frames ("chunks_emptied" and "emptied_ids": the chunks without any weight at the end, each once); collect=True hands those to
+        GarbageCollect.  stats=False: the call does not wait for its own end and returns None"""
+        self._use(integrator)
+        n = len(frames)
+        fa = (DepthFrame * max(n, 1))()
+        keep = []
+        for i, (d, p, cam) in enumerate(frames):
+            fa[i], k = depth_frame(d, p, cam)
+            keep.append(k)
+        if not stats:
+            assert not collect, "collect=True needs the ids, which stats=False does not wait for"
+            check(self.L.chisel_hip_deintegrate_batch(self.h, n, fa, int(bool(color_rules)), None, None, 0))
+            self._keep = keep
+            return None
+        st = capi.DeintegrateStats()
+        ids = np.zeros((max(1, self.NumChunks()), 3), np.int32)  # (no chunk is created: the resident ones bound the emptied ones)
+        check(self.L.chisel_hip_deintegrate_batch(self.h, n, fa, int(bool(color_rules)), C.byref(st), ids.ctypes.data_as(C.POINTER(C.c_int)), len(ids)))
+        self._keep = keep
+        out = {n: int(getattr(st, n)) for n, _ in capi.DeintegrateStats._fields_}
+        out["emptied_ids"] = ids[:min(out["chunks_emptied"], len(ids))].copy()
+        if collect and len(out["emptied_ids"]):
+            self.GarbageCollect(out["emptied_ids"])
+        return out
+
+    def ReintegrateDepthScans(self, integrator, frames, new_poses, colors=None, stats=True, collect=False):
+        """a stretch of trajectory whose poses were corrected after its keyframes were fused: DeintegrateDepthScans of `frames` (a
+        list of (depth, pose, camera), the poses they went in with), then IntegrateBatch of the same images at `new_poses`.  With
+        `colors` (a list of (color image, color camera), or of color images alone, which take the depth camera) the frames went in
+        through the colour rules and go back that way, each colour camera riding on the corrected depth pose.
+        All out, then all in: NOT the arithmetic of n calls of ReintegrateDepthScan, which take out and put back frame by frame --
+        the two orders round differently.  -> what DeintegrateDepthScans returns"""
+        assert len(new_poses) == len(frames) and (colors is None or len(colors) == len(frames))
+        out = self.DeintegrateDepthScans(integrator, frames, colors is not None, stats, collect)
+        again = [(d, p, cam) for (d, _, cam), p in zip(frames, new_poses)]
+        riding = None
+        if colors is not None:
+            riding = []
+            for c, p, (_, _, cam) in zip(colors, new_poses, frames):
+                image, ccam = c if isinstance(c, (tuple, list)) else (c, cam)
+                riding.append((image, p, ccam))
+        if again:
+            self.IntegrateBatch(integrator, again, riding)
+        return out
+
     def MemoryStatistics(self):
         """ChunkManager::PrintMemoryStatistics (ChunkManager.cpp:641-678) as numbers: the voxel census of Chunk::ComputeStatistics over
         the resident chunks, the weight sum, the bounds of the chunk boxes and the two memory figures the reference prints (it

@@ -395,6 +395,23 @@ struct chisel_hip_map {
         DeviceBuffer<unsigned long long> stats;
         PinnedBuffer<unsigned long long> host;                         // [DS_WORDS] where the stats reach the host
         DeintegrateView view{};                                        // (what the kernels take: copies of the pointers above)
+        // chisel_hip_deintegrate_batch: the (slot, frame mask) list | the stats and one list length per launch set | the frames' table
+        DeviceBuffer<int2> batch_list;
+        DeviceBuffer<unsigned long long> batch_words;                  // [DS_WORDS + launch sets]: zeroed by the call's one memset
+        DeviceBuffer<DeintegrateBatchEntry> batch_table;               // [frames of the call]
+        PinnedBuffer<unsigned long long> batch_host;                   // [DS_WORDS] where its stats reach the host
+        // The host side of a table's upload lives until the copy is over: a block is taken again once its event has passed, so that
+        // a call that waits for nothing can follow one whose copy is still queued.
+        struct TableUpload {
+            PinnedBuffer<DeintegrateBatchEntry> host;
+            size_t capacity = 0;                                       // entries
+            hipEvent_t copied = nullptr;
+            TableUpload() = default;
+            TableUpload(TableUpload &&o) noexcept : host(std::move(o.host)), capacity(o.capacity), copied(o.copied) { o.copied = nullptr; o.capacity = 0; }
+            TableUpload &operator=(TableUpload &&) = delete;
+            ~TableUpload() { if (copied) (void)hipEventDestroy(copied); }
+        };
+        std::vector<TableUpload> uploads;
     } deintegrate_mem;
     // profiling
     bool profiling = false;

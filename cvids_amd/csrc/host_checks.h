@@ -1,6 +1,7 @@
-// host_checks.h -- the host-side pieces of the side entries (chisel_hip_align_terms / _align_depth, chisel_hip_deintegrate_depth) that
-// call nothing of HIP (included by kernels_deintegrate.h and, on its own, by tests/host_checks_check.cpp, which runs them under the
-// address and undefined-behaviour sanitizers on the CPU): what the entries refuse about a frame's image, what de-integration refuses
+// host_checks.h -- the host-side pieces of the side entries (chisel_hip_align_terms / _align_depth, chisel_hip_deintegrate_depth / _batch)
+// that call nothing of HIP (included by kernels_deintegrate.h and, on its own, by tests/host_checks_check.cpp and
+// tests/host_checks_batch_check.cpp, which run them under the address and undefined-behaviour sanitizers on the CPU): what the entries
+// refuse about a frame's image, what de-integration refuses
 // about its other arguments, and the planes its list kernel rejects chunks by.
 #pragma once
 #include <math.h>
@@ -82,6 +83,26 @@ inline const char *deintegrate_refusal(const float *depth, int width, int height
     if (!isfinite(fx) || !isfinite(fy) || !isfinite(cx) || !isfinite(cy)) return "intrinsics that are not finite";
     if (max_ids < 0) return "max_ids < 0";
     if (want_ids && !want_stats) return "emptied_ids_xyz without stats (the count of the ids is reported there)";
+    return nullptr;
+}
+
+// what chisel_hip_deintegrate_batch refuses about its arguments other than the map, every frame looked at before anything is touched;
+// null = go on (n == 0 included).  *bad_frame: the index of the frame the refusal is about, -1 when it is about the call.  Frame:
+// chisel_hip_depth_frame (a template, so that this header goes on including nothing of the library's)
+template <class Frame>
+inline const char *deintegrate_batch_refusal(int n, const Frame *frames, bool want_stats, bool want_ids, int max_ids, int *bad_frame) {
+    *bad_frame = -1;
+    if (n < 0) return "n < 0";
+    if (n > 0 && !frames) return "null frames with n > 0";
+    if (max_ids < 0) return "max_ids < 0";
+    if (want_ids && !want_stats) return "emptied_ids_xyz without stats (the count of the ids is reported there)";
+    for (int i = 0; i < n; i++) {
+        const Frame &f = frames[i];
+        if (const char *why = deintegrate_refusal(f.depth, f.width, f.height, f.pose, f.fx, f.fy, f.cx, f.cy, want_stats, want_ids, max_ids)) {
+            *bad_frame = i;
+            return why;
+        }
+    }
     return nullptr;
 }
 

@@ -1,8 +1,9 @@
-// host_deintegrate.h -- chisel_hip_deintegrate_depth (included by chisel_hip.hip; the kernels and the definition: kernels_deintegrate.h,
+// host_deintegrate.h -- chisel_hip_deintegrate_depth and chisel_hip_deintegrate_batch (included by chisel_hip.hip; the kernels and the definition: kernels_deintegrate.h,
 // DESIGN.md 3.10).  Everything runs on the map's stream: the list kernel, then the apply kernel, whose fixed grid reads the list's length
 // from the device -- no host wait between them, and none at all when the caller asks for neither stats nor ids.  The scratch lives in the
 // map (chisel_hip_map::deintegrate_mem), is reused by the next call and freed with the map; a host image goes through the map's
-// staging buffer (stage_depth).  The frame it shares with the other entries that rewrite a map: host_rewrite.h; what it refuses about
+// staging buffer (stage_depth; the batch entry stages a launch set's host images side by side and keeps its per-frame constants in a
+// table on the device).  The frame it shares with the other entries that rewrite a map: host_rewrite.h; what it refuses about
 // its arguments, and the planes of the list kernel: host_checks.h.
 #pragma once
 
@@ -20,6 +21,45 @@ int ensure_scratch(chisel_hip_map *m, int max_ids) {
     if (rc) return rc;
     return grow_buffer(O.ids, (size_t)3 * max_ids, m->stream);
 }
+
+// chisel_hip_deintegrate_batch: room for one list entry per committed slot, the stats and a list length per launch set, `max_ids` ids, a
+// table entry per frame and the largest launch set's host images
+int ensure_batch_scratch(chisel_hip_map *m, int n, int n_sets, int max_ids, size_t stage_floats) {
+    chisel_hip_map::DeintegrateMemory &O = m->deintegrate_mem;
+    if (!O.batch_host) HIP_TRY(O.batch_host.alloc(DS_WORDS));
+    int rc = grow_buffer(O.batch_list, (size_t)std::max(m->view.committed, 1), m->stream);
+    if (!rc) rc = grow_buffer(O.batch_words, (size_t)DS_WORDS + (size_t)n_sets, m->stream);
+    if (!rc) rc = grow_buffer(O.batch_table, (size_t)n, m->stream);
+    if (!rc) rc = grow_buffer(O.ids, (size_t)3 * max_ids, m->stream);
+    if (!rc && stage_floats) rc = grow_buffer(m->frame_stage, stage_floats, m->stream);
+    return rc;
+}
+
+// a block of pinned memory for n table entries whose last upload is over (a new one when all are busy)
+int take_upload(chisel_hip_map *m, size_t n, chisel_hip_map::DeintegrateMemory::TableUpload **out) {
+    std::vector<chisel_hip_map::DeintegrateMemory::TableUpload> &U = m->deintegrate_mem.uploads;
+    chisel_hip_map::DeintegrateMemory::TableUpload *u = nullptr;
+    for (auto &c : U)
+        if (hipEventQuery(c.copied) == hipSuccess) {
+            u = &c;
+            break;
+        }
+    (void)hipGetLastError();  // (hipErrorNotReady is not an error)
+    if (!u) {
+        U.emplace_back();
+        u = &U.back();
+        HIP_TRY(hipEventCreateWithFlags(&u->copied, hipEventDisableTiming));
+    }
+    if (u->capacity < n) {
+        u->capacity = 0;
+        HIP_TRY(u->host.alloc(n));
+        u->capacity = n;
+    }
+    *out = u;
+    return CHISEL_HIP_OK;
+}
+
+inline size_t stage_floats_of(const chisel_hip_depth_frame &f) { return f.on_device ? 0 : (((size_t)f.width * f.height + 3) & ~(size_t)3); }  // (16-byte sections)
 
 }  // namespace deintegrate
 }  // namespace
@@ -83,6 +123,110 @@ extern "C" int chisel_hip_deintegrate_depth(chisel_hip_map *m, const chisel_hip_
     rc = check_device_error(m);  // the one wait
     if (rc) return rc;
     const volatile unsigned long long *res = O.host.get();
+    stats->chunks_tested = (int64_t)res[DS_TESTED];
+    stats->chunks_touched = (int64_t)res[DS_TOUCHED];
+    stats->chunks_emptied = (int64_t)res[DS_EMPTIED];
+    stats->voxels_updated = (int64_t)res[DS_UPDATED];
+    stats->voxels_cleared = (int64_t)res[DS_CLEARED];
+    stats->voxels_skipped = (int64_t)res[DS_SKIPPED];
+    const int64_t n_ids = std::min<int64_t>(stats->chunks_emptied, want_ids);
+    if (n_ids > 0) HIP_TRY(hipMemcpy(emptied_ids_xyz, O.ids.get(), (size_t)n_ids * 3 * sizeof(int), hipMemcpyDeviceToHost));
+    return CHISEL_HIP_OK;
+}
+
+// Many frames in one call: launch sets of at most KMAX frames, in order, two launches each, all on the map's stream with no host wait
+// between them.  One table of per-frame constants per call (a later call's upload is queued behind this call's kernels), one memset of
+// the stats and the sets' list lengths per call.
+extern "C" int chisel_hip_deintegrate_batch(chisel_hip_map *m, int n, const chisel_hip_depth_frame *frames, int color_rules, chisel_hip_deintegrate_stats *stats,
+                                            int *emptied_ids_xyz, int max_ids) {
+    const char *name = "chisel_hip_deintegrate_batch";
+    // ---- refusals: every frame is looked at before anything is touched
+    if (m && m->is_group) return fail(CHISEL_HIP_ERR_UNSUPPORTED, std::string(name) + " rewrites the voxels of all owners: a group's shards hold a part each, and ghost chunks would need a rule of their own");
+    if (!m) return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": null map");
+    if (m->cfg.n_shards > 1) return fail(CHISEL_HIP_ERR_UNSUPPORTED, std::string(name) + " rewrites the voxels of all owners: this map is one shard of several");
+    int bad_frame = -1;
+    if (const char *why = deintegrate_batch_refusal(n, frames, stats != nullptr, emptied_ids_xyz != nullptr, max_ids, &bad_frame))
+        return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": " + (bad_frame >= 0 ? "frame " + std::to_string(bad_frame) + ": " : std::string()) + why);
+    if (stats) *stats = chisel_hip_deintegrate_stats{0, 0, 0, 0, 0, 0};
+    if (n == 0) return CHISEL_HIP_OK;
+    int rc = rewrite_begin(m);
+    if (rc) return rc;
+    const int want_ids = emptied_ids_xyz ? max_ids : 0;
+    const int n_sets = (n + KMAX - 1) / KMAX;
+    size_t stage_floats = 0;  // the largest set's host images
+    bool any_host = false;
+    for (int s = 0; s < n_sets; s++) {
+        size_t sum = 0;
+        for (int i = s * KMAX; i < std::min(n, (s + 1) * KMAX); i++) sum += deintegrate::stage_floats_of(frames[i]);
+        stage_floats = std::max(stage_floats, sum);
+        any_host = any_host || sum != 0;
+    }
+    rc = deintegrate::ensure_batch_scratch(m, n, n_sets, want_ids, stage_floats);
+    if (rc) return rc;
+    chisel_hip_map::DeintegrateMemory &O = m->deintegrate_mem;
+    chisel_hip_map::DeintegrateMemory::TableUpload *up = nullptr;
+    rc = deintegrate::take_upload(m, (size_t)n, &up);
+    if (rc) return rc;
+
+    // ---- the table: a host image of set s has the s-th use of its place in the staging buffer
+    DeintegrateBatchEntry *T = up->host.get();
+    for (int s = 0; s < n_sets; s++) {
+        size_t at = 0;
+        for (int i = s * KMAX; i < std::min(n, (s + 1) * KMAX); i++) {
+            const chisel_hip_depth_frame &f = frames[i];
+            deintegrate_pyramid(f.pose, f.fx, f.fy, f.cx, f.cy, f.width, f.height, m->N, m->cfg.voxel_resolution, T[i].Y);
+            fill_camera(T[i].cam, f.pose, f.fx, f.fy, f.cx, f.cy, f.width, f.height);
+            T[i].depth = f.on_device ? f.depth : m->frame_stage.get() + at;
+            at += deintegrate::stage_floats_of(f);
+        }
+    }
+    rc = wait_for_input(m, m->stream);  // chisel_hip_wait_event / _order_map_after_stream: a device image is ready behind it
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(O.batch_table.get(), T, (size_t)n * sizeof(DeintegrateBatchEntry), hipMemcpyHostToDevice, m->stream));
+    HIP_TRY(hipEventRecord(up->copied, m->stream));
+
+    // ---- per set: its host images, then the two launches
+    DeintegrateBatchView G;
+    G.list = O.batch_list.get();
+    G.stats = O.batch_words.get();
+    G.emptied = want_ids ? O.ids.get() : nullptr;
+    G.max_ids = want_ids;
+    G.table = O.batch_table.get();
+    DeintegrateFrame F{};  // the call's constants; the camera and the image come from the table
+    F.trunc_kind = m->integ.truncator_kind;
+    F.trunc_param = m->integ.truncator_param;
+    F.weight = m->integ.weight;
+    F.res = m->cfg.voxel_resolution;
+    F.half_res = m->cfg.voxel_resolution * 0.5f;                                          // ChunkManager.cpp:52
+    F.diag = (float)(2.0 * ::sqrt((double)3.0f) * (double)m->cfg.voxel_resolution);       // ProjectionIntegrator.h:58,109
+    F.color_rules = color_rules ? 1 : 0;
+    F.max_depth = color_rules ? 100.0f : 50.0f;
+    HIP_TRY(hipMemsetAsync(G.stats, 0, ((size_t)DS_WORDS + (size_t)n_sets) * sizeof(unsigned long long), m->stream));
+    const unsigned list_grid = (unsigned)std::max(1, (m->view.committed + 255) / 256);
+    const unsigned grid = (unsigned)std::max(1, std::min(m->view.committed, DEINTEGRATE_GRID));
+    for (int s = 0; s < n_sets; s++) {
+        const int first = s * KMAX, count = std::min(n - first, KMAX);
+        for (int i = first; i < first + count; i++)
+            if (!frames[i].on_device)
+                HIP_TRY(hipMemcpyAsync(const_cast<float *>(T[i].depth), frames[i].depth, (size_t)frames[i].width * frames[i].height * sizeof(float), hipMemcpyHostToDevice, m->stream));
+        G.listed = G.stats + DS_WORDS + s;
+        hipLaunchKernelGGL(deintegrate_list_batch_kernel, dim3(list_grid), dim3(256), 0, m->stream, m->view, G, first, count);
+        FOR_CHUNK_SIZE(m->N, hipLaunchKernelGGL((deintegrate_apply_batch_kernel<N, deintegrate_batch_threads(N)>), dim3(grid), dim3(deintegrate_batch_threads(N)), 0, m->stream, m->view, G, F, first));
+    }
+    HIP_TRY(hipGetLastError());
+
+    // ---- the bookkeeping
+    rc = rewrite_end(m);
+    if (rc) return rc;
+    if (!stats) {
+        if (any_host) HIP_TRY(hipStreamSynchronize(m->stream));  // (the copies of the caller's images are over on return)
+        return CHISEL_HIP_OK;
+    }
+    hipLaunchKernelGGL(report_words_kernel<unsigned long long>, dim3(1), dim3(1), 0, m->stream, (const unsigned long long *)G.stats, O.batch_host.dev(), DS_WORDS);
+    HIP_TRY(hipGetLastError());
+    rc = check_device_error(m);  // the one wait
+    if (rc) return rc;
+    const volatile unsigned long long *res = O.batch_host.get();
     stats->chunks_tested = (int64_t)res[DS_TESTED];
     stats->chunks_touched = (int64_t)res[DS_TOUCHED];
     stats->chunks_emptied = (int64_t)res[DS_EMPTIED];

@@ -893,6 +893,30 @@ class Chisel {  // Chisel.h:38-230
         if (collectEmptied && stats.chunks_emptied > 0) hip_check(chisel_hip_garbage_collect(map, ids.data(), (int)stats.chunks_emptied));
         return stats;
     }
+    // ... and a stretch of trajectory in one call (chisel_hip_deintegrate_batch): the map is left, bit for bit, as DeintegrateDepthScan on
+    // each frame in order would leave it, a voxel under several of them being read and written once.  The frames may differ in image
+    // size and camera.  The stats are the sums over the frames; chunks_emptied counts every emptied chunk once.
+    struct DepthScan {
+        std::shared_ptr<const DepthImage<float>> depthImage;
+        Transform extrinsic;
+        PinholeCamera camera;
+    };
+    chisel_hip_deintegrate_stats DeintegrateDepthScans(const ProjectionIntegrator &integrator, const std::vector<DepthScan> &scans, bool colorRules,
+                                                       bool collectEmptied = true) {
+        const chisel_hip_integrator in = integrator.HipStruct();
+        hip_check(chisel_hip_set_integrator(map, &in));
+        std::vector<chisel_hip_depth_frame> frames;
+        frames.reserve(scans.size());
+        for (const DepthScan &s : scans) frames.push_back(hipfacade::DepthFrame(*s.depthImage, s.extrinsic, s.camera));
+        int64_t resident = 0;
+        hip_check(chisel_hip_num_chunks(map, &resident));
+        std::vector<int> ids(collectEmptied ? 3 * (size_t)resident : 0);
+        chisel_hip_deintegrate_stats stats;
+        hip_check(chisel_hip_deintegrate_batch(map, (int)frames.size(), frames.data(), colorRules ? 1 : 0, &stats, ids.empty() ? nullptr : ids.data(),
+                                               (int)(ids.size() / 3)));
+        if (collectEmptied && stats.chunks_emptied > 0) hip_check(chisel_hip_garbage_collect(map, ids.data(), (int)stats.chunks_emptied));
+        return stats;
+    }
     chisel_hip_map *HipMap() const { return map; }
 
   protected:

@@ -46,8 +46,8 @@ extern "C" {
  *      (chisel_hip_shell_plan_queue, _import_shells_fixed, _shell_commit), the stereo matcher (chisel_hip_stereo_*)
  *   3  chisel_hip_export_chunks, _import_ghost_chunks, _export_shells, _import_ghost_shells removed; later additions within 3 (nothing
  *      removed or re-typed): chisel_hip_render_view, chisel_hip_query_points, chisel_hip_cast_rays, chisel_hip_align_terms,
- *      chisel_hip_align_solve, chisel_hip_align_depth, chisel_hip_merge_map, chisel_hip_deintegrate_depth (no slot in the hipEvent profiler:
- *      CHISEL_HIP_NUM_KERNELS stays) */
+ *      chisel_hip_align_solve, chisel_hip_align_depth, chisel_hip_merge_map, chisel_hip_deintegrate_depth, chisel_hip_deintegrate_batch (no slot in
+ *      the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
 #define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -673,6 +673,22 @@ typedef struct {
     int64_t chunks_tested, chunks_touched, chunks_emptied, voxels_updated, voxels_cleared, voxels_skipped;
 } chisel_hip_deintegrate_stats;   /* 48 bytes */
 int chisel_hip_deintegrate_depth(chisel_hip_map *map, const chisel_hip_depth_frame *frame, int color_rules, chisel_hip_deintegrate_stats *stats,
+                                 int *emptied_ids_xyz, int max_ids);
+/* Many frames taken out in one call -- a loop closure moves a stretch of a trajectory, and most of its keyframes look at the same voxels.
+ * The map is left, bit for bit, in the state that n calls of chisel_hip_deintegrate_depth on frames[0], ..., frames[n-1], in that order,
+ * would leave it: the distance voxels (the frames apply to a voxel in call order; the rule depends on the voxel's state), meshesToUpdate
+ * and the sign summaries; the CHISEL_HIP_CNT_* counters are not touched.  DESIGN.md "Many frames in one call" has the definition.  The
+ * frames go in launch sets of up to 16, and a voxel under several frames of a set is read and written once.
+ * stats: the sums of what the n single calls would report -- chunks_tested = n x the resident chunks, chunks_touched = the (chunk, frame)
+ * pairs in which that frame updated or cleared a voxel, chunks_emptied = the chunks some frame of the call touched and in which no voxel
+ * has a weight > 0 at the end (each counted once; the ids of the first max_ids of them, in any order, in emptied_ids_xyz).
+ * The frames of one call may differ in image size, camera and memory space (on_device per frame); host images are staged, a launch set
+ * at a time, and all of them have been copied when the call returns.  The work is queued on the map's stream; with stats == NULL and
+ * device images only the call waits for nothing, otherwise once, at its end.  n == 0: CHISEL_HIP_OK, zero stats, nothing launched.
+ * Refused with nothing touched, every frame being looked at first: CHISEL_HIP_ERR_INVALID for a null map, n < 0, null frames with n > 0,
+ * max_ids < 0, emptied_ids_xyz without stats, and any frame chisel_hip_deintegrate_depth refuses (the message names its index);
+ * CHISEL_HIP_ERR_UNSUPPORTED for a group or one shard of several. */
+int chisel_hip_deintegrate_batch(chisel_hip_map *map, int n, const chisel_hip_depth_frame *frames, int color_rules, chisel_hip_deintegrate_stats *stats,
                                  int *emptied_ids_xyz, int max_ids);
 /* ProjectionIntegrator::Integrate<DataType>(depthImage, camera, cameraPose, chunk) / IntegrateColor (ProjectionIntegrator.h:51-52,
  * :101-102): ONE frame into ONE resident chunk -- whether or not the frustum's id range holds it, as the reference's per-chunk call

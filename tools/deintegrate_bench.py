@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time chisel_hip_deintegrate_depth on the maps of bench.py's default stream (sphere_room, 640 x 480 depth + colour, 1 cm voxels, 16^3
+"""Time chisel_hip_deintegrate_depth and chisel_hip_deintegrate_batch on the maps of bench.py's default stream (sphere_room, 640 x 480 depth + colour, 1 cm voxels, 16^3
 chunks, InverseTruncator(1), carving 0.05 m): after frames 0-219 (the default window's map) and after frames 0-619 (the late window's,
 three times larger), every depth image in HBM, after warm-up.
 
@@ -10,6 +10,11 @@ Per map, medians and minima in microseconds (hipEvents on the map's stream aroun
                          `iters` frames of the stream; each is integrated again, untimed, before the next one leaves, so that every
                          timed call meets the same map
   deintegrate/wall       the same call returning its stats and the emptied ids to the host
+  deintegrate/device_again  the first line measured once more at the end of the map's lines: its run-to-run spread within one session
+  deintegrate_batch/device  16 keyframes taken out by one chisel_hip_deintegrate_batch call (the 16 frames that end at the rotating
+                         keyframe), nothing waited for; all 16 are integrated again, untimed, before the next call.  To be compared
+                         with 16 x deintegrate/device of the same run; per_keyframe_us is the median over 16
+  deintegrate_batch/wall the same call returning its stats and the emptied ids to the host
   list_only/device       the same call for a camera turned away from the map: the list kernel visits every committed slot, lists
                          (nearly) nothing, and the apply kernel's workgroups find an empty list -- the part of the call that grows with
                          the pool and not with the frame
@@ -53,7 +58,8 @@ def main():
     torch.cuda.synchronize()
 
     def stats(t):
-        return {"us": round(float(np.median(t)), 1), "us_min": round(float(np.min(t)), 1)}
+        return {"us": round(float(np.median(t)), 1), "us_min": round(float(np.min(t)), 1), "us_p10": round(float(np.percentile(t, 10)), 1),
+                "us_p90": round(float(np.percentile(t, 90)), 1)}
 
     res = {"voxel_m": RES, "chunk": CHUNK, "image": "%dx%d" % (W, H), "iters": a.iters, "maps": {}}
     for n in counts:
@@ -99,6 +105,23 @@ def main():
         r["deintegrate/device"] = timed(lambda k: gm.DeintegrateDepthScan(integ, frames[k][0], frames[k][1], cam, color_rules=True, stats=False), undo=forward)
         r["deintegrate/wall"] = timed(lambda k: gm.DeintegrateDepthScan(integ, frames[k][0], frames[k][1], cam, color_rules=True), undo=forward, wall=True)
 
+        # ---- 16 keyframes per call
+        def stretch(k):
+            return list(range(max(0, k - 15), k + 1))
+
+        def batch_out(k, **kw):
+            return gm.DeintegrateDepthScans(integ, [(frames[j][0], frames[j][1], cam) for j in stretch(k)], color_rules=True, **kw)
+
+        def batch_in(k):
+            gm.IntegrateBatch(integ, [(frames[j][0], frames[j][1], cam) for j in stretch(k)], [(color, frames[j][1], cam) for j in stretch(k)])
+
+        took = batch_out(keys[0])
+        batch_in(keys[0])
+        r["one_batch_call"] = dict({k: v for k, v in took.items() if k != "emptied_ids"}, keyframes=len(stretch(keys[0])))
+        r["deintegrate_batch/device"] = timed(lambda k: batch_out(k, stats=False), undo=batch_in)
+        r["deintegrate_batch/device"]["per_keyframe_us"] = round(r["deintegrate_batch/device"]["us"] / len(stretch(keys[0])), 2)
+        r["deintegrate_batch/wall"] = timed(batch_out, undo=batch_in, wall=True)
+
         def away(k):
             p = np.array(frames[k][1], np.float32)
             p[:3, :3] = p[:3, :3] @ np.diag([1.0, -1.0, -1.0]).astype(np.float32)
@@ -110,6 +133,7 @@ def main():
         back = lambda k: gm.DeintegrateDepthScan(integ, frames[k][0], frames[k][1], cam, color_rules=True, stats=False)
         r["forward/device"] = timed(forward, undo=back)
         r["forward/wall"] = timed(forward, undo=back, wall=True)
+        r["deintegrate/device_again"] = timed(lambda k: gm.DeintegrateDepthScan(integ, frames[k][0], frames[k][1], cam, color_rules=True, stats=False), undo=forward)
         t = []
         for _ in range(3):
             gm.synchronize()
