@@ -637,14 +637,19 @@ class Chisel:
         for its own end and returns None"""
         self._use(integrator)
         f, keep = depth_frame(depth_image, extrinsic, camera)
+        return self._deintegrate(self.L.chisel_hip_deintegrate_depth, (self.h, C.byref(f), int(bool(color_rules))), [keep], stats, collect)
+
+    def _deintegrate(self, entry, head, keep, stats, collect):
+        """the tail of DeintegrateDepthScan and DeintegrateDepthScans: `entry` is the C entry, `head` its arguments in front of
+        (stats, ids, max_ids), `keep` what the frames point at"""
         if not stats:
             assert not collect, "collect=True needs the ids, which stats=False does not wait for"
-            check(self.L.chisel_hip_deintegrate_depth(self.h, C.byref(f), int(bool(color_rules)), None, None, 0))
-            self._keep = [keep]
+            check(entry(*head, None, None, 0))
+            self._keep = keep  # (the call may still be queued: the images live until the next one)
             return None
         st = capi.DeintegrateStats()
         ids = np.zeros((max(1, self.NumChunks()), 3), np.int32)  # (no chunk is created: the resident ones bound the emptied ones)
-        check(self.L.chisel_hip_deintegrate_depth(self.h, C.byref(f), int(bool(color_rules)), C.byref(st), ids.ctypes.data_as(C.POINTER(C.c_int)), len(ids)))
+        check(entry(*head, C.byref(st), ids.ctypes.data_as(C.POINTER(C.c_int)), len(ids)))  # (it has waited for its own end: nothing to keep)
         out = {n: int(getattr(st, n)) for n, _ in capi.DeintegrateStats._fields_}
         out["emptied_ids"] = ids[:min(out["chunks_emptied"], len(ids))].copy()
         if collect and len(out["emptied_ids"]):
@@ -680,20 +685,7 @@ class Chisel:
         for i, (d, p, cam) in enumerate(frames):
             fa[i], k = depth_frame(d, p, cam)
             keep.append(k)
-        if not stats:
-            assert not collect, "collect=True needs the ids, which stats=False does not wait for"
-            check(self.L.chisel_hip_deintegrate_batch(self.h, n, fa, int(bool(color_rules)), None, None, 0))
-            self._keep = keep
-            return None
-        st = capi.DeintegrateStats()
-        ids = np.zeros((max(1, self.NumChunks()), 3), np.int32)  # (no chunk is created: the resident ones bound the emptied ones)
-        check(self.L.chisel_hip_deintegrate_batch(self.h, n, fa, int(bool(color_rules)), C.byref(st), ids.ctypes.data_as(C.POINTER(C.c_int)), len(ids)))
-        self._keep = keep
-        out = {n: int(getattr(st, n)) for n, _ in capi.DeintegrateStats._fields_}
-        out["emptied_ids"] = ids[:min(out["chunks_emptied"], len(ids))].copy()
-        if collect and len(out["emptied_ids"]):
-            self.GarbageCollect(out["emptied_ids"])
-        return out
+        return self._deintegrate(self.L.chisel_hip_deintegrate_batch, (self.h, n, fa, int(bool(color_rules))), keep, stats, collect)
 
     def ReintegrateDepthScans(self, integrator, frames, new_poses, colors=None, stats=True, collect=False):
         """a stretch of trajectory whose poses were corrected after its keyframes were fused: DeintegrateDepthScans of `frames` (a

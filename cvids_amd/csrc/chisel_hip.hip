@@ -390,16 +390,12 @@ struct chisel_hip_map {
         MergeView view{};                                              // (what the kernels take: copies of the pointers above)
         int64_t chunks_hint = 0;                                       // chunks of the latest source (sizes the table of the next merge)
     } merge_mem;
-    struct DeintegrateMemory {                                         // chisel_hip_deintegrate_depth (host_deintegrate.h), allocated on first use, grown on demand
-        DeviceBuffer<int> list, ids;                                   // the listed slots | the ids of the emptied chunks
-        DeviceBuffer<unsigned long long> stats;
+    struct DeintegrateMemory {                                         // chisel_hip_deintegrate_depth and _batch (host_deintegrate.h: one set for both), allocated on first use, grown on demand
+        DeviceBuffer<int2> list;                                       // [committed slots] a batch's (slot, frame mask) entries; a single frame's slots, as int
+        DeviceBuffer<int> ids;                                         // the ids of the emptied chunks
+        DeviceBuffer<unsigned long long> words;                        // [DS_WORDS + launch sets] the stats and the list lengths: zeroed by the call's one memset
         PinnedBuffer<unsigned long long> host;                         // [DS_WORDS] where the stats reach the host
-        DeintegrateView view{};                                        // (what the kernels take: copies of the pointers above)
-        // chisel_hip_deintegrate_batch: the (slot, frame mask) list | the stats and one list length per launch set | the frames' table
-        DeviceBuffer<int2> batch_list;
-        DeviceBuffer<unsigned long long> batch_words;                  // [DS_WORDS + launch sets]: zeroed by the call's one memset
-        DeviceBuffer<DeintegrateBatchEntry> batch_table;               // [frames of the call]
-        PinnedBuffer<unsigned long long> batch_host;                   // [DS_WORDS] where its stats reach the host
+        DeviceBuffer<DeintegrateBatchEntry> table;                     // [frames of the call] a batch's own
         // The host side of a table's upload lives until the copy is over: a block is taken again once its event has passed, so that
         // a call that waits for nothing can follow one whose copy is still queued.
         struct TableUpload {

@@ -1,7 +1,8 @@
-// kernels_rewrite.h -- the chunk pass: what merge_gather_kernel (kernels_merge.h) and deintegrate_apply_kernel
-// (kernels_deintegrate.h), which rewrite voxels outside the integration path, have in common.  One workgroup of 256 per listed chunk
-// at a time; a lane owns 4 consecutive x voxels (the map's lane layout: 16-byte accesses), quads q = thread, thread + 256, ...; thread
-// 0 ends with the chunk's note (chisel_device.h: note_slot_updated).  And report_words_kernel, the way of a few words to the host.
+// kernels_rewrite.h -- the chunk pass: what merge_gather_kernel (kernels_merge.h) and the two de-integration apply
+// kernels (kernels_deintegrate.h), which rewrite voxels outside the integration path, have in common.  One workgroup of T = 256 (512
+// in the batched apply kernel from 16^3 on) per listed chunk at a time; a lane owns 4 consecutive x voxels (the map's lane layout:
+// 16-byte accesses), quads q = thread, thread + T, ...; thread 0 ends with the chunk's note (chisel_device.h: note_slot_updated; for
+// de-integration inside deintegrate_chunk_end).  And report_words_kernel, the way of a few words to the host.
 #pragma once
 #include "chisel_device.h"
 

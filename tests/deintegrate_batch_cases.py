@@ -81,6 +81,13 @@ def case(oracle_mod, seq, N, trunc, color_rules):
 
 # ---- the corrected stretch of trajectory ------------------------------------------------------------------------------------------------
 REINTEGRATED = (1, 2)  # the frames of `tilt` that go in 2 cm / 1 degree off
+# The largest |sdf difference| between a batch re-integration in the restatement and the oracle's map of the frames as they are, over
+# 8^3 and 16^3 and the three truncators, by color_rules (test_reintegration_bound_is_the_measurement of
+# tests/test_deintegrate_batch_cases.py prints them); the bound is four times that, since taking out more frames compounds the
+# rounding.  Under the depth rules the weights are small integers and the round trip is exact: equality.  Metres.
+REINTEGRATION_MEASURED = {False: 0.0, True: 5.9604644775390625e-08}  # 2^-24
+REINTEGRATION_BOUND = {k: 4 * v for k, v in REINTEGRATION_MEASURED.items()}
+REINTEGRATION_CASES = [(N, t) for N in (8, 16) for t in dr.TRUNCATORS]
 
 
 def reintegration_frames():

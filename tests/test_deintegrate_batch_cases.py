@@ -20,14 +20,6 @@ REACH = {
 }
 FIRST_SET = {"tilt": (25477, 174, 6), "hostile": (134257, 163, 5), "neg_aniso": (43531, 209, 9)}
 
-# The largest |sdf difference| between a batch re-integration in the restatement and the oracle's map of the frames as they are, over
-# 8^3 and 16^3 and the three truncators, by color_rules (test_reintegration_bound_is_the_measurement prints them); the bound is four
-# times that, since taking out more frames compounds the rounding.  Under the depth rules the weights are small
-# integers and the round trip is exact: equality.  Metres.
-REINTEGRATION_MEASURED = {False: 0.0, True: 5.9604644775390625e-08}  # 2^-24
-REINTEGRATION_BOUND = {k: 4 * v for k, v in REINTEGRATION_MEASURED.items()}
-REINTEGRATION_CASES = [(N, t) for N in (8, 16) for t in dr.TRUNCATORS]
-
 
 @pytest.mark.parametrize("seq,N,trunc,color_rules", bc.CASES, ids=lambda v: str(v))
 def test_cases_reach_what_they_are_for(oracle_mod, seq, N, trunc, color_rules):
@@ -60,7 +52,7 @@ def test_order_matters(oracle_mod):
 
 
 @pytest.mark.parametrize("color_rules", [False, True])
-@pytest.mark.parametrize("N,trunc", REINTEGRATION_CASES, ids=lambda v: str(v))
+@pytest.mark.parametrize("N,trunc", bc.REINTEGRATION_CASES, ids=lambda v: str(v))
 def test_batch_reintegration_against_the_oracle(oracle_mod, N, trunc, color_rules):
     got, right = bc.reintegration(oracle_mod, N, trunc, color_rules)
     worst, same_w = dr.max_sdf_difference(got, right)
@@ -68,14 +60,14 @@ def test_batch_reintegration_against_the_oracle(oracle_mod, N, trunc, color_rule
     assert len(right) > 50
     if not color_rules:
         assert same_w and worst == 0.0
-    assert worst <= REINTEGRATION_BOUND[color_rules], (worst, REINTEGRATION_BOUND[color_rules])
+    assert worst <= bc.REINTEGRATION_BOUND[color_rules], (worst, bc.REINTEGRATION_BOUND[color_rules])
 
 
 def test_reintegration_bound_is_the_measurement(oracle_mod):
     for color_rules in (False, True):
-        worst = max(dr.max_sdf_difference(*bc.reintegration(oracle_mod, N, t, color_rules))[0] for N, t in REINTEGRATION_CASES)
+        worst = max(dr.max_sdf_difference(*bc.reintegration(oracle_mod, N, t, color_rules))[0] for N, t in bc.REINTEGRATION_CASES)
         print("color_rules %s: %.17g" % (color_rules, worst))
-        assert worst == REINTEGRATION_MEASURED[color_rules]
+        assert worst == bc.REINTEGRATION_MEASURED[color_rules]
 
 
 def test_the_entry_is_declared_and_exported(hip_lib):

@@ -9,10 +9,10 @@ import numpy as np
 import pytest
 
 from tests import deintegrate_batch_cases as bc
+from tests import deintegrate_gpu as gd
 from tests import deintegrate_restated as dr
 from tests import frame_cases as fc
 from tests import merge_restated as mr
-from tests import test_gpu_deintegrate as gd
 from tests.common import compare_meshes, fields_of, free_bytes, upload
 
 pytestmark = pytest.mark.gpu
@@ -99,6 +99,44 @@ def test_batch_is_the_single_calls_in_order(seq, N, trunc, color_rules):
     assert gd.dirty(a) == gd.dirty(b) and a.counters() == b.counters()
     a.close()
     b.close()
+
+
+def test_single_and_batch_calls_interleaved_without_a_wait():
+    """both entries share one set of scratch in the map: a single call, a batch and a single call queued with stats=False on device
+    images (nothing waited for), then the same three kinds with stats and ids; every count, the fields and the dirty set against the
+    restated fold of the same frames in the same order"""
+    import torch
+    gm, frames, cam, rules = filled(*bc.CASES[2])
+    N, integ = 8, gd.integrator(rules)
+    out = frames[bc.OUT]
+    images = [torch.from_numpy(np.ascontiguousarray(f[0])).to("cuda:0") for f in out]
+    torch.cuda.synchronize()
+    field, listed, touched = fields_of(gm, N), gd.dirty(gm), set()
+    for lo, hi in ((0, 1), (1, 6), (6, 7)):  # queued: nothing returned, nothing waited for
+        part = scans(out[lo:hi], cam, images[lo:hi])
+        if hi - lo == 1:
+            assert gm.DeintegrateDepthScan(integ, *part[0], color_rules=rules.color_rules, stats=False) is None
+        else:
+            assert gm.DeintegrateDepthScans(integ, part, color_rules=rules.color_rules, stats=False) is None
+    field, _, detail = bc.restated_batch(field, out[:7], rules, N, dr.GRIDS[N])
+    touched |= detail["touched"]
+    emptied = 0
+    for lo, hi in ((7, 8), (8, 16), (16, 17)):  # behind them, on the same scratch: stats and ids
+        part = scans(out[lo:hi], cam, images[lo:hi])
+        if hi - lo == 1:
+            got = gm.DeintegrateDepthScan(integ, *part[0], color_rules=rules.color_rules)
+        else:
+            got = gm.DeintegrateDepthScans(integ, part, color_rules=rules.color_rules)
+        field, wstats, detail = bc.restated_batch(field, out[lo:hi], rules, N, dr.GRIDS[N])
+        print((lo, hi), wstats)
+        assert {k: got[k] for k in dr.STAT_NAMES} == wstats, (got, wstats)
+        assert sorted(map(tuple, got["emptied_ids"].tolist())) == detail["emptied"]
+        touched |= detail["touched"]
+        emptied += wstats["chunks_emptied"]
+    assert emptied > 0 and len(touched) > 17
+    mr.assert_fields_bit_equal(field, fields_of(gm, N), True, "single, batch, single, twice")
+    assert gd.dirty(gm) == listed | gd.neighbourhoods(touched)
+    gm.close()
 
 
 # ---- c. the order of the frames ---------------------------------------------------------------------------------------------------------------
@@ -240,7 +278,6 @@ def test_emptied_chunks_are_collected():
 def test_reintegrate_scans(oracle_mod, color_rules):
     """ReintegrateDepthScans is DeintegrateDepthScans + IntegrateBatch, bit for bit; what it leaves is the oracle's map of the frames as
     they are within the bound the CPU test measured; and the map is good for meshing and for a further frame"""
-    from tests.test_deintegrate_batch_cases import REINTEGRATION_BOUND
     N, trunc = 8, "constant"
     frames, wrong, cam = bc.reintegration_frames()
     rules = dr.rules_of(trunc, color_rules)
@@ -260,8 +297,8 @@ def test_reintegrate_scans(oracle_mod, color_rules):
     b.close()
     right = dr.oracle_map(oracle_mod, N, dr.GRIDS[N], rules, frames, cam).fields()
     worst, same_w = dr.max_sdf_difference({c: (s, w, None) for c, (s, w, _) in a.fields().items()}, right)
-    print("against the oracle: max |d sdf| %.9e, weights bit-equal: %s; bound %.9e" % (worst, same_w, REINTEGRATION_BOUND[color_rules]))
-    assert worst <= REINTEGRATION_BOUND[color_rules]
+    print("against the oracle: max |d sdf| %.9e, weights bit-equal: %s; bound %.9e" % (worst, same_w, bc.REINTEGRATION_BOUND[color_rules]))
+    assert worst <= bc.REINTEGRATION_BOUND[color_rules]
     # the mesh over what the map lists, and a further frame, against the oracle started from the downloaded fields
     om = oracle_mod.OracleMap(N, dr.GRIDS[N], color_rules)
     om.set_integrator(rules.kind, float(rules.param), float(rules.weight), rules.carving, float(rules.carving_dist))
