@@ -126,7 +126,7 @@ EXPORTS = [
 SELFTEST_EXPORTS = [
     "chisel_hip_kat_truncation", "chisel_hip_kat_dist", "chisel_hip_kat_color", "chisel_hip_kat_color_fresh", "chisel_hip_kat_color_any",
     "chisel_hip_kat_reciprocal", "chisel_hip_kat_floor", "chisel_hip_kat_raycast", "chisel_hip_debug_cloud_stats",
-    "chisel_hip_debug_cull_space", "chisel_hip_debug_frustum_range", "chisel_hip_debug_stereo_prep",
+    "chisel_hip_debug_cull_space", "chisel_hip_debug_frustum_range", "chisel_hip_debug_stereo_prep", "chisel_hip_debug_hash_table",
 ]
 
 
@@ -278,6 +278,7 @@ def load_library():
                         ("chisel_hip_kat_color_fresh", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_kat_color_any", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_debug_cloud_stats", [vp, i64p]),
+                        ("chisel_hip_debug_hash_table", [vp, i64p, vp, vp, vp, vp]),
                         ("chisel_hip_kat_raycast", [f32p, C.c_int, i32p, i32p, i32p, C.c_int, i32p]),
                         ("chisel_hip_kat_reciprocal", [C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint)]),
                         ("chisel_hip_kat_floor", [C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint)])):

@@ -750,6 +750,19 @@ class Chisel:
         check(self.L.chisel_hip_pool_info(self.h, out))
         return {"committed": int(out[0]), "limit": int(out[1]), "grown": int(out[2]), "growable": bool(out[3])}
 
+    def hash_table(self):
+        """chisel_hip_debug_hash_table: the chunk hash and the slot tables as they stand (tests; one map, not a group) -- capacity,
+        committed, free_top, hash_keys[capacity] (uint64), hash_vals[capacity], slot_key[committed], free_list[:free_top]"""
+        info = (C.c_int64 * 4)()
+        check(self.L.chisel_hip_debug_hash_table(self.h, info, None, None, None, None))
+        cap, committed = int(info[0]), int(info[1])
+        keys, vals = np.empty(cap, np.uint64), np.empty(cap, np.int32)
+        slot_key, free_list = np.empty(committed, np.uint64), np.empty(committed, np.int32)
+        check(self.L.chisel_hip_debug_hash_table(self.h, info, keys.ctypes.data, vals.ctypes.data, slot_key.ctypes.data, free_list.ctypes.data))
+        assert (int(info[0]), int(info[1])) == (cap, committed)
+        return {"capacity": cap, "committed": committed, "free_top": int(info[2]), "hash_keys": keys, "hash_vals": vals,
+                "slot_key": slot_key, "free_list": free_list[:int(info[2])].copy()}
+
     def launch_stats(self, reset=False):
         """which shapes the launch heuristics picked (chisel_hip_get_launch_stats)"""
         out = (C.c_int64 * len(self.LAUNCH_STATS))()

@@ -61,6 +61,21 @@ int fail(int code, const std::string &msg) {
     return code;
 }
 
+// The chunk ids the map can hold: -ID_BIAS + 2 ... ID_BIAS - 2 on every axis (what the depth path admits of a frustum's range, and what
+// the kernels' neighbour look-ups guard: an id and its 26 neighbours then fit pack_id's 21 bits per axis, and no packed id is KEY_EMPTY or
+// KEY_TOMB).  Every entry that takes a chunk id from its caller refuses the others with CHISEL_HIP_ERR_INVALID before it launches anything.
+inline bool chunk_id_in_range(const int id[3]) {
+    for (int a = 0; a < 3; a++)
+        if (id[a] < -ID_BIAS + 2 || id[a] > ID_BIAS - 2) return false;
+    return true;
+}
+inline bool chunk_ids_in_range(const int *ids, int n) {
+    for (int j = 0; j < n; j++)
+        if (!chunk_id_in_range(ids + 3 * j)) return false;
+    return true;
+}
+const char *const kIdOutOfRange = "chunk id outside the addressable range (-2^20 + 2 ... 2^20 - 2 on every axis)";
+
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
@@ -1808,6 +1823,7 @@ int chisel_hip_integrate_batch(chisel_hip_map *m, int n, const chisel_hip_depth_
 // goes through the ordinary launch set with the candidate range pinned to that id.
 int chisel_hip_integrate_chunk(chisel_hip_map *m, const int id[3], const chisel_hip_depth_frame *f, const chisel_hip_color_frame *c, int *updated) {
     SETTLE(m);
+    if (id && !chunk_id_in_range(id)) return fail(CHISEL_HIP_ERR_INVALID, kIdOutOfRange);
     if (m && m->is_group) return id ? chisel_hip_integrate_chunk(group::owner_map(m, id), id, f, c, updated) : fail(CHISEL_HIP_ERR_INVALID, "null argument");
     if (!m || !id || !f) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
     if (chunk_owner(id[0], id[1], id[2], m->cfg.n_shards, m->cfg.shard_block) != m->cfg.shard_rank) return fail(CHISEL_HIP_ERR_INVALID, "this shard does not own the chunk");
@@ -1833,6 +1849,7 @@ int chisel_hip_integrate_chunk(chisel_hip_map *m, const int id[3], const chisel_
 
 int chisel_hip_garbage_collect(chisel_hip_map *m, const int *ids, int n) {
     SETTLE(m);
+    if (ids && n > 0 && !chunk_ids_in_range(ids, n)) return fail(CHISEL_HIP_ERR_INVALID, kIdOutOfRange);
     if (m && m->is_group) return group::garbage_collect(m, ids, n);
     if (!m || n < 0 || (n > 0 && !ids)) return fail(CHISEL_HIP_ERR_INVALID, "bad id list");
     if (n == 0) return CHISEL_HIP_OK;
@@ -1942,6 +1959,7 @@ int chisel_hip_list_chunks(chisel_hip_map *m, int *ids, int64_t max_ids, int64_t
 
 int chisel_hip_has_chunk(chisel_hip_map *m, const int id[3], int *out) {
     SETTLE(m);
+    if (id && !chunk_id_in_range(id)) return fail(CHISEL_HIP_ERR_INVALID, kIdOutOfRange);
     if (m && m->is_group) return id ? chisel_hip_has_chunk(group::owner_map(m, id), id, out) : fail(CHISEL_HIP_ERR_INVALID, "null argument");
     if (!m || !id || !out) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(m->device));
@@ -1954,6 +1972,7 @@ int chisel_hip_has_chunk(chisel_hip_map *m, const int id[3], int *out) {
 
 int chisel_hip_download_chunk(chisel_hip_map *m, const int id[3], float *sdf, float *weight, uint8_t *rgbw) {
     SETTLE(m);
+    if (id && !chunk_id_in_range(id)) return fail(CHISEL_HIP_ERR_INVALID, kIdOutOfRange);
     if (m && m->is_group) return id ? chisel_hip_download_chunk(group::owner_map(m, id), id, sdf, weight, rgbw) : fail(CHISEL_HIP_ERR_INVALID, "null argument");
     if (!m || !id) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(m->device));
@@ -2515,6 +2534,7 @@ int chisel_hip_load_map(chisel_hip_map *m, const char *path) {
         in.read(reinterpret_cast<char *>(wgt.data()), (std::streamsize)(V * sizeof(float)));
         if (h.has_color) in.read(reinterpret_cast<char *>(col.data()), (std::streamsize)(4 * V));
         if (!in) return fail(CHISEL_HIP_ERR_IO, std::string("truncated map file: ") + path);
+        if (!chunk_id_in_range(id)) return fail(CHISEL_HIP_ERR_INVALID, std::string("map file names a ") + kIdOutOfRange);
         if (chunk_owner(id[0], id[1], id[2], m->cfg.n_shards, m->cfg.shard_block) != m->cfg.shard_rank) continue;  // another shard's chunk
         rc = chisel_hip_upload_chunk(m, id, sdf.data(), wgt.data(), h.has_color ? col.data() : nullptr);
         if (rc) return rc;
@@ -2524,6 +2544,7 @@ int chisel_hip_load_map(chisel_hip_map *m, const char *path) {
 
 int chisel_hip_upload_chunk(chisel_hip_map *m, const int id[3], const float *sdf, const float *weight, const uint8_t *rgbw) {
     SETTLE(m);
+    if (id && !chunk_id_in_range(id)) return fail(CHISEL_HIP_ERR_INVALID, kIdOutOfRange);
     if (m && m->is_group) return id ? chisel_hip_upload_chunk(group::owner_map(m, id), id, sdf, weight, rgbw) : fail(CHISEL_HIP_ERR_INVALID, "null argument");
     if (!m || !id || !sdf || !weight) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
     if (chunk_owner(id[0], id[1], id[2], m->cfg.n_shards, m->cfg.shard_block) != m->cfg.shard_rank)
@@ -2540,6 +2561,8 @@ int chisel_hip_upload_chunk(chisel_hip_map *m, const int id[3], const float *sdf
     int slot = -1;
     HIP_TRY(hipMemcpyAsync(&slot, m->scratch_i.get(), sizeof(int), hipMemcpyDeviceToHost, m->stream));
     HIP_TRY(hipStreamSynchronize(m->stream));
+    // (a full pool refuses this chunk and nothing else: the map holds what it held, so the refusal is not latched as "map incomplete")
+    if (slot == -2) return fail(CHISEL_HIP_ERR_POOL_FULL, "chunk pool exhausted: raise chisel_hip_config.max_chunks");
     if (slot < 0) return check_device_error(m) ? CHISEL_HIP_ERR_POOL_FULL : fail(CHISEL_HIP_ERR_POOL_FULL, "no slot");
     const size_t off = (size_t)slot * m->V;
     {

@@ -564,6 +564,7 @@ int chisel_hip_update_meshes_of(chisel_hip_map *m, const int *ids, int n) {
     SETTLE(m);
     if (m && m->is_group) return fail(CHISEL_HIP_ERR_UNSUPPORTED, "chisel_hip_update_meshes_of is a call between the shards of a map: a group makes it itself (chisel_hip_update_meshes)");
     if (!m || n < 0 || (n > 0 && !ids)) return fail(CHISEL_HIP_ERR_INVALID, "bad id list");
+    if (!chunk_ids_in_range(ids, n)) return fail(CHISEL_HIP_ERR_INVALID, kIdOutOfRange);
     HIP_TRY(hipSetDevice(m->device));
     int rc = resolve_pending_meshes(m);  // the device buffers of the previous recompute are about to be reused
     if (rc) return rc;
@@ -623,6 +624,7 @@ int chisel_hip_update_meshes_planned(chisel_hip_map *m) {
 // caller's business there (Chisel::UpdateMeshes clears it, Chisel.cpp:57), so nothing of it is touched here
 int chisel_hip_recompute_mesh(chisel_hip_map *m, const int id[3]) {
     SETTLE(m);
+    if (id && !chunk_id_in_range(id)) return fail(CHISEL_HIP_ERR_INVALID, kIdOutOfRange);
     if (m && m->is_group) return id ? chisel_hip_recompute_mesh(group::owner_map(m, id), id) : fail(CHISEL_HIP_ERR_INVALID, "null argument");
     if (!m || !id) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
     m->mesh_detached = true;
@@ -636,6 +638,7 @@ int chisel_hip_recompute_mesh(chisel_hip_map *m, const int id[3]) {
 int chisel_hip_mesh_cube(chisel_hip_map *m, const int id[3], const int voxel[3], const float coords[3], float *vertices, float *normals, int *n_vertices,
                          int *occupied) {
     SETTLE(m);
+    if (id && !chunk_id_in_range(id)) return fail(CHISEL_HIP_ERR_INVALID, kIdOutOfRange);
     if (m && m->is_group) return id ? chisel_hip_mesh_cube(group::owner_map(m, id), id, voxel, coords, vertices, normals, n_vertices, occupied)
                                     : fail(CHISEL_HIP_ERR_INVALID, "null argument");
     if (!m || !id || !voxel || !coords || !n_vertices || !occupied) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
@@ -668,6 +671,7 @@ int chisel_hip_mesh_cube(chisel_hip_map *m, const int id[3], const int voxel[3],
 int chisel_hip_generate_mesh(chisel_hip_map *m, const int id[3], int stages, int64_t capacity_vertices, int64_t capacity_grids, float *vertices,
                              float *normals, float *colors, float *grids, int64_t *n_vertices, int64_t *n_grids) {
     SETTLE(m);
+    if (id && !chunk_id_in_range(id)) return fail(CHISEL_HIP_ERR_INVALID, kIdOutOfRange);
     if (m && m->is_group) return id ? chisel_hip_generate_mesh(group::owner_map(m, id), id, stages, capacity_vertices, capacity_grids, vertices, normals, colors, grids, n_vertices, n_grids)
                                     : fail(CHISEL_HIP_ERR_INVALID, "null argument");
     if (!m || !id || !n_vertices || !n_grids) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
@@ -761,6 +765,7 @@ int chisel_hip_list_meshes(chisel_hip_map *m, int *ids, int64_t max_ids, int64_t
 
 int chisel_hip_mesh_size(chisel_hip_map *m, const int id[3], int64_t *nv, int64_t *ng) {
     SETTLE(m);
+    if (id && !chunk_id_in_range(id)) return fail(CHISEL_HIP_ERR_INVALID, kIdOutOfRange);
     if (m && m->is_group) return id ? chisel_hip_mesh_size(group::owner_map(m, id), id, nv, ng) : fail(CHISEL_HIP_ERR_INVALID, "null argument");
     if (!m || !id) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(m->device));
@@ -775,6 +780,7 @@ int chisel_hip_mesh_size(chisel_hip_map *m, const int id[3], int64_t *nv, int64_
 
 int chisel_hip_download_mesh(chisel_hip_map *m, const int id[3], float *v, float *n, float *c, float *g) {
     SETTLE(m);
+    if (id && !chunk_id_in_range(id)) return fail(CHISEL_HIP_ERR_INVALID, kIdOutOfRange);
     if (m && m->is_group) return id ? chisel_hip_download_mesh(group::owner_map(m, id), id, v, n, c, g) : fail(CHISEL_HIP_ERR_INVALID, "null argument");
     if (!m || !id) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(m->device));

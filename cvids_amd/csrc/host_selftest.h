@@ -73,6 +73,23 @@ int chisel_hip_debug_cloud_stats(chisel_hip_map *m, int64_t out[4]) {
     out[0] = ctl[0]; out[1] = ctl[1]; out[2] = mx; out[3] = used;
     return CHISEL_HIP_OK;
 }
+// the chunk hash and the slot tables as they stand once the map's stream has drained (copies only): info = {hash capacity, committed
+// slots, free_top, 0}; arrays that are null are skipped -- a first call with none of them tells the sizes
+int chisel_hip_debug_hash_table(chisel_hip_map *m, int64_t info[4], uint64_t *hash_keys, int *hash_vals, uint64_t *slot_key, int *free_list) {
+    SETTLE(m);
+    if (!m || !info || m->is_group) return fail(CHISEL_HIP_ERR_INVALID, "the read-out of one map's table (not of a group)");
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    const size_t cap = (size_t)m->view.hash_mask + 1, committed = (size_t)m->view.committed;
+    int top = 0;
+    HIP_TRY(hipMemcpy(&top, m->view.free_top, sizeof(int), hipMemcpyDeviceToHost));
+    info[0] = (int64_t)cap; info[1] = (int64_t)committed; info[2] = top; info[3] = 0;
+    if (hash_keys) HIP_TRY(hipMemcpy(hash_keys, m->view.hash_keys, cap * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (hash_vals) HIP_TRY(hipMemcpy(hash_vals, m->view.hash_vals, cap * sizeof(int), hipMemcpyDeviceToHost));
+    if (slot_key && committed) HIP_TRY(hipMemcpy(slot_key, m->view.slot_key, committed * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (free_list && committed) HIP_TRY(hipMemcpy(free_list, m->view.free_list, committed * sizeof(int), hipMemcpyDeviceToHost));
+    return CHISEL_HIP_OK;
+}
 int chisel_hip_kat_color_any(unsigned *mismatches) {
     DeviceBuffer<unsigned> d;
     HIP_TRY(d.alloc(1));

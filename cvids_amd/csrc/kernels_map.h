@@ -202,7 +202,7 @@ __global__ void ensure_chunk_kernel(MapView M, int x, int y, int z, int *out_slo
         int top = atomicSub(M.free_top, 1) - 1;
         if (top < 0) {
             atomicAdd(M.free_top, 1);
-            raise_error(M.error_flag, 1);
+            slot = -2;  // no slot left: the caller's chunk is refused and the map is as complete as it was -- no error word is raised
         } else {
             slot = M.free_list[top];
             const uint64_t key = pack_id(x, y, z);
@@ -221,6 +221,7 @@ __global__ void ensure_chunk_kernel(MapView M, int x, int y, int z, int *out_slo
                 M.slot_key[slot] = key;
                 bbox_include(M.mesh_ctl, x, y, z);
             } else {
+                atomicAdd(M.free_top, 1);  // (the slot stays where it was on the free list)
                 raise_error(M.error_flag, 2);
                 slot = -1;
             }

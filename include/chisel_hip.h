@@ -203,6 +203,12 @@ int chisel_hip_integrate_pointcloud(chisel_hip_map *map, const chisel_hip_pointc
  * frames of one image size share launch sets of up to 16 frames: the voxels of a chunk stay in registers across them. */
 int chisel_hip_integrate_batch(chisel_hip_map *map, int n, const chisel_hip_depth_frame *frames,
                                const chisel_hip_color_frame *colors);
+/* CHUNK IDS.  The map addresses the ids -2^20 + 2 ... 2^20 - 2 on every axis (an id and its 26 neighbours fit the 21 bits per axis the
+ * chunk hash packs them into).  Every entry that takes a chunk id from its caller -- chisel_hip_garbage_collect, _has_chunk,
+ * _download_chunk, _upload_chunk, _integrate_chunk, _update_meshes_of, _recompute_mesh, _mesh_size, _download_mesh, _generate_mesh,
+ * _mesh_cube, and chisel_hip_load_map for the ids of its file (chisel_hip_chunk_owner is a function of the id alone and takes any) --
+ * refuses an id outside that range with CHISEL_HIP_ERR_INVALID before anything is launched: the map is as it was (after a refused
+ * chisel_hip_load_map: reset, holding the file's chunks in front of the refused one). */
 /* Chisel::GarbageCollect(const ChunkIDList&) Chisel.cpp:61-67 / ChunkManager::RemoveChunk(ChunkID) ChunkManager.h:99-108 */
 int chisel_hip_garbage_collect(chisel_hip_map *map, const int *chunk_ids_xyz, int n);
 /* Chisel::UpdateMeshes Chisel.cpp:50-59 (recompute on every 10th call unless force) ->
@@ -219,7 +225,8 @@ int chisel_hip_list_chunks(chisel_hip_map *map, int *ids_xyz, int64_t max_ids, i
 int chisel_hip_has_chunk(chisel_hip_map *map, const int id_xyz[3], int *out);
 /* Chunk::GetVoxels / GetColorVoxels Chunk.h:66,117-120: N^3 sdf, N^3 weight, 4*N^3 rgbw (may be NULL) */
 int chisel_hip_download_chunk(chisel_hip_map *map, const int id_xyz[3], float *sdf, float *weight, uint8_t *rgbw);
-/* inverse of download (ChunkManager::AddChunk ChunkManager.h:89-92 with caller-filled voxels) */
+/* inverse of download (ChunkManager::AddChunk ChunkManager.h:89-92 with caller-filled voxels).  A chunk the pool has no slot for is
+ * refused with CHISEL_HIP_ERR_POOL_FULL and the map stays as it was: later calls do not report the pool as exhausted */
 int chisel_hip_upload_chunk(chisel_hip_map *map, const int id_xyz[3], const float *sdf, const float *weight,
                             const uint8_t *rgbw);
 /* Chisel::GetMeshesToUpdate Chisel.h:220-223: ids flagged since the last recompute (27-neighbourhoods) */

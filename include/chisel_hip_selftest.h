@@ -26,6 +26,10 @@ int chisel_hip_kat_floor(unsigned long long *mismatches, unsigned *example_bits)
 int chisel_hip_kat_raycast(const float *rays, int n, const int lo[3], const int hi[3], int *cells, int cap, int *count);
 /* point-cloud path: listed chunks, (unit, point) pairs, busiest unit, units of the last cloud */
 int chisel_hip_debug_cloud_stats(chisel_hip_map *map, int64_t out[4]);
+/* the chunk hash and the slot tables of ONE map (a group handle: CHISEL_HIP_ERR_INVALID) once its stream has drained; copies, no kernels.
+ * info = {hash capacity, committed slots, free_top, 0}; hash_keys / hash_vals take `capacity` entries, slot_key / free_list `committed`
+ * (the live part of the free list is its first free_top entries); null arrays are skipped, so a first call with none tells the sizes */
+int chisel_hip_debug_hash_table(chisel_hip_map *map, int64_t info[4], uint64_t *hash_keys, int *hash_vals, uint64_t *slot_key, int *free_list);
 /* host evaluation of the candidate enumeration: the ids cull_kernel hands to one shard; the reference's id range + planes + corners */
 int chisel_hip_debug_cull_space(const int range_min[3], const int range_dim[3], int n_shards, int shard_rank, int shard_block, int *ids,
                                 int capacity, int *count);
