@@ -98,6 +98,14 @@ class DeintegrateStats(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("chunks_tested", "chunks_touched", "chunks_emptied", "voxels_updated", "voxels_cleared", "voxels_skipped")]
 
 
+class DistanceWindow(C.Structure):
+    """chisel_hip_distance_window (include/chisel_hip.h): the window of chisel_hip_distance_field, 36 bytes"""
+    _fields_ = [("origin", C.c_int * 3), ("dims", C.c_int * 3), ("radius", C.c_int), ("unknown_is_obstacle", C.c_int),
+                ("surface_offset", C.c_float)]
+
+
+DISTANCE_MAX_RADIUS = 64  # chisel_hip_distance_field's largest radius, voxels
+
 ALIGN_CONVERGED, ALIGN_ITERATION_LIMIT, ALIGN_TOO_FEW_PIXELS, ALIGN_DEGENERATE = 0, 1, 2, 3  # CHISEL_HIP_ALIGN_*
 ALIGN_STATUS = {0: "CONVERGED", 1: "ITERATION_LIMIT", 2: "TOO_FEW_PIXELS", 3: "DEGENERATE"}
 
@@ -120,7 +128,7 @@ EXPORTS = [
     "chisel_hip_get_counters", "chisel_hip_memory_statistics", "chisel_hip_topology_epoch", "chisel_hip_candidates", "chisel_hip_cloud_candidates", "chisel_hip_mesh_cube", "chisel_hip_write_mesh_ply", "chisel_hip_shade_vertices", "chisel_hip_generate_mesh", "chisel_hip_recompute_mesh", "chisel_hip_integrate_chunk", "chisel_hip_dirty_ids_device", "chisel_hip_mesh_shell_plan",
     "chisel_hip_shell_volume", "chisel_hip_set_profiling", "chisel_hip_get_profile", "chisel_hip_get_launch_stats", "chisel_hip_pool_info", "chisel_hip_mc_tables", "chisel_hip_mesh_cube_values", "chisel_hip_interpolate_vertex", "chisel_hip_raycast", "chisel_hip_chunk_owner", "chisel_hip_frustum", "chisel_hip_frustum_from_vectors", "chisel_hip_create_group", "chisel_hip_render_view",
     "chisel_hip_query_points", "chisel_hip_cast_rays", "chisel_hip_align_terms", "chisel_hip_align_solve", "chisel_hip_align_depth",
-    "chisel_hip_merge_map", "chisel_hip_deintegrate_depth", "chisel_hip_deintegrate_batch",
+    "chisel_hip_merge_map", "chisel_hip_deintegrate_depth", "chisel_hip_deintegrate_batch", "chisel_hip_distance_field",
 ]
 # the device self-tests and debug read-outs include/chisel_hip_selftest.h declares
 SELFTEST_EXPORTS = [
@@ -275,6 +283,7 @@ def load_library():
                         ("chisel_hip_merge_map", [vp, vp, f32p, C.POINTER(MergeStats)]),
                         ("chisel_hip_deintegrate_depth", [vp, C.POINTER(DepthFrame), C.c_int, C.POINTER(DeintegrateStats), i32p, C.c_int]),
                         ("chisel_hip_deintegrate_batch", [vp, C.c_int, C.POINTER(DepthFrame), C.c_int, C.POINTER(DeintegrateStats), i32p, C.c_int]),
+                        ("chisel_hip_distance_field", [vp, C.POINTER(DistanceWindow), vp, vp, vp, C.c_int]),
                         ("chisel_hip_kat_color_fresh", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_kat_color_any", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_debug_cloud_stats", [vp, i64p]),

@@ -586,6 +586,51 @@ class Chisel:
         check(self.L.chisel_hip_cast_rays(self.h, ptr(rays), n, float(step), *[ptr(res[name]) for name, _, _ in self._RAY_OUTPUTS], 0))
         return res
 
+    _DISTANCE_OUTPUTS = (("state", np.uint8), ("dist2", np.int32), ("distance", np.float32))
+
+    def DistanceWindow(self, lo_m, hi_m):
+        """(origin, dims) of the voxels whose centres ((g + 0.5) res per axis, g the global voxel index) lie in the closed metric box
+        lo_m ... hi_m: what DistanceField takes.  Computed in float64; a box that holds no centre on some axis gives a dim below 1."""
+        res = float(np.float32(self.voxel_resolution))
+        lo = np.ceil(np.asarray(lo_m, np.float64) / res - 0.5).astype(np.int64)
+        hi = np.floor(np.asarray(hi_m, np.float64) / res - 0.5).astype(np.int64)
+        return tuple(int(v) for v in lo), tuple(int(v) for v in hi - lo + 1)
+
+    def DistanceField(self, origin, dims, radius, unknown_is_obstacle=False, surface_offset=0.0, state=True, dist2=True, distance=False, out=None):
+        """chisel_hip_distance_field: over the window of dims = (nx, ny, nz) voxels whose first voxel has the global index `origin`
+        (chunk id * N + voxel coordinate per axis), the truncated exact Euclidean distance transform of DESIGN.md 3.11.
+        -> {"state": uint8 -- 0 unknown, 1 free, 2 occupied (observed with sdf < surface_offset) --, "dist2": int32, the squared
+        distance in voxels to the nearest obstacle of the map within `radius` (1 ... 64), -1 without one, "distance": float32, metres,
+        +inf without one}: numpy arrays of shape (nz, ny, nx), None for what was not asked for.  Obstacles are the occupied voxels,
+        with unknown_is_obstacle the unknown ones too.
+        `out`: a dict of contiguous torch CUDA tensors of that shape and those types: exactly the outputs named in it are filled in
+        place on the map's stream, nothing is waited for; it is returned."""
+        w = capi.DistanceWindow()
+        w.origin[:] = [int(v) for v in origin]
+        w.dims[:] = [int(v) for v in dims]
+        w.radius, w.unknown_is_obstacle, w.surface_offset = int(radius), int(bool(unknown_is_obstacle)), float(surface_offset)
+        shape = (int(dims[2]), int(dims[1]), int(dims[0]))
+        if out is not None:
+            import torch
+            unknown = set(out) - {name for name, _ in self._DISTANCE_OUTPUTS}
+            assert not unknown, "out: unknown outputs %s" % sorted(unknown)
+            ptrs = []
+            for name, dtype in self._DISTANCE_OUTPUTS:
+                t = out.get(name)
+                want = {np.uint8: torch.uint8, np.int32: torch.int32, np.float32: torch.float32}[dtype]
+                assert t is None or (t.is_cuda and t.dtype == want and t.is_contiguous() and tuple(t.shape) == shape), \
+                    "out[%r]: a contiguous %s CUDA tensor of shape %s" % (name, want, shape)
+                ptrs.append(t.data_ptr() if t is not None and t.numel() else None)
+            check(self.L.chisel_hip_distance_field(self.h, C.byref(w), *ptrs, 1))
+            self._keep = [out]
+            return out
+        asked = {"state": state, "dist2": dist2, "distance": distance}
+        ok = all(d >= 1 for d in shape) and shape[0] * shape[1] * shape[2] <= 1 << 30  # (a window the library refuses by its size allocates nothing here either)
+        res = {name: (np.empty(shape if ok else (0, 0, 0), dtype) if asked[name] else None) for name, dtype in self._DISTANCE_OUTPUTS}
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        check(self.L.chisel_hip_distance_field(self.h, C.byref(w), *[ptr(res[name]) for name, _ in self._DISTANCE_OUTPUTS], 0))
+        return res
+
     def AlignTerms(self, depth, pose, camera, max_residual=0.0, out=None):
         """chisel_hip_align_terms: the normal equations of one Gauss-Newton step that aligns the depth image (numpy, or a torch CUDA
         tensor used in place) taken by `camera` at the guess `pose` (camera -> world) to the map.  -> (32,) float64: [0..20] the upper

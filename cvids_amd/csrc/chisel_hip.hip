@@ -41,6 +41,8 @@
 #include "kernels_cloud.h"
 #include "kernels_merge.h"
 #include "kernels_deintegrate.h"
+#include "distance_checks.h"
+#include "kernels_distance.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
 #include "kernels_stereo_prep.h"
@@ -430,6 +432,12 @@ struct chisel_hip_map {
     std::vector<hipEvent_t> event_pool;
     double prof_ms[CHISEL_HIP_NUM_KERNELS] = {};
     int64_t prof_launches[CHISEL_HIP_NUM_KERNELS] = {};
+    struct DistanceMemory {                                            // chisel_hip_distance_field (host_distance.h), allocated on first use, grown on demand
+        DeviceBuffer<unsigned long long> bits;                         // one obstacle bit per voxel of the widened window
+        DeviceBuffer<unsigned short> g1, g2;                           // the squared distances after the passes along x and along y
+        DeviceBuffer<float> table;                                     // [64^2 + 1] metres by squared voxel distance ...
+        PinnedBuffer<float> table_host;                                // ... as the host computed it (written once, before its one upload)
+    } distance_mem;
 };
 
 namespace {
@@ -3034,4 +3042,5 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 #include "host_align.h"
 #include "host_merge.h"
 #include "host_deintegrate.h"
+#include "host_distance.h"
 #include "host_selftest.h"

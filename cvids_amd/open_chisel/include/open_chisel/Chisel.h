@@ -917,6 +917,31 @@ class Chisel {  // Chisel.h:38-230
         if (collectEmptied && stats.chunks_emptied > 0) hip_check(chisel_hip_garbage_collect(map, ids.data(), (int)stats.chunks_emptied));
         return stats;
     }
+    // Not in the reference: how far the nearest obstacle is from every voxel of a window, and whether the voxel was ever observed
+    // (chisel_hip_distance_field: a truncated, exact Euclidean distance transform in squared voxel units) -- what a planner asks of a box
+    // around the robot.  origin: the global voxel index (chunk id * chunk size + voxel coordinate) of the window's first voxel; dims:
+    // (nx, ny, nz); element (x, y, z) of every output sits at (z ny + y) nx + x.  A null vector is not asked for; the others are resized.
+    // state: 0 unknown, 1 free, 2 occupied (observed with sdf < surfaceOffset); dist2: squared voxels to the nearest obstacle within
+    // `radius` (1 ... 64), -1 without one; distance: metres, +inf without one.  The map is only read.
+    void DistanceField(const Eigen::Vector3i &origin, const Eigen::Vector3i &dims, int radius, bool unknownIsObstacle, float surfaceOffset,
+                       std::vector<uint8_t> *state, std::vector<int32_t> *dist2, std::vector<float> *distance) const {
+        chisel_hip_distance_window w;
+        for (int a = 0; a < 3; a++) {
+            w.origin[a] = origin(a);
+            w.dims[a] = dims(a);
+        }
+        w.radius = radius;
+        w.unknown_is_obstacle = unknownIsObstacle ? 1 : 0;
+        w.surface_offset = surfaceOffset;
+        const bool sized = dims(0) >= 1 && dims(1) >= 1 && dims(2) >= 1 && (int64_t)dims(0) * dims(1) <= (1ll << 30) &&
+                           (int64_t)dims(0) * dims(1) * dims(2) <= (1ll << 30);  // (what is not is refused below)
+        const size_t n = sized ? (size_t)dims(0) * dims(1) * dims(2) : 1;
+        if (state) state->resize(n);
+        if (dist2) dist2->resize(n);
+        if (distance) distance->resize(n);
+        hip_check(chisel_hip_distance_field(map, &w, state ? state->data() : nullptr, dist2 ? dist2->data() : nullptr,
+                                            distance ? distance->data() : nullptr, 0));
+    }
     chisel_hip_map *HipMap() const { return map; }
 
   protected:

@@ -46,7 +46,8 @@ extern "C" {
  *      (chisel_hip_shell_plan_queue, _import_shells_fixed, _shell_commit), the stereo matcher (chisel_hip_stereo_*)
  *   3  chisel_hip_export_chunks, _import_ghost_chunks, _export_shells, _import_ghost_shells removed; later additions within 3 (nothing
  *      removed or re-typed): chisel_hip_render_view, chisel_hip_query_points, chisel_hip_cast_rays, chisel_hip_align_terms,
- *      chisel_hip_align_solve, chisel_hip_align_depth, chisel_hip_merge_map, chisel_hip_deintegrate_depth, chisel_hip_deintegrate_batch (no slot in
+ *      chisel_hip_align_solve, chisel_hip_align_depth, chisel_hip_merge_map, chisel_hip_deintegrate_depth, chisel_hip_deintegrate_batch,
+ *      chisel_hip_distance_field (no slot in
  *      the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
 #define CHISEL_HIP_ABI_VERSION 3
 
@@ -581,6 +582,32 @@ typedef struct {
  * NaN step or a null t_hit.  DESIGN.md "Querying points and rays" has the definition to the bit. */
 int chisel_hip_cast_rays(chisel_hip_map *map, const chisel_hip_ray *rays, int64_t n, float step, float *t_hit, uint8_t *status,
                          float *normals /* 3 n */, float *colors /* 3 n */, int on_device);
+/* A window of voxels for chisel_hip_distance_field.  A global voxel index per axis is chunk_id * N + voxel_coordinate (floor division
+ * for negative indices); origin is the index of the window's first voxel, dims = (nx, ny, nz) its extent, radius R the reach of the
+ * transform in voxels (1 ... 64). */
+typedef struct {
+    int origin[3];
+    int dims[3];
+    int radius;
+    int unknown_is_obstacle;   /* nonzero: unknown voxels are obstacles too */
+    float surface_offset;      /* metres: a voxel is occupied when it is observed with sdf < surface_offset */
+} chisel_hip_distance_window;   /* 36 bytes */
+/* Not in the reference: how far the nearest obstacle is from every voxel of a window, and whether the voxel was ever observed -- what
+ * a planner asks of a box around the robot.  A truncated, exact Euclidean distance transform in squared voxel units (integers: the
+ * answer does not depend on the algorithm).  Element (x, y, z) of every output sits at (z ny + y) nx + x.
+ *   state (uint8)     0 unknown: the voxel's chunk is not resident (or its id is outside the addressable range), or its weight reads
+ *                     as unobserved by ChunkManager::GetSDF's rule (src/ChunkManager.cpp:489); 2 occupied: observed and
+ *                     sdf < surface_offset (one fp32 compare); 1 free: observed otherwise
+ *   dist2 (int32)     min |v - o|^2 over the obstacle voxels o of the MAP (not of the window: the seeds are read over the window
+ *                     widened by R on every side) with |v - o|^2 <= R^2; -1 where there is none.  Obstacles: the occupied voxels,
+ *                     with unknown_is_obstacle the unknown ones too
+ *   distance (float)  (float)(sqrt((double)dist2) * (double)voxel_resolution), +inf where dist2 is -1; read from a table the host computes
+ * Any of the three may be NULL, not all.  on_device, the stream, groups and shards: as chisel_hip_query_points.  The map is only read;
+ * the scratch is kept in the map, grown on demand and freed with it.  CHISEL_HIP_ERR_INVALID (nothing is touched): null window, no
+ * output, a dimension < 1, R < 1 or R > 64, a NaN surface_offset, a coordinate of the widened window beyond +-2^30;
+ * CHISEL_HIP_ERR_UNSUPPORTED: a widened window of more than 2^30 voxels.  DESIGN.md 3.11 "Distance field" has the definition. */
+int chisel_hip_distance_field(chisel_hip_map *map, const chisel_hip_distance_window *window, uint8_t *state, int32_t *dist2, float *distance,
+                              int on_device);
 /* Not in the reference: the normal equations of one Gauss-Newton step that aligns a depth frame to the map (point-to-surface against the
  * TSDF; DESIGN.md "Aligning a frame to the map" has the definition to the bit).  frame->pose is the guess, camera -> world.  Pixel i
  * with depth z is VALID when z is finite and near <= z <= far; its point p = o + z d lies on chisel_hip_render_view's ray of that pixel;
