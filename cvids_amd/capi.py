@@ -106,6 +106,20 @@ class DistanceWindow(C.Structure):
 
 DISTANCE_MAX_RADIUS = 64  # chisel_hip_distance_field's largest radius, voxels
 
+
+class MeshRequest(C.Structure):
+    """chisel_hip_mesh_request (include/chisel_hip.h): the selection and the marker colours of chisel_hip_gather_meshes, 56 bytes"""
+    _fields_ = [("ids_xyz", C.POINTER(C.c_int)), ("n_ids", C.c_int64), ("marker_colors", C.c_int), ("light0", C.c_float * 3),
+                ("light1", C.c_float * 3), ("diffuse", C.c_float), ("ambient", C.c_float)]
+
+
+class MeshTotals(C.Structure):
+    """chisel_hip_mesh_totals (include/chisel_hip.h): what a selection of chisel_hip_gather_meshes holds, 48 bytes"""
+    _fields_ = [(n, C.c_int64) for n in ("meshes", "meshes_nonempty", "vertices", "grids", "arenas_read", "tiles")]
+
+
+GATHER_TILE_FLOATS = 4096  # CHISEL_HIP_GATHER_TILE_FLOATS
+
 ALIGN_CONVERGED, ALIGN_ITERATION_LIMIT, ALIGN_TOO_FEW_PIXELS, ALIGN_DEGENERATE = 0, 1, 2, 3  # CHISEL_HIP_ALIGN_*
 ALIGN_STATUS = {0: "CONVERGED", 1: "ITERATION_LIMIT", 2: "TOO_FEW_PIXELS", 3: "DEGENERATE"}
 
@@ -129,6 +143,7 @@ EXPORTS = [
     "chisel_hip_shell_volume", "chisel_hip_set_profiling", "chisel_hip_get_profile", "chisel_hip_get_launch_stats", "chisel_hip_pool_info", "chisel_hip_mc_tables", "chisel_hip_mesh_cube_values", "chisel_hip_interpolate_vertex", "chisel_hip_raycast", "chisel_hip_chunk_owner", "chisel_hip_frustum", "chisel_hip_frustum_from_vectors", "chisel_hip_create_group", "chisel_hip_render_view",
     "chisel_hip_query_points", "chisel_hip_cast_rays", "chisel_hip_align_terms", "chisel_hip_align_solve", "chisel_hip_align_depth",
     "chisel_hip_merge_map", "chisel_hip_deintegrate_depth", "chisel_hip_deintegrate_batch", "chisel_hip_distance_field",
+    "chisel_hip_gather_meshes", "chisel_hip_gather_meshes_size", "chisel_hip_save_ply_binary",
 ]
 # the device self-tests and debug read-outs include/chisel_hip_selftest.h declares
 SELFTEST_EXPORTS = [
@@ -284,6 +299,10 @@ def load_library():
                         ("chisel_hip_deintegrate_depth", [vp, C.POINTER(DepthFrame), C.c_int, C.POINTER(DeintegrateStats), i32p, C.c_int]),
                         ("chisel_hip_deintegrate_batch", [vp, C.c_int, C.POINTER(DepthFrame), C.c_int, C.POINTER(DeintegrateStats), i32p, C.c_int]),
                         ("chisel_hip_distance_field", [vp, C.POINTER(DistanceWindow), vp, vp, vp, C.c_int]),
+                        ("chisel_hip_gather_meshes", [vp, C.POINTER(MeshRequest), C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.c_int, i64p, i32p,
+                                                      C.POINTER(MeshTotals)]),
+                        ("chisel_hip_gather_meshes_size", [vp, C.POINTER(MeshRequest), C.POINTER(MeshTotals)]),
+                        ("chisel_hip_save_ply_binary", [vp, C.c_char_p]),
                         ("chisel_hip_kat_color_fresh", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_kat_color_any", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_debug_cloud_stats", [vp, i64p]),

@@ -149,6 +149,17 @@ class PointCloud:
         self.colors = None
 
 
+def marker_light_dir():
+    """ChiselServer::FillMarkerTopicWithMeshes' lightDir (chisel_ros/src/ChiselServer.cpp:652-655): (0.8, -0.2, 0.7) normalised twice
+    with Eigen's Vector3f::normalize -- v / sqrt(squaredNorm), the sum of squares in order, every step in fp32 -> 3 float32"""
+    v = np.array([0.8, -0.2, 0.7], np.float32)
+    for _ in range(2):
+        sq = v * v
+        n2 = np.float32(np.float32(sq[0] + sq[1]) + sq[2])
+        v = (v / np.sqrt(n2)).astype(np.float32)
+    return tuple(float(x) for x in v)
+
+
 class Chisel:
     """chisel::Chisel (Chisel.h:38-230) + the ChunkManager queries its callers use."""
 
@@ -630,6 +641,113 @@ class Chisel:
         ptr = lambda a: a.ctypes.data if a is not None else None
         check(self.L.chisel_hip_distance_field(self.h, C.byref(w), *[ptr(res[name]) for name, _ in self._DISTANCE_OUTPUTS], 0))
         return res
+
+    _GATHER_OUTPUTS = (("vertices", 3), ("normals", 3), ("colors", 3), ("rgba", 4), ("grids", 3))
+    # ChiselServer's marker lights (chisel_ros/src/ChiselServer.cpp:652-655, :657-658): lightDir normalised twice, lightDir1 as it stands
+    MARKER_LIGHTS = {"light0": marker_light_dir(), "light1": (-0.5, 0.2, 0.2), "diffuse": 0.5, "ambient": 0.2}
+
+    def _mesh_request(self, ids, lights):
+        """-> (chisel_hip_mesh_request, what it points at)"""
+        req = capi.MeshRequest()
+        keep = None
+        if ids is not None:
+            keep = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1, 3))
+            req.ids_xyz = keep.ctypes.data_as(C.POINTER(C.c_int))
+            req.n_ids = len(keep)
+        if lights is not None:
+            req.marker_colors = 1
+            req.light0[:] = [float(v) for v in lights["light0"]]
+            req.light1[:] = [float(v) for v in lights["light1"]]
+            req.diffuse, req.ambient = float(lights["diffuse"]), float(lights["ambient"])
+        return req, keep
+
+    @staticmethod
+    def _totals_dict(t):
+        return {name: int(getattr(t, name)) for name, _ in capi.MeshTotals._fields_}
+
+    def GatherMeshesSize(self, ids=None, lights=None):
+        """chisel_hip_gather_meshes_size: the totals of a selection (GatherMeshes) without a launch -> {"meshes", "meshes_nonempty",
+        "vertices", "grids", "arenas_read", "tiles"}"""
+        req, keep = self._mesh_request(ids, lights)
+        t = capi.MeshTotals()
+        rc = self.L.chisel_hip_gather_meshes_size(self.h, C.byref(req), C.byref(t))
+        if rc == 4:
+            raise KeyError(self.L.chisel_hip_last_error().decode(errors="replace"))
+        check(rc)
+        return self._totals_dict(t)
+
+    def GatherMeshes(self, ids=None, normals=True, colors=None, rgba=False, grids=True, lights=None, out=None):
+        """chisel_hip_gather_meshes: the chunk meshes of `ids` ((n, 3), in that order, duplicates allowed; None: every mesh in
+        GetMeshIDs' order) packed into contiguous arrays by one launch.  -> {"vertices": (V, 3), "normals": (V, 3), "colors":
+        (V, 3), "rgba": (V, 4), "grids": (G, 3)} float32 numpy arrays, None for what was not asked for (colors=None: asked for iff
+        the map holds colour), plus "table": (n, 4) int64 -- first vertex, vertices, first grid, grids of every mesh --, "ids":
+        (n, 3) int32 and "totals".  Every float is the one GetMesh returns for that chunk.  rgba: FillMarkerTopicWithMeshes'
+        colours with `lights` (None: Chisel.MARKER_LIGHTS, ChiselServer's own).
+        `out`: a dict of contiguous torch CUDA float32 tensors of shape (rows, 3) -- (rows, 4) for "rgba" -- with at least V
+        ("grids": G) rows: exactly the outputs named in it are filled in place on the map's stream, nothing is waited for; it is
+        returned with "table", "ids" and "totals" (numpy, host) added.  KeyError for an id without a mesh."""
+        want_rgba = rgba or (out is not None and "rgba" in out)
+        req, keep = self._mesh_request(ids, (lights if lights is not None else self.MARKER_LIGHTS) if want_rgba else None)
+        t = capi.MeshTotals()
+
+        def call(cap_v, cap_g, ptrs, on_device, table, ids_out):
+            rc = self.L.chisel_hip_gather_meshes(self.h, C.byref(req), cap_v, cap_g, *ptrs, on_device,
+                                                 table.ctypes.data_as(C.POINTER(C.c_int64)) if table is not None else None,
+                                                 ids_out.ctypes.data_as(C.POINTER(C.c_int)) if ids_out is not None else None, C.byref(t))
+            if rc == 4:
+                raise KeyError(self.L.chisel_hip_last_error().decode(errors="replace"))
+            check(rc)
+
+        size = self.GatherMeshesSize(ids)
+        n, V, G = size["meshes"], size["vertices"], size["grids"]
+        table, ids_out = np.zeros((n, 4), np.int64), np.zeros((n, 3), np.int32)
+        if out is not None:
+            import torch
+            unknown = set(out) - {name for name, _ in self._GATHER_OUTPUTS}
+            assert not unknown, "out: unknown outputs %s" % sorted(unknown)
+            assert out, "out: no output named"
+            ptrs, cap_v, cap_g = [], None, None
+            for name, width in self._GATHER_OUTPUTS:
+                tns = out.get(name)
+                assert tns is None or (tns.is_cuda and tns.dtype == torch.float32 and tns.is_contiguous() and tns.dim() == 2 and tns.shape[1] == width), \
+                    "out[%r]: a contiguous float32 CUDA tensor of shape (rows, %d)" % (name, width)
+                if tns is not None:
+                    rows = int(tns.shape[0])
+                    if name == "grids":
+                        cap_g = rows
+                    else:
+                        cap_v = rows if cap_v is None else min(cap_v, rows)
+                # (an empty tensor has no address: it stands for its array only when there is nothing to write)
+                ptrs.append(tns.data_ptr() if tns is not None and tns.numel() else None)
+            if all(p is None for p in ptrs):
+                assert V <= (cap_v if cap_v is not None else V) and G <= (cap_g if cap_g is not None else G), "out: tensors without room"
+                res = dict(out)
+                res.update(table=table, ids=ids_out, totals=size)
+                return res
+            call(cap_v if cap_v is not None else V, cap_g if cap_g is not None else G, ptrs, 1, table, ids_out)
+            self._keep = [out]
+            res = dict(out)
+            res.update(table=table, ids=ids_out, totals=self._totals_dict(t))
+            return res
+        if colors is None:
+            colors = self.use_color
+        asked = {"vertices": True, "normals": normals, "colors": colors, "rgba": rgba, "grids": grids}
+        res = {name: (np.empty((G if name == "grids" else V, width), np.float32) if asked[name] else None) for name, width in self._GATHER_OUTPUTS}
+        # (an array without rows has nothing to receive: the library is told of the others)
+        ptrs = [res[name].ctypes.data if res[name] is not None and res[name].size else None for name, _ in self._GATHER_OUTPUTS]
+        if any(p is not None for p in ptrs):
+            call(V, G, ptrs, 0, table, ids_out)
+            size = self._totals_dict(t)
+        res.update(table=table, ids=ids_out, totals=size)
+        return res
+
+    def SaveAllMeshesToPLYBinary(self, filename):
+        """chisel_hip_save_ply_binary: SaveAllMeshesToPLY's elements, properties and vertex order as binary_little_endian 1.0"""
+        rc = self.L.chisel_hip_save_ply_binary(self.h, str(filename).encode())
+        if rc == 6:
+            return False
+        check(rc)
+        return True
 
     def AlignTerms(self, depth, pose, camera, max_residual=0.0, out=None):
         """chisel_hip_align_terms: the normal equations of one Gauss-Newton step that aligns the depth image (numpy, or a torch CUDA

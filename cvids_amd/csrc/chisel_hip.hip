@@ -43,6 +43,8 @@
 #include "kernels_deintegrate.h"
 #include "distance_checks.h"
 #include "kernels_distance.h"
+#include "gather_checks.h"
+#include "kernels_gather.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
 #include "kernels_stereo_prep.h"
@@ -208,6 +210,18 @@ struct ProfEvent {
 enum LaunchStat { LS_VPL2, LS_VPL4, LS_VPL4_SPLIT, LS_CULL_NARROW, LS_CULL_WIDE, LS_CULL, LS_INLINE, LS_INTEGRATE, LS_DEFERRED, LS_REPLAYED, LS_COUNT };
 static_assert(LS_COUNT == CHISEL_HIP_NUM_LAUNCH_STATS, "launch_stats: one name per word of chisel_hip_get_launch_stats");
 static_assert(CHISEL_FRONT_SETS >= 3 && (CHISEL_PENDING_RING & (CHISEL_PENDING_RING - 1)) == 0 && CHISEL_PENDING_RING >= 4, "front-half rings");
+// The host side of a per-call table's upload lives until the copy is over: a block of pinned memory is taken again once its event has
+// passed (take_upload), so that a call that waits for nothing can follow one whose copy is still queued.
+template <class T>
+struct UploadBlock {
+    PinnedBuffer<T> host;
+    size_t capacity = 0;                                               // entries
+    hipEvent_t copied = nullptr;
+    UploadBlock() = default;
+    UploadBlock(UploadBlock &&o) noexcept : host(std::move(o.host)), capacity(o.capacity), copied(o.copied) { o.copied = nullptr; o.capacity = 0; }
+    UploadBlock &operator=(UploadBlock &&) = delete;
+    ~UploadBlock() { if (copied) (void)hipEventDestroy(copied); }
+};
 struct chisel_hip_map {
     // a group handle (chisel_hip_create_group, host_group.h): no device state of its own, one shard map per GPU
     bool is_group = false;
@@ -413,19 +427,13 @@ struct chisel_hip_map {
         DeviceBuffer<unsigned long long> words;                        // [DS_WORDS + launch sets] the stats and the list lengths: zeroed by the call's one memset
         PinnedBuffer<unsigned long long> host;                         // [DS_WORDS] where the stats reach the host
         DeviceBuffer<DeintegrateBatchEntry> table;                     // [frames of the call] a batch's own
-        // The host side of a table's upload lives until the copy is over: a block is taken again once its event has passed, so that
-        // a call that waits for nothing can follow one whose copy is still queued.
-        struct TableUpload {
-            PinnedBuffer<DeintegrateBatchEntry> host;
-            size_t capacity = 0;                                       // entries
-            hipEvent_t copied = nullptr;
-            TableUpload() = default;
-            TableUpload(TableUpload &&o) noexcept : host(std::move(o.host)), capacity(o.capacity), copied(o.copied) { o.copied = nullptr; o.capacity = 0; }
-            TableUpload &operator=(TableUpload &&) = delete;
-            ~TableUpload() { if (copied) (void)hipEventDestroy(copied); }
-        };
+        using TableUpload = UploadBlock<DeintegrateBatchEntry>;        // (the host side of a table's upload: take_upload)
         std::vector<TableUpload> uploads;
     } deintegrate_mem;
+    struct GatherMemory {                                              // chisel_hip_gather_meshes (host_gather.h), allocated on first use, grown on demand
+        DeviceBuffer<GatherSeg> table;                                 // [segments of the call] the segment table as the kernel reads it
+        std::vector<UploadBlock<GatherSeg>> uploads;                   // ... and the host side of its uploads
+    } gather_mem;
     // profiling
     bool profiling = false;
     std::vector<ProfEvent> prof_live;
@@ -601,6 +609,30 @@ int grow_buffer(DeviceBuffer<T> &buf, size_t n, hipStream_t stream, T **view = n
     const hipError_t e = buf.alloc(n);
     if (view) *view = buf.get();
     HIP_TRY(e);
+    return CHISEL_HIP_OK;
+}
+
+// a block of pinned memory for n entries of a per-call table whose last upload is over (a new one when all are busy)
+template <class T>
+int take_upload(std::vector<UploadBlock<T>> &U, size_t n, UploadBlock<T> **out) {
+    UploadBlock<T> *u = nullptr;
+    for (auto &c : U)
+        if (hipEventQuery(c.copied) == hipSuccess) {
+            u = &c;
+            break;
+        }
+    (void)hipGetLastError();  // (hipErrorNotReady is not an error)
+    if (!u) {
+        U.emplace_back();
+        u = &U.back();
+        HIP_TRY(hipEventCreateWithFlags(&u->copied, hipEventDisableTiming));
+    }
+    if (u->capacity < n) {
+        u->capacity = 0;
+        HIP_TRY(u->host.alloc(n));
+        u->capacity = n;
+    }
+    *out = u;
     return CHISEL_HIP_OK;
 }
 
@@ -3043,4 +3075,5 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 #include "host_merge.h"
 #include "host_deintegrate.h"
 #include "host_distance.h"
+#include "host_gather.h"
 #include "host_selftest.h"

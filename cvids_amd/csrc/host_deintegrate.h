@@ -80,30 +80,6 @@ int finish(chisel_hip_map *m, const DeintegrateBatchView &G, bool host_images, c
     return CHISEL_HIP_OK;
 }
 
-// a block of pinned memory for n table entries whose last upload is over (a new one when all are busy)
-int take_upload(chisel_hip_map *m, size_t n, chisel_hip_map::DeintegrateMemory::TableUpload **out) {
-    std::vector<chisel_hip_map::DeintegrateMemory::TableUpload> &U = m->deintegrate_mem.uploads;
-    chisel_hip_map::DeintegrateMemory::TableUpload *u = nullptr;
-    for (auto &c : U)
-        if (hipEventQuery(c.copied) == hipSuccess) {
-            u = &c;
-            break;
-        }
-    (void)hipGetLastError();  // (hipErrorNotReady is not an error)
-    if (!u) {
-        U.emplace_back();
-        u = &U.back();
-        HIP_TRY(hipEventCreateWithFlags(&u->copied, hipEventDisableTiming));
-    }
-    if (u->capacity < n) {
-        u->capacity = 0;
-        HIP_TRY(u->host.alloc(n));
-        u->capacity = n;
-    }
-    *out = u;
-    return CHISEL_HIP_OK;
-}
-
 inline size_t stage_floats_of(const chisel_hip_depth_frame &f) { return f.on_device ? 0 : (((size_t)f.width * f.height + 3) & ~(size_t)3); }  // (16-byte sections)
 
 }  // namespace deintegrate
@@ -173,7 +149,7 @@ extern "C" int chisel_hip_deintegrate_batch(chisel_hip_map *m, int n, const chis
     if (!rc && stage_floats) rc = grow_buffer(m->frame_stage, stage_floats, m->stream);
     if (rc) return rc;
     chisel_hip_map::DeintegrateMemory::TableUpload *up = nullptr;
-    rc = deintegrate::take_upload(m, (size_t)n, &up);
+    rc = take_upload(O.uploads, (size_t)n, &up);  // (chisel_hip.hip)
     if (rc) return rc;
 
     // ---- the table: a host image of set s has the s-th use of its place in the staging buffer

@@ -505,15 +505,12 @@ int query_sdf(chisel_hip_map *m, const float pos[3], int with_gradient, double *
 std::vector<uint64_t> sorted_mesh_keys(const chisel_hip_map *m) {
     std::vector<uint64_t> keys;
     keys.reserve(m->meshes.size());
-    for (const auto &kv : m->meshes) keys.push_back(kv.first);
-    std::sort(keys.begin(), keys.end(), [](uint64_t a, uint64_t b) {
-        int ax, ay, az, bx, by, bz;
-        unpack_id(a, ax, ay, az);
-        unpack_id(b, bx, by, bz);
-        if (ax != bx) return ax < bx;
-        if (ay != by) return ay < by;
-        return az < bz;
-    });
+    // pack_id keeps x in the low 21 bits and z in the high ones, each biased to be non-negative: with the x and z fields exchanged the
+    // keys sort as plain integers (an involution: the same exchange gives the keys back)
+    const auto swap_xz = [](uint64_t k) { return ((k & 0x1FFFFFull) << 42) | (k & (0x1FFFFFull << 21)) | ((k >> 42) & 0x1FFFFFull); };
+    for (const auto &kv : m->meshes) keys.push_back(swap_xz(kv.first));
+    std::sort(keys.begin(), keys.end());
+    for (uint64_t &k : keys) k = swap_xz(k);
     return keys;
 }
 

@@ -601,6 +601,64 @@ class ChunkManager {  // ChunkManager.h:57-216 over one chisel_hip_map
         }
         return allMeshes;
     }
+    // Not in the reference as a call: what ChiselServer::FillMarkerTopicWithMeshes (chisel_ros/src/ChiselServer.cpp:613-716) collects by
+    // walking GetAllMeshes() -- every chunk mesh's vertices and grids in one buffer, every vertex coloured from the mesh colours or
+    // from two Lambert terms of its normal -- as ONE call (chisel_hip_gather_meshes) instead of two calls and three copies per mesh.
+    struct MarkerLights {  // ChiselServer.cpp:652-658: lightDir normalised twice, lightDir1 as it stands, 0.5, 0.2
+        Vec3 light0, light1;
+        float diffuse = 0.5f, ambient = 0.2f;
+        MarkerLights() : light0(0.8f, -0.2f, 0.7f), light1(-0.5f, 0.2f, 0.2f) {
+            light0.normalize();
+            light0.normalize();
+        }
+    };
+    struct PackedMeshes {
+        std::vector<float> vertices, normals, colors, rgba, grids;  // 3 floats per entry, rgba 4; colors only on a map with colour
+        std::vector<int64_t> table;                                  // 4 per mesh: first vertex, vertices, first grid, grids
+        std::vector<int> ids;                                        // 3 per mesh
+        chisel_hip_mesh_totals totals{};
+    };
+    // ids empty: every mesh, in ascending id order; otherwise these chunks' meshes in this order (std::out_of_range for one without a
+    // mesh).  wantRgba: the marker colours, with `lights`.  Vertices and (on a map with colour) colours are always returned.
+    PackedMeshes GatherMeshes(const ChunkIDList &ids = ChunkIDList(), bool wantNormals = true, bool wantRgba = false, bool wantGrids = true,
+                              const MarkerLights &lights = MarkerLights()) const {
+        std::vector<int> flat;
+        for (const ChunkID &c : ids) {
+            flat.push_back(c(0)); flat.push_back(c(1)); flat.push_back(c(2));
+        }
+        chisel_hip_mesh_request req{};
+        req.ids_xyz = flat.empty() ? nullptr : flat.data();
+        req.n_ids = (int64_t)ids.size();
+        req.marker_colors = wantRgba ? 1 : 0;
+        for (int a = 0; a < 3; a++) {
+            req.light0[a] = lights.light0(a);
+            req.light1[a] = lights.light1(a);
+        }
+        req.diffuse = lights.diffuse;
+        req.ambient = lights.ambient;
+        PackedMeshes out;
+        int rc = chisel_hip_gather_meshes_size(map, &req, &out.totals);
+        if (rc == CHISEL_HIP_ERR_NOT_FOUND) throw std::out_of_range("ChunkManager::GatherMeshes");
+        hip_check(rc);
+        const size_t V = (size_t)out.totals.vertices, G = (size_t)out.totals.grids;
+        out.table.resize((size_t)out.totals.meshes * 4);
+        out.ids.resize((size_t)out.totals.meshes * 3);
+        out.vertices.resize(V * 3);
+        if (wantNormals) out.normals.resize(V * 3);
+        if (useColor) out.colors.resize(V * 3);
+        if (wantRgba) out.rgba.resize(V * 4);
+        if (wantGrids) out.grids.resize(G * 3);
+        auto ptr = [](std::vector<float> &a) { return a.empty() ? nullptr : a.data(); };
+        if (V == 0 && out.grids.empty()) {  // nothing to copy: the bookkeeping alone (no output array may be named)
+            for (int64_t i = 0; i < out.totals.meshes && !flat.empty(); i++)
+                for (int a = 0; a < 3; a++) out.ids[(size_t)(3 * i + a)] = flat[(size_t)(3 * i + a)];
+            if (flat.empty() && out.totals.meshes) hip_check(chisel_hip_list_meshes(map, out.ids.data(), out.totals.meshes, &out.totals.meshes));
+            return out;
+        }
+        hip_check(chisel_hip_gather_meshes(map, &req, out.totals.vertices, out.totals.grids, ptr(out.vertices), ptr(out.normals), ptr(out.colors), ptr(out.rgba),
+                                           ptr(out.grids), 0, out.table.data(), out.ids.data(), &out.totals));
+        return out;
+    }
     bool HasMesh(const ChunkID &id) const {
         const int v[3] = {id(0), id(1), id(2)};
         int64_t nv = 0, ng = 0;
@@ -840,6 +898,14 @@ class Chisel {  // Chisel.h:38-230
     }
     bool SaveAllMeshesToPLY(const std::string &filename) {  // Chisel.cpp:69-105
         const int rc = chisel_hip_save_ply(map, filename.c_str());
+        if (rc == CHISEL_HIP_ERR_IO) return false;
+        hip_check(rc);
+        return true;
+    }
+    // the same elements, properties and vertex order as "format binary_little_endian 1.0" (chisel_hip_save_ply_binary: one gather, no
+    // per-mesh copies)
+    bool SaveAllMeshesToPLYBinary(const std::string &filename) {
+        const int rc = chisel_hip_save_ply_binary(map, filename.c_str());
         if (rc == CHISEL_HIP_ERR_IO) return false;
         hip_check(rc);
         return true;

@@ -47,8 +47,8 @@ extern "C" {
  *   3  chisel_hip_export_chunks, _import_ghost_chunks, _export_shells, _import_ghost_shells removed; later additions within 3 (nothing
  *      removed or re-typed): chisel_hip_render_view, chisel_hip_query_points, chisel_hip_cast_rays, chisel_hip_align_terms,
  *      chisel_hip_align_solve, chisel_hip_align_depth, chisel_hip_merge_map, chisel_hip_deintegrate_depth, chisel_hip_deintegrate_batch,
- *      chisel_hip_distance_field (no slot in
- *      the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
+ *      chisel_hip_distance_field, chisel_hip_gather_meshes,
+ *      chisel_hip_gather_meshes_size, chisel_hip_save_ply_binary (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
 #define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -259,6 +259,47 @@ int chisel_hip_save_ply(chisel_hip_map *map, const char *path);
  * [0, 1] per vertex) may be NULL; indices: three per face, as Mesh::indices.  Host I/O only. */
 int chisel_hip_write_mesh_ply(const char *path, const float *vertices, const float *colors, int64_t n_vertices, const int64_t *indices,
                               int64_t n_indices);
+
+/* ---- the map's chunk meshes gathered into one buffer (DESIGN.md 3.12 "Mesh gather") ----------------------------------
+ * Not in the reference as an entry: what ChiselServer::FillMarkerTopicWithMeshes (chisel_ros/src/ChiselServer.cpp:613-716) does
+ * by walking GetAllMeshes() -- every chunk mesh's vertices and grids appended to one marker, every vertex coloured from the mesh
+ * colours or from two Lambert terms of its normal -- as one call from HBM into the caller's contiguous arrays. */
+#define CHISEL_HIP_GATHER_TILE_FLOATS 4096   /* floats of the concatenated outputs one workgroup copies (tests aim at tile edges) */
+typedef struct {
+    const int *ids_xyz; int64_t n_ids;  /* NULL / 0: every mesh, in chisel_hip_list_meshes' order (x, then y, then z); otherwise these
+                                           chunks' meshes in the caller's order, duplicates allowed */
+    int marker_colors;                  /* 0: rgba is not asked for */
+    float light0[3], light1[3];         /* used as given, not normalised by the library */
+    float diffuse, ambient;
+} chisel_hip_mesh_request;              /* 56 bytes */
+typedef struct { int64_t meshes, meshes_nonempty, vertices, grids, arenas_read, tiles; } chisel_hip_mesh_totals;
+/* Mesh i of the selection occupies vertices [first_i, first_i + n_v,i) of `vertices`, `normals`, `colors` (3 floats each; colors only
+ * on a map that holds colour) and `rgba` (4 floats), and grid entries [gfirst_i, gfirst_i + n_g,i) of `grids` (3 floats); the firsts
+ * are the exclusive prefix sums of the selection in order, and every float is the bit pattern chisel_hip_download_mesh returns for
+ * that chunk.  A mesh that exists but is empty contributes a table row of zeros.  rgba (a = 1): on a map with colour the mesh colour
+ * of the vertex; otherwise, in fp32 with every operation rounded on its own, d_k = (n.x l_k.x + n.y l_k.y) + n.z l_k.z,
+ * s_k = fmaxf(d_k, 0) diffuse (0 for a NaN normal), c = (s_0 + s_1) + ambient, r = g = b = fminf(c, 1).
+ * Any of the five output arrays may be NULL, not all.  With on_device they are device pointers, filled on the map's stream by one
+ * launch, and nothing is waited for after it; otherwise host arrays, complete on return, each copied out once, exactly its live
+ * data.  capacity_vertices / capacity_grids: the entries the per-vertex arrays / the grids array have room for (an array that is not
+ * asked for needs none).  mesh_table (4 int64 per mesh: first vertex, vertices, first
+ * grid, grids), mesh_ids_xyz (3 per mesh) and totals are host memory, complete on return, and may be NULL.  The map is only read.
+ * Waits: once, for the job records of a mesh recompute that is still in flight (as chisel_hip_list_meshes does); the segment table
+ * goes up from pinned memory that outlives the call, its device copy is scratch kept in the map, grown on demand, freed with it.
+ * Refused with nothing written: CHISEL_HIP_ERR_INVALID for a null map or request, n_ids < 0, ids without a count or a count without
+ * ids, an id outside the addressable range, no output, colors on a map without colour, a light, diffuse or ambient that is not
+ * finite with marker_colors set, rgba without marker_colors, a capacity below the totals (totals is filled all the same, so that
+ * the caller can retry); CHISEL_HIP_ERR_NOT_FOUND for an id without a mesh (the message names its index);
+ * CHISEL_HIP_ERR_UNSUPPORTED for a group (its meshes sit on several devices; one shard of several is served: its meshes are its
+ * own) and for a selection of more than 2^31 - 1 floats in one array. */
+int chisel_hip_gather_meshes(chisel_hip_map *map, const chisel_hip_mesh_request *request, int64_t capacity_vertices, int64_t capacity_grids,
+                             float *vertices, float *normals, float *colors, float *rgba, float *grids, int on_device,
+                             int64_t *mesh_table, int *mesh_ids_xyz, chisel_hip_mesh_totals *totals);
+/* the same bookkeeping without a launch: the totals of the selection (tiles: of all arrays the map and the request could give) */
+int chisel_hip_gather_meshes_size(chisel_hip_map *map, const chisel_hip_mesh_request *request, chisel_hip_mesh_totals *totals);
+/* chisel_hip_save_ply's elements, properties and vertex order as "format binary_little_endian 1.0", fed by one host-side gather (no
+ * host copy of any arena is made).  A group is CHISEL_HIP_ERR_UNSUPPORTED. */
+int chisel_hip_save_ply_binary(chisel_hip_map *map, const char *path);
 
 /* ---- meshing a sharded map (SURVEY.md 8e "meshing across shards") -------------------------------------------------
  * A chunk's mesh reads its 26 neighbours (cube corners: ChunkManager.cpp:316-357; gradient normals and colours of border
