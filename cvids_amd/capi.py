@@ -120,6 +120,15 @@ class MeshTotals(C.Structure):
 
 GATHER_TILE_FLOATS = 4096  # CHISEL_HIP_GATHER_TILE_FLOATS
 
+
+class ChunkRequest(C.Structure):
+    """chisel_hip_chunk_request (include/chisel_hip.h): the selection of chisel_hip_gather_chunks, 48 bytes"""
+    _fields_ = [("ids_xyz", C.POINTER(C.c_int)), ("n_ids", C.c_int64), ("use_box", C.c_int), ("box_lo", C.c_int * 3), ("box_hi", C.c_int * 3)]
+
+
+assert C.sizeof(ChunkRequest) == 48
+CHUNK_TILE_BYTES = 16384  # bytes of one packed array one workgroup of the chunk copy kernels moves (kernels_chunks.h: CHUNK_TILE_QUADS * 16)
+
 ALIGN_CONVERGED, ALIGN_ITERATION_LIMIT, ALIGN_TOO_FEW_PIXELS, ALIGN_DEGENERATE = 0, 1, 2, 3  # CHISEL_HIP_ALIGN_*
 ALIGN_STATUS = {0: "CONVERGED", 1: "ITERATION_LIMIT", 2: "TOO_FEW_PIXELS", 3: "DEGENERATE"}
 
@@ -144,6 +153,7 @@ EXPORTS = [
     "chisel_hip_query_points", "chisel_hip_cast_rays", "chisel_hip_align_terms", "chisel_hip_align_solve", "chisel_hip_align_depth",
     "chisel_hip_merge_map", "chisel_hip_deintegrate_depth", "chisel_hip_deintegrate_batch", "chisel_hip_distance_field",
     "chisel_hip_gather_meshes", "chisel_hip_gather_meshes_size", "chisel_hip_save_ply_binary",
+    "chisel_hip_gather_chunks", "chisel_hip_scatter_chunks",
 ]
 # the device self-tests and debug read-outs include/chisel_hip_selftest.h declares
 SELFTEST_EXPORTS = [
@@ -303,6 +313,8 @@ def load_library():
                                                       C.POINTER(MeshTotals)]),
                         ("chisel_hip_gather_meshes_size", [vp, C.POINTER(MeshRequest), C.POINTER(MeshTotals)]),
                         ("chisel_hip_save_ply_binary", [vp, C.c_char_p]),
+                        ("chisel_hip_gather_chunks", [vp, C.POINTER(ChunkRequest), C.c_int64, vp, vp, vp, C.c_int, i32p, i64p]),
+                        ("chisel_hip_scatter_chunks", [vp, i32p, C.c_int64, vp, vp, vp, C.c_int, C.c_int, i64p]),
                         ("chisel_hip_kat_color_fresh", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_kat_color_any", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_debug_cloud_stats", [vp, i64p]),

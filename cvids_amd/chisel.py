@@ -749,6 +749,122 @@ class Chisel:
         check(rc)
         return True
 
+    _CHUNK_ARRAYS = (("sdf", np.float32, ()), ("weight", np.float32, ()), ("rgbw", np.uint8, (4,)))
+
+    def _chunk_request(self, ids, box):
+        """-> (chisel_hip_chunk_request, what it points at)"""
+        req = capi.ChunkRequest()
+        keep = None
+        if ids is not None:
+            keep = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1, 3))
+            req.ids_xyz = keep.ctypes.data_as(C.POINTER(C.c_int))
+            req.n_ids = len(keep)
+        if box is not None:
+            req.use_box = 1
+            req.box_lo[:] = [int(v) for v in box[0]]
+            req.box_hi[:] = [int(v) for v in box[1]]
+        return req, keep
+
+    def _gather_chunks_call(self, req, capacity, ptrs, on_device, ids_out, retry=False):
+        """-> the number of chunks of the selection; with `retry`, minus that number - 1 when the capacity was below it (nothing written)"""
+        n = C.c_int64(-1)
+        rc = self.L.chisel_hip_gather_chunks(self.h, C.byref(req), capacity, *ptrs, on_device,
+                                             ids_out.ctypes.data_as(C.POINTER(C.c_int)) if ids_out is not None and ids_out.size else None, C.byref(n))
+        if rc == 4:
+            raise KeyError(self.L.chisel_hip_last_error().decode(errors="replace"))
+        if retry and rc == 1 and n.value > capacity:
+            return -n.value - 1
+        check(rc)
+        return n.value
+
+    def GatherChunksSize(self, ids=None, box=None):
+        """chisel_hip_gather_chunks with a capacity of 0: the number of chunks of a selection (GatherChunks)"""
+        req, keep = self._chunk_request(ids, box)
+        return self._gather_chunks_call(req, 0, [None, None, None], 0, None)
+
+    def GatherChunks(self, ids=None, box=None, sdf=True, weight=True, rgbw=None, out=None):
+        """chisel_hip_gather_chunks: the voxels of the chunks `ids` ((n, 3), in that order, duplicates allowed; None: every resident
+        chunk in GetChunkIDs' order, with box=(lo, hi) those with lo <= id <= hi on every axis) packed by one launch.  ->
+        {"sdf": (n, V), "weight": (n, V), "rgbw": (n, V, 4)} numpy arrays, float32 / uint8, None for what was not asked for
+        (rgbw=None: asked for iff the map holds colour), plus "ids": (n, 3) int32.  Every value is the one GetChunk returns.
+        `out`: a dict of contiguous torch CUDA tensors of those shapes with at least n rows (16-byte aligned): exactly the arrays
+        named in it are filled in place on the map's stream, nothing is waited for; it is returned with "ids" (numpy, host)
+        added.  KeyError for a listed id that is not resident."""
+        req, keep = self._chunk_request(ids, box)
+        if out is not None:
+            import torch
+            unknown = set(out) - {name for name, _, _ in self._CHUNK_ARRAYS}
+            assert not unknown, "out: unknown outputs %s" % sorted(unknown)
+            assert out, "out: no output named"
+            ptrs, cap = [], None
+            for name, dtype, tail in self._CHUNK_ARRAYS:
+                t = out.get(name)
+                want = torch.uint8 if dtype is np.uint8 else torch.float32
+                assert t is None or (t.is_cuda and t.dtype == want and t.is_contiguous() and tuple(t.shape[1:]) == (self.V,) + tail), \
+                    "out[%r]: a contiguous %s CUDA tensor of shape (rows, %d%s)" % (name, want, self.V, ", 4" if tail else "")
+                if t is not None:
+                    cap = int(t.shape[0]) if cap is None else min(cap, int(t.shape[0]))
+                ptrs.append(t.data_ptr() if t is not None and t.numel() else None)
+            if cap and any(p is not None for p in ptrs):  # one call: the selection is made once (a capacity below it is refused)
+                ids_out = np.zeros((cap, 3), np.int32)
+                ids_out = ids_out[:self._gather_chunks_call(req, cap, ptrs, 1, ids_out)]
+            else:  # (an empty tensor has no address: it stands for its array only when there is nothing to write)
+                assert self._gather_chunks_call(req, 0, [None, None, None], 0, None) == 0, "out: tensors without room"
+                ids_out = np.zeros((0, 3), np.int32)
+            self._keep = [out]
+            res = dict(out)
+            res["ids"] = ids_out
+            return res
+        if rgbw is None:
+            rgbw = self.use_color
+        asked = {"sdf": sdf, "weight": weight, "rgbw": rgbw}
+        # one call makes the selection once: room for the list as given, for every resident chunk otherwise (a box: its size is asked
+        # first, it may hold a small part of the map); a capacity that turns out too small is refused with the count, and tried again
+        cap = len(keep) if keep is not None else (self._gather_chunks_call(req, 0, [None, None, None], 0, None) if box is not None else self.NumChunks())
+        while True:
+            res = {name: (np.empty((cap, self.V) + tail, dtype) if asked[name] else None) for name, dtype, tail in self._CHUNK_ARRAYS}
+            ids_out = np.zeros((cap, 3), np.int32)
+            n = 0
+            if cap:
+                n = self._gather_chunks_call(req, cap, [res[name].ctypes.data if res[name] is not None else None for name, _, _ in self._CHUNK_ARRAYS], 0, ids_out, retry=True)
+            else:
+                n = -self._gather_chunks_call(req, 0, [None, None, None], 0, None) - 1
+                n = 0 if n == -1 else n
+            if n >= 0:
+                break
+            cap = -n - 1
+        res = {name: (a[:n] if a is not None else None) for name, a in res.items()}
+        res["ids"] = ids_out[:n]
+        return res
+
+    def ScatterChunks(self, ids, sdf, weight, rgbw=None, mark_updated=False):
+        """chisel_hip_scatter_chunks: the packed chunks `ids` (n, 3), sdf (n, V), weight (n, V), rgbw (n, V, 4) or None (zeros on a map
+        with colour) into the map -- what AddChunk per chunk leaves, by one classify, one create and one copy launch.  numpy arrays,
+        or contiguous torch CUDA tensors that are complete on the map's stream (used in place, nothing is waited for after the
+        copy launch).  mark_updated: the chunks are also left as an integration that changed them leaves them (GetMeshesToUpdate
+        names them and their resident neighbours).  -> the number of chunks created."""
+        ids = np.ascontiguousarray(np.asarray(ids, np.int32).reshape(-1, 3))
+        n = len(ids)
+        created = C.c_int64(0)
+        on_device = 0
+        arrays = []
+        if any(hasattr(a, "is_cuda") for a in (sdf, weight, rgbw) if a is not None):
+            import torch
+            on_device = 1
+            for a, (name, dtype, tail) in zip((sdf, weight, rgbw), self._CHUNK_ARRAYS):
+                want = torch.uint8 if dtype is np.uint8 else torch.float32
+                assert a is None or (a.is_cuda and a.dtype == want and a.is_contiguous() and tuple(a.shape) == (n, self.V) + tail), \
+                    "%s: a contiguous %s CUDA tensor of shape %s" % (name, want, (n, self.V) + tail)
+                arrays.append(a)
+            ptrs = [a.data_ptr() if a is not None and a.numel() else None for a in arrays]
+        else:
+            for a, (name, dtype, tail) in zip((sdf, weight, rgbw), self._CHUNK_ARRAYS):
+                arrays.append(np.ascontiguousarray(a, dtype).reshape((n, self.V) + tail) if a is not None else None)
+            ptrs = [a.ctypes.data if a is not None and a.size else None for a in arrays]
+        check(self.L.chisel_hip_scatter_chunks(self.h, ids.ctypes.data_as(C.POINTER(C.c_int)), n, *ptrs, on_device, 1 if mark_updated else 0, C.byref(created)))
+        self._keep = [arrays]
+        return created.value
+
     def AlignTerms(self, depth, pose, camera, max_residual=0.0, out=None):
         """chisel_hip_align_terms: the normal equations of one Gauss-Newton step that aligns the depth image (numpy, or a torch CUDA
         tensor used in place) taken by `camera` at the guess `pose` (camera -> world) to the map.  -> (32,) float64: [0..20] the upper

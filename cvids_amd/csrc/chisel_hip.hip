@@ -45,6 +45,8 @@
 #include "kernels_distance.h"
 #include "gather_checks.h"
 #include "kernels_gather.h"
+#include "chunk_checks.h"
+#include "kernels_chunks.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
 #include "kernels_stereo_prep.h"
@@ -52,6 +54,7 @@
 using namespace chisel_hip;
 
 // kernel arguments travel in a 4 KiB segment
+static_assert(CHUNK_ID_BIAS == ID_BIAS, "chunk_checks.h orders ids by the bias the chunk hash packs them with");
 static_assert(sizeof(IntegrateParams) + sizeof(MapView) + 6 * sizeof(void *) <= 4096, "integrate_kernel arguments");
 static_assert(sizeof(CullParams) + sizeof(PyramidView) + 6 * sizeof(void *) <= 4096, "cull_kernel arguments");
 static_assert(sizeof(PyramidParams) + sizeof(PyramidView) + 2 * sizeof(void *) <= 4096, "depth_pyramid_kernel arguments");
@@ -434,6 +437,11 @@ struct chisel_hip_map {
         DeviceBuffer<GatherSeg> table;                                 // [segments of the call] the segment table as the kernel reads it
         std::vector<UploadBlock<GatherSeg>> uploads;                   // ... and the host side of its uploads
     } gather_mem;
+    struct ChunkMemory {                                               // chisel_hip_gather_chunks / _scatter_chunks (host_chunks.h), allocated on first use, grown on demand
+        DeviceBuffer<int> ids, slots, ctl;                             // [3 n] the ids of the call | [n] the slot table the copy kernels read | [CK_INTS] a scatter's control words
+        PinnedBuffer<int> host;                                        // [CK_INTS] where the control words reach the host
+        std::vector<UploadBlock<int>> uploads;                         // the host side of the tables' uploads
+    } chunk_mem;
     // profiling
     bool profiling = false;
     std::vector<ProfEvent> prof_live;
@@ -2504,83 +2512,7 @@ int chisel_hip_mesh_shell_plan(const int *entries, int64_t n_entries, int n_shar
 // voxels in the payload of a box of a chunk of edge n
 int64_t chisel_hip_shell_volume(int box, int chunk_edge) { return (int64_t)shell_volume(box, chunk_edge); }
 
-int chisel_hip_save_map(chisel_hip_map *m, const char *path) {
-    SETTLE(m);
-    if (m && m->is_group) return group::save_map(m, path);
-    if (!m || !path) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(m->device));
-    int rc = check_device_error(m);  // waits for the queued batches
-    if (rc) return rc;
-    std::vector<int> ids, slots;
-    rc = fetch_listed(m, false, ids, &slots);
-    if (rc) return rc;
-    const size_t n = slots.size();
-    std::vector<size_t> order(n);
-    for (size_t i = 0; i < n; i++) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-        for (int k = 0; k < 3; k++)
-            if (ids[3 * a + k] != ids[3 * b + k]) return ids[3 * a + k] < ids[3 * b + k];
-        return false;
-    });
-    std::ofstream out(path, std::ios::binary);
-    if (!out) return fail(CHISEL_HIP_ERR_IO, std::string("cannot open ") + path);
-    MapFileHeader h;
-    memcpy(h.magic, "CHSLHIP1", 8);
-    h.chunk_edge = m->N;
-    h.resolution = m->cfg.voxel_resolution;
-    h.has_color = m->view.rgbw ? 1 : 0;
-    h.spare = 0;
-    h.n_chunks = (int64_t)n;
-    out.write(reinterpret_cast<const char *>(&h), sizeof(h));
-    const size_t V = (size_t)m->V;
-    std::vector<float> sdf(V), wgt(V);
-    std::vector<uint8_t> col(h.has_color ? 4 * V : 0);
-    for (size_t i : order) {
-        const size_t off = (size_t)slots[i] * V;
-        HIP_TRY(hipMemcpy(sdf.data(), m->view.sdf + off, V * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(wgt.data(), m->view.wgt + off, V * sizeof(float), hipMemcpyDeviceToHost));
-        if (h.has_color) HIP_TRY(hipMemcpy(col.data(), m->view.rgbw + off, 4 * V, hipMemcpyDeviceToHost));
-        out.write(reinterpret_cast<const char *>(&ids[3 * i]), 3 * sizeof(int));
-        out.write(reinterpret_cast<const char *>(sdf.data()), (std::streamsize)(V * sizeof(float)));
-        out.write(reinterpret_cast<const char *>(wgt.data()), (std::streamsize)(V * sizeof(float)));
-        if (h.has_color) out.write(reinterpret_cast<const char *>(col.data()), (std::streamsize)(4 * V));
-    }
-    if (!out) return fail(CHISEL_HIP_ERR_IO, std::string("write failed: ") + path);
-    return CHISEL_HIP_OK;
-}
-
-int chisel_hip_load_map(chisel_hip_map *m, const char *path) {
-    if (m && m->is_group) return group::for_all(m, [&](chisel_hip_map *s) { return chisel_hip_load_map(s, path); });  // every shard takes the chunks it owns
-    if (!m || !path) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
-    std::ifstream in(path, std::ios::binary);
-    if (!in) return fail(CHISEL_HIP_ERR_IO, std::string("cannot open ") + path);
-    MapFileHeader h;
-    in.read(reinterpret_cast<char *>(&h), sizeof(h));
-    if (!in || memcmp(h.magic, "CHSLHIP1", 8) != 0) return fail(CHISEL_HIP_ERR_IO, "not a chisel-hip map file");
-    if (h.chunk_edge != m->N || h.resolution != m->cfg.voxel_resolution || (h.has_color != 0) != (m->view.rgbw != nullptr))
-        return fail(CHISEL_HIP_ERR_INVALID, "map file was written with another chunk size, resolution or colour setting");
-    if (h.n_chunks < 0 || h.n_chunks > m->view.max_chunks) return fail(CHISEL_HIP_ERR_POOL_FULL, "map file holds more chunks than max_chunks");
-    int rc = chisel_hip_reset(m);
-    if (rc) return rc;
-    rc = ensure_free_exact(m, h.n_chunks);  // (a growable pool: room for the file's chunks)
-    if (rc) return rc;
-    const size_t V = (size_t)m->V;
-    std::vector<float> sdf(V), wgt(V);
-    std::vector<uint8_t> col(h.has_color ? 4 * V : 0);
-    for (int64_t i = 0; i < h.n_chunks; i++) {
-        int id[3];
-        in.read(reinterpret_cast<char *>(id), sizeof(id));
-        in.read(reinterpret_cast<char *>(sdf.data()), (std::streamsize)(V * sizeof(float)));
-        in.read(reinterpret_cast<char *>(wgt.data()), (std::streamsize)(V * sizeof(float)));
-        if (h.has_color) in.read(reinterpret_cast<char *>(col.data()), (std::streamsize)(4 * V));
-        if (!in) return fail(CHISEL_HIP_ERR_IO, std::string("truncated map file: ") + path);
-        if (!chunk_id_in_range(id)) return fail(CHISEL_HIP_ERR_INVALID, std::string("map file names a ") + kIdOutOfRange);
-        if (chunk_owner(id[0], id[1], id[2], m->cfg.n_shards, m->cfg.shard_block) != m->cfg.shard_rank) continue;  // another shard's chunk
-        rc = chisel_hip_upload_chunk(m, id, sdf.data(), wgt.data(), h.has_color ? col.data() : nullptr);
-        if (rc) return rc;
-    }
-    return CHISEL_HIP_OK;
-}
+// chisel_hip_save_map, chisel_hip_load_map: host_chunks.h
 
 int chisel_hip_upload_chunk(chisel_hip_map *m, const int id[3], const float *sdf, const float *weight, const uint8_t *rgbw) {
     SETTLE(m);
@@ -3076,4 +3008,5 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 #include "host_deintegrate.h"
 #include "host_distance.h"
 #include "host_gather.h"
+#include "host_chunks.h"
 #include "host_selftest.h"

@@ -659,6 +659,66 @@ class ChunkManager {  // ChunkManager.h:57-216 over one chisel_hip_map
                                            ptr(out.grids), 0, out.table.data(), out.ids.data(), &out.totals));
         return out;
     }
+    // Not in the reference as calls: the voxels of many chunks as one packed set (chisel_hip_gather_chunks / chisel_hip_scatter_chunks) --
+    // what a loop of GetChunk()->GetVoxels() / AddChunk moves, by one launch each way.  Chunk i of `ids` (3 ints each) has its V =
+    // chunk-size voxels at sdf[i V ...], weight[i V ...], rgbw[4 i V ...] (rgbw only on a map with colour), voxel order the chunk's.
+    struct PackedChunks {
+        std::vector<int> ids;
+        std::vector<float> sdf, weight;
+        std::vector<uint8_t> rgbw;
+    };
+    // ids empty: every chunk, in ascending id order; otherwise these chunks in this order (std::out_of_range for an absent one, as GetChunk)
+    PackedChunks GatherChunks(const ChunkIDList &ids = ChunkIDList()) const {
+        std::vector<int> flat;
+        for (const ChunkID &c : ids) {
+            flat.push_back(c(0)); flat.push_back(c(1)); flat.push_back(c(2));
+        }
+        chisel_hip_chunk_request req{};
+        req.ids_xyz = flat.empty() ? nullptr : flat.data();
+        req.n_ids = (int64_t)ids.size();
+        // one call makes the selection once: room for the list as given, for every resident chunk otherwise; a capacity that turns out
+        // too small (chunks created since) is refused with the count, and tried again
+        int64_t cap = (int64_t)ids.size(), n = 0;
+        if (flat.empty()) hip_check(chisel_hip_num_chunks(map, &cap));
+        const size_t V = (size_t)chunkSize(0) * chunkSize(1) * chunkSize(2);
+        PackedChunks out;
+        for (;;) {
+            if (cap == 0) {  // (nothing resident: the size query says whether that is still so)
+                hip_check(chisel_hip_gather_chunks(map, &req, 0, nullptr, nullptr, nullptr, 0, nullptr, &n));
+                if (n == 0) return out;
+                cap = n;
+            }
+            out.ids.resize((size_t)cap * 3);
+            out.sdf.resize((size_t)cap * V);
+            out.weight.resize((size_t)cap * V);
+            if (useColor) out.rgbw.resize((size_t)cap * V * 4);
+            n = -1;
+            const int rc = chisel_hip_gather_chunks(map, &req, cap, out.sdf.data(), out.weight.data(), useColor ? out.rgbw.data() : nullptr, 0, out.ids.data(), &n);
+            if (rc == CHISEL_HIP_ERR_NOT_FOUND) throw std::out_of_range("ChunkManager::GatherChunks");
+            if (rc == CHISEL_HIP_ERR_INVALID && n > cap) {
+                cap = n;
+                continue;
+            }
+            hip_check(rc);
+            break;
+        }
+        out.ids.resize((size_t)n * 3);
+        out.sdf.resize((size_t)n * V);
+        out.weight.resize((size_t)n * V);
+        if (useColor) out.rgbw.resize((size_t)n * V * 4);
+        return out;
+    }
+    // the packed chunks become the map's (absent ids are created, resident chunks overwritten whole; without rgbw a map with colour gets
+    // zeros); markUpdated: they also join meshesToUpdate with their neighbours, as after an integration.  -> the chunks created
+    int64_t ScatterChunks(const PackedChunks &packed, bool markUpdated = false) {
+        const size_t n = packed.ids.size() / 3, V = (size_t)chunkSize(0) * chunkSize(1) * chunkSize(2);
+        if (packed.ids.size() != 3 * n || packed.sdf.size() != n * V || packed.weight.size() != n * V || (!packed.rgbw.empty() && packed.rgbw.size() != 4 * n * V))
+            throw std::invalid_argument("ChunkManager::ScatterChunks: array sizes do not match the ids");
+        int64_t created = 0;
+        hip_check(chisel_hip_scatter_chunks(map, packed.ids.data(), (int64_t)n, packed.sdf.data(), packed.weight.data(),
+                                            (useColor && !packed.rgbw.empty()) ? packed.rgbw.data() : nullptr, 0, markUpdated ? 1 : 0, &created));
+        return created;
+    }
     bool HasMesh(const ChunkID &id) const {
         const int v[3] = {id(0), id(1), id(2)};
         int64_t nv = 0, ng = 0;

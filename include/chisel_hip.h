@@ -48,7 +48,7 @@ extern "C" {
  *      removed or re-typed): chisel_hip_render_view, chisel_hip_query_points, chisel_hip_cast_rays, chisel_hip_align_terms,
  *      chisel_hip_align_solve, chisel_hip_align_depth, chisel_hip_merge_map, chisel_hip_deintegrate_depth, chisel_hip_deintegrate_batch,
  *      chisel_hip_distance_field, chisel_hip_gather_meshes,
- *      chisel_hip_gather_meshes_size, chisel_hip_save_ply_binary (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
+ *      chisel_hip_gather_meshes_size, chisel_hip_save_ply_binary, chisel_hip_gather_chunks, chisel_hip_scatter_chunks (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
 #define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -207,7 +207,7 @@ int chisel_hip_integrate_batch(chisel_hip_map *map, int n, const chisel_hip_dept
 /* CHUNK IDS.  The map addresses the ids -2^20 + 2 ... 2^20 - 2 on every axis (an id and its 26 neighbours fit the 21 bits per axis the
  * chunk hash packs them into).  Every entry that takes a chunk id from its caller -- chisel_hip_garbage_collect, _has_chunk,
  * _download_chunk, _upload_chunk, _integrate_chunk, _update_meshes_of, _recompute_mesh, _mesh_size, _download_mesh, _generate_mesh,
- * _mesh_cube, and chisel_hip_load_map for the ids of its file (chisel_hip_chunk_owner is a function of the id alone and takes any) --
+ * _mesh_cube, _gather_chunks, _scatter_chunks, and chisel_hip_load_map for the ids of its file (chisel_hip_chunk_owner is a function of the id alone and takes any) --
  * refuses an id outside that range with CHISEL_HIP_ERR_INVALID before anything is launched: the map is as it was (after a refused
  * chisel_hip_load_map: reset, holding the file's chunks in front of the refused one). */
 /* Chisel::GarbageCollect(const ChunkIDList&) Chisel.cpp:61-67 / ChunkManager::RemoveChunk(ChunkID) ChunkManager.h:99-108 */
@@ -300,6 +300,50 @@ int chisel_hip_gather_meshes_size(chisel_hip_map *map, const chisel_hip_mesh_req
 /* chisel_hip_save_ply's elements, properties and vertex order as "format binary_little_endian 1.0", fed by one host-side gather (no
  * host copy of any arena is made).  A group is CHISEL_HIP_ERR_UNSUPPORTED. */
 int chisel_hip_save_ply_binary(chisel_hip_map *map, const char *path);
+
+/* ---- many chunks out of and into the map in one launch each (DESIGN.md 3.13 "Chunk gather and scatter") ---------------
+ * Not in the reference as entries: what a loop of Chunk::GetVoxels / ChunkManager::AddChunk over many chunks moves
+ * (chisel_hip_download_chunk / chisel_hip_upload_chunk here), as one packed set.  A packed set of n chunks is sdf[n][V],
+ * weight[n][V], rgbw[n][V][4] with V = N^3: chunk i of the selection at index i, voxel order the map's ((z N + y) N + x), every value
+ * the bit pattern the per-chunk entry moves (NaN payloads, -0.0 and denormals included).  With on_device the three arrays are
+ * device pointers, 16-byte aligned; otherwise host arrays.  Ids are always host memory. */
+typedef struct {
+    const int *ids_xyz; int64_t n_ids;  /* NULL / 0: every resident chunk, ascending (x, then y, then z) as chisel_hip_list_chunks;
+                                           otherwise these chunks in the caller's order, duplicates allowed */
+    int use_box; int box_lo[3], box_hi[3]; /* with ids NULL and use_box: only the resident chunks with lo <= id <= hi on every axis */
+} chisel_hip_chunk_request;             /* 48 bytes */
+/* Only reads the map.  Any of sdf, weight, rgbw may be NULL.  capacity_chunks: the chunks each given array (and chunk_ids_xyz) has
+ * room for; capacity_chunks == 0 is the size query, which fills *n_chunks and nothing else.  With all three arrays NULL at a non-zero
+ * capacity, chunk_ids_xyz alone is filled (the selection's ids; nothing is launched).  With on_device the arrays are filled by one
+ * launch on the map's stream, behind whatever is queued, and nothing is waited for after it; host arrays are staged through one
+ * owned device buffer, copied out once each, and are complete on return.  One wait, for the selection: the listing of the resident
+ * chunks (all, box) or the slot look-up of a list.  chunk_ids_xyz (3 per chunk, may be NULL) and *n_chunks are complete on return.
+ * Refused with nothing written: CHISEL_HIP_ERR_INVALID for a null map or request, n_ids < 0, ids without a count or a count without
+ * ids, use_box together with ids, a box with lo > hi on an axis, an id outside the addressable range (the message names its index), no
+ * output at a non-zero capacity, rgbw on a map without colour, a device pointer that is not 16-byte aligned, a capacity below the
+ * selection (*n_chunks is filled all the same, so that the caller can retry); CHISEL_HIP_ERR_NOT_FOUND for a listed id that is not
+ * resident (the message names its index); CHISEL_HIP_ERR_UNSUPPORTED for a group (one shard of several is served with its own chunks)
+ * and for a selection whose bytes or launch grid do not fit (2^31 - 1 chunks, 2^31 - 1 tiles of 16 KiB per array). */
+int chisel_hip_gather_chunks(chisel_hip_map *map, const chisel_hip_chunk_request *request, int64_t capacity_chunks,
+                             float *sdf, float *weight, uint8_t *rgbw, int on_device,
+                             int *chunk_ids_xyz, int64_t *n_chunks);
+/* Changes the map: for an accepted call what n calls of chisel_hip_upload_chunk in order leave -- resident ids, every voxel,
+ * chisel_hip_meshes_to_update, the meshes of a later recompute, what later integrations leave.  An absent id is created, a resident
+ * chunk is overwritten whole; rgbw == NULL on a map with colour writes zeros; the slot's sign summary says "any sign" (the mesher
+ * looks at the chunk).  mark_updated != 0: every chunk of the call is also left as an integration that changed it leaves it -- it
+ * and its resident neighbours are named by chisel_hip_meshes_to_update and meshed by the next recompute (a live map that receives
+ * chunks needs this; a restore into a fresh map does not).  On the map's stream: ids up, a classify launch (slot per id, the absent
+ * ones counted), THE ONE WAIT of the call (the absent count and the free slots, through pinned memory), room in a growable pool, a
+ * create launch, the copy launch.  With on_device nothing is waited for after the copy launch; host arrays are staged and are
+ * consumed on return.  *n_created (may be NULL): the chunks the call created.  n == 0 is a successful no-op.
+ * Refused with the map as it was: CHISEL_HIP_ERR_INVALID for a null map, ids, sdf or weight, n < 0, an id out of range, an id that
+ * repeats an earlier one (the message names the second index), an id another shard owns (chisel_hip_chunk_owner; the message names
+ * its index), rgbw on a map without colour, a device pointer that is not 16-byte aligned; CHISEL_HIP_ERR_POOL_FULL when a fixed pool
+ * (or a growable one at its limit) cannot take the absent ids -- all or nothing, decided before the create launch, and not latched
+ * as "map incomplete"; CHISEL_HIP_ERR_UNSUPPORTED for a group. */
+int chisel_hip_scatter_chunks(chisel_hip_map *map, const int *ids_xyz, int64_t n,
+                              const float *sdf, const float *weight, const uint8_t *rgbw, int on_device,
+                              int mark_updated, int64_t *n_created);
 
 /* ---- meshing a sharded map (SURVEY.md 8e "meshing across shards") -------------------------------------------------
  * A chunk's mesh reads its 26 neighbours (cube corners: ChunkManager.cpp:316-357; gradient normals and colours of border

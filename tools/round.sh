@@ -1,6 +1,6 @@
 #!/bin/bash
 # everything DESIGN.md's measurement section / profiles/<tag>_* is made of, on one box; pieces by name:
-#   bash tools/round.sh <tag> tests | profile | diag | table | shards | lines | group | ranks | hosttime | soak
+#   bash tools/round.sh <tag> tests | profile | diag | table | shards | lines | group | ranks | hosttime | soak | chunks
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
 TAG=$1; shift
 prune() { find gpurun_out -name "*kernel_trace.csv" -delete; find gpurun_out -name "*counter_collection.csv" -delete; find gpurun_out -name "*.db" -delete; find gpurun_out -name "*agent_info.csv" -delete; }
@@ -35,6 +35,14 @@ for piece in "$@"; do
         rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/shk_$n -o t -- python3 tools/sharded_host_time.py $n > /dev/null 2>&1
         python3 tools/sharded_kernel_time.py gpurun_out/shk_$n $n 11 >> gpurun_out/${TAG}_sharded_host_time_$n.txt 2>&1
       done; prune ;;
+    chunks)  # chisel_hip_gather_chunks / _scatter_chunks against the per-chunk loops, SaveMap / LoadMap, then the copy kernels under rocprofv3
+             # (the parent commit's files: the same script with --files-only --append and CHISEL_HIP_LIB naming its library)
+      # (each step under its own time limit, the next one only after the one before ended well; the logs are kept beside the table)
+      TRACE=$(mktemp -d); T=profiles/${TAG}_chunk_transfer_bench
+      timeout -k 10 900 python3 tools/chunk_transfer_bench.py --out $T.txt > $T.log 2>&1 &&
+        timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $TRACE -o t -- python3 tools/chunk_transfer_bench.py --device-only > ${T}_trace.log 2>&1 &&
+        timeout -k 10 60 python3 tools/chunk_transfer_bench.py --summarize-trace $TRACE --out $T.txt
+      rm -rf $TRACE ;;
     soak)
       python3 tools/soak.py 6000 > gpurun_out/${TAG}_soak.txt 2>&1
       python3 tools/soak.py 3000 0 grow > gpurun_out/${TAG}_soak_grow.txt 2>&1 ;;
