@@ -352,6 +352,14 @@ int chisel_hip_scatter_chunks(chisel_hip_map *map, const int *ids_xyz, int64_t n
  * shard owns) -- recomputes the meshes of its own chunks and drops the ghosts again.  cvids_amd/sharded.py orchestrates
  * the exchange (ShardedChisel.UpdateMeshes) with the device plan and its wait-free form further down
  * (chisel_hip_shell_plan_device, chisel_hip_shell_plan_queue).
+ * What the meshes are equal to: the reference's on this shard's VIEW -- its own chunks and the received boxes, default voxels
+ * elsewhere in a ghost -- element for element.  Against the reference on the whole map, vertex positions and grid entries are
+ * always equal; normals and colours are equal except at vertices whose normal or colour the reference reads outside the job's 26
+ * neighbours: the v1 + 0.5 v2 vertex of InterpolateVertex's degenerate branch (MarchingCubes.h:135-146), 1.5 times as far from the
+ * origin as its cube, and InterpolateColor's eight look-ups at voxel indices taken for metres (ChunkManager.cpp:506-520), which near
+ * the origin land in chunks of other shards.  Measured on hand-built fields: no row of 285 870 at 3 cm away from
+ * such look-ups, up to 2 747 colour rows of 285 870 where they land inside the map, up to 1 301 normal and 2 168 colour rows of
+ * 76 800 with degenerate vertices near the origin; none far from the origin.  Whole far chunks are not moved.
  *   drop_ghost_chunks    remove the ghosts of the latest chisel_hip_import_shells_packed / _import_shells_fixed (named by
  *                        the items of the received segments, which must stay untouched until then)
  *   update_meshes_of     RecomputeMeshes (ChunkManager.cpp:130-169) for exactly these chunk ids -- the shard's share of
