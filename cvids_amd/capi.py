@@ -129,6 +129,19 @@ class ChunkRequest(C.Structure):
 assert C.sizeof(ChunkRequest) == 48
 CHUNK_TILE_BYTES = 16384  # bytes of one packed array one workgroup of the chunk copy kernels moves (kernels_chunks.h: CHUNK_TILE_QUADS * 16)
 
+
+class CoarseRequest(C.Structure):
+    """chisel_hip_coarse_request (include/chisel_hip.h): the selection, the stride and the stages of chisel_hip_coarse_mesh, 56 bytes"""
+    _fields_ = [("chunks", ChunkRequest), ("stride", C.c_int), ("stages", C.c_int)]
+
+
+class CoarseTotals(C.Structure):
+    """chisel_hip_coarse_totals (include/chisel_hip.h): what a coarse mesh of a selection holds, 32 bytes"""
+    _fields_ = [(n, C.c_int64) for n in ("chunks", "chunks_nonempty", "cubes_meshed", "vertices")]
+
+
+assert C.sizeof(CoarseRequest) == 56 and C.sizeof(CoarseTotals) == 32
+
 ALIGN_CONVERGED, ALIGN_ITERATION_LIMIT, ALIGN_TOO_FEW_PIXELS, ALIGN_DEGENERATE = 0, 1, 2, 3  # CHISEL_HIP_ALIGN_*
 ALIGN_STATUS = {0: "CONVERGED", 1: "ITERATION_LIMIT", 2: "TOO_FEW_PIXELS", 3: "DEGENERATE"}
 
@@ -153,7 +166,7 @@ EXPORTS = [
     "chisel_hip_query_points", "chisel_hip_cast_rays", "chisel_hip_align_terms", "chisel_hip_align_solve", "chisel_hip_align_depth",
     "chisel_hip_merge_map", "chisel_hip_deintegrate_depth", "chisel_hip_deintegrate_batch", "chisel_hip_distance_field",
     "chisel_hip_gather_meshes", "chisel_hip_gather_meshes_size", "chisel_hip_save_ply_binary",
-    "chisel_hip_gather_chunks", "chisel_hip_scatter_chunks",
+    "chisel_hip_gather_chunks", "chisel_hip_scatter_chunks", "chisel_hip_coarse_mesh",
 ]
 # the device self-tests and debug read-outs include/chisel_hip_selftest.h declares
 SELFTEST_EXPORTS = [
@@ -315,6 +328,7 @@ def load_library():
                         ("chisel_hip_save_ply_binary", [vp, C.c_char_p]),
                         ("chisel_hip_gather_chunks", [vp, C.POINTER(ChunkRequest), C.c_int64, vp, vp, vp, C.c_int, i32p, i64p]),
                         ("chisel_hip_scatter_chunks", [vp, i32p, C.c_int64, vp, vp, vp, C.c_int, C.c_int, i64p]),
+                        ("chisel_hip_coarse_mesh", [vp, C.POINTER(CoarseRequest), C.c_int64, vp, vp, vp, C.c_int, i64p, i32p, C.POINTER(CoarseTotals)]),
                         ("chisel_hip_kat_color_fresh", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_kat_color_any", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_debug_cloud_stats", [vp, i64p]),

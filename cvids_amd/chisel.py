@@ -865,6 +865,98 @@ class Chisel:
         self._keep = [arrays]
         return created.value
 
+    _COARSE_OUTPUTS = ("vertices", "normals", "colors")
+
+    def _coarse_request(self, stride, ids, box, stages):
+        """-> (chisel_hip_coarse_request, what it points at)"""
+        req = capi.CoarseRequest()
+        req.chunks, keep = self._chunk_request(ids, box)
+        req.stride, req.stages = int(stride), int(stages)
+        return req, keep
+
+    def _coarse_call(self, req, capacity, ptrs, on_device, table, ids_out):
+        """-> (totals, refused for a capacity below them)"""
+        t = capi.CoarseTotals()
+        rc = self.L.chisel_hip_coarse_mesh(self.h, C.byref(req), capacity, *ptrs, on_device,
+                                           table.ctypes.data_as(C.POINTER(C.c_int64)) if table is not None and table.size else None,
+                                           ids_out.ctypes.data_as(C.POINTER(C.c_int)) if ids_out is not None and ids_out.size else None, C.byref(t))
+        if rc == 4:
+            raise KeyError(self.L.chisel_hip_last_error().decode(errors="replace"))
+        check(rc)
+        return {name: int(getattr(t, name)) for name, _ in capi.CoarseTotals._fields_}
+
+    def CoarseMeshSize(self, stride, ids=None, box=None):
+        """chisel_hip_coarse_mesh with a capacity of 0: the totals of a coarse mesh (CoarseMesh) -> {"chunks", "chunks_nonempty",
+        "cubes_meshed", "vertices"}"""
+        req, keep = self._coarse_request(stride, ids, box, 0)
+        return self._coarse_call(req, 0, [None, None, None], 0, None, None)
+
+    def CoarseMesh(self, stride, ids=None, box=None, normals=True, colors=None, out=None, stages=None):
+        """chisel_hip_coarse_mesh: the marching-cubes mesh over every `stride`-th voxel (stride divides the chunk edge) of the chunks
+        `ids` ((n, 3), in that order, duplicates allowed; None: every resident chunk in GetChunkIDs' order, with box=(lo, hi) those
+        with lo <= id <= hi on every axis), packed in that order.  -> {"vertices": (V, 3), "normals": (V, 3), "colors": (V, 3)}
+        float32 numpy arrays, None for what was not asked for (colors=None: asked for iff the map holds colour), plus "table": (n, 2)
+        int64 -- first vertex, vertices of every chunk --, "ids": (n, 3) int32 and "totals".  stages: bit 0 gradient normals (else
+        face normals), bit 1 colours; None: what the outputs asked for take.
+        `out`: a dict of contiguous torch CUDA float32 tensors of shape (rows, 3) with at least V rows, "vertices" among them:
+        exactly the outputs named in it are filled in place on the map's stream, without a wait after the one the call needs; it is
+        returned with "table", "ids" and "totals" (numpy, host) added.  KeyError for a listed id that is not resident."""
+        if out is not None:
+            import torch
+            unknown = set(out) - set(self._COARSE_OUTPUTS)
+            assert not unknown, "out: unknown outputs %s" % sorted(unknown)
+            assert "vertices" in out, "out: vertices must be named"
+            if stages is None:
+                stages = (1 if "normals" in out else 0) | (2 if "colors" in out else 0)
+            req, keep = self._coarse_request(stride, ids, box, stages)
+            ptrs, cap = [], None
+            for name in self._COARSE_OUTPUTS:
+                t = out.get(name)
+                assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 3), \
+                    "out[%r]: a contiguous float32 CUDA tensor of shape (rows, 3)" % name
+                if t is not None:
+                    cap = int(t.shape[0]) if cap is None else min(cap, int(t.shape[0]))
+                ptrs.append(t.data_ptr() if t is not None and t.numel() else None)
+            n = len(keep) if keep is not None else self.NumChunks()
+            table, ids_out = np.zeros((n, 2), np.int64), np.zeros((n, 3), np.int32)
+            if cap:
+                totals = self._coarse_call(req, cap, ptrs, 1, table, ids_out)
+            else:  # (an empty tensor has no address: it stands for its array only when there is nothing to write)
+                totals = self._coarse_call(req, 0, [None, None, None], 0, table, ids_out)
+                assert totals["vertices"] == 0, "out: tensors without room"
+            self._keep = [out]
+            res = dict(out)
+            res.update(table=table[:totals["chunks"]], ids=ids_out[:totals["chunks"]], totals=totals)
+            return res
+        if colors is None:
+            colors = self.use_color
+        if stages is None:
+            stages = (1 if normals else 0) | (2 if colors else 0)
+        req, keep = self._coarse_request(stride, ids, box, stages)
+        size = self._coarse_call(req, 0, [None, None, None], 0, None, None)
+        n, V = size["chunks"], size["vertices"]
+        asked = {"vertices": True, "normals": normals, "colors": colors}
+        res = {name: (np.empty((V, 3), np.float32) if asked[name] else None) for name in self._COARSE_OUTPUTS}
+        table, ids_out = np.zeros((n, 2), np.int64), np.zeros((n, 3), np.int32)
+        # (nothing has changed the map since the size query; without a vertex the second call is the size query again, with the tables)
+        ptrs = [res[name].ctypes.data if res[name] is not None and V else None for name in self._COARSE_OUTPUTS]
+        totals = self._coarse_call(req, V, ptrs, 0, table, ids_out)
+        res.update(table=table, ids=ids_out, totals=totals)
+        return res
+
+    def SaveCoarseMeshPLY(self, filename, stride):
+        """the coarse mesh of every resident chunk (CoarseMesh) as SaveMeshPLYASCII writes a mesh (chisel_hip_write_mesh_ply)"""
+        mesh = self.CoarseMesh(stride, normals=False, colors=self.use_color)
+        v = np.ascontiguousarray(mesh["vertices"], np.float32)
+        c = np.ascontiguousarray(mesh["colors"], np.float32) if mesh["colors"] is not None else None
+        idx = np.arange(len(v), dtype=np.int64)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None and a.size else None
+        rc = self.L.chisel_hip_write_mesh_ply(str(filename).encode(), fp(v), fp(c), len(v), idx.ctypes.data_as(C.POINTER(C.c_int64)) if len(v) else None, len(idx))
+        if rc == 6:
+            return False
+        check(rc)
+        return True
+
     def AlignTerms(self, depth, pose, camera, max_residual=0.0, out=None):
         """chisel_hip_align_terms: the normal equations of one Gauss-Newton step that aligns the depth image (numpy, or a torch CUDA
         tensor used in place) taken by `camera` at the guess `pose` (camera -> world) to the map.  -> (32,) float64: [0..20] the upper

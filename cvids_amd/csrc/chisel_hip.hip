@@ -47,6 +47,8 @@
 #include "kernels_gather.h"
 #include "chunk_checks.h"
 #include "kernels_chunks.h"
+#include "coarse_checks.h"
+#include "kernels_coarse.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
 #include "kernels_stereo_prep.h"
@@ -442,6 +444,12 @@ struct chisel_hip_map {
         PinnedBuffer<int> host;                                        // [CK_INTS] where the control words reach the host
         std::vector<UploadBlock<int>> uploads;                         // the host side of the tables' uploads
     } chunk_mem;
+    struct CoarseMemory {                                              // chisel_hip_coarse_mesh (host_coarse.h), allocated on first use, grown on demand; the slot list is chunk_mem's
+        DeviceBuffer<int> counts;                                      // [2 n] vertices and meshed cubes of every chunk of the call
+        DeviceBuffer<long long> first;                                 // [n] the vertices in front of every chunk
+        PinnedBuffer<long long> host;                                  // [COARSE_HOST_WORDS + 2 n] where totals and table reach the host
+        size_t host_words = 0;                                         // entries of `host`
+    } coarse_mem;
     // profiling
     bool profiling = false;
     std::vector<ProfEvent> prof_live;
@@ -3009,4 +3017,5 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 #include "host_distance.h"
 #include "host_gather.h"
 #include "host_chunks.h"
+#include "host_coarse.h"
 #include "host_selftest.h"

@@ -719,6 +719,34 @@ class ChunkManager {  // ChunkManager.h:57-216 over one chisel_hip_map
                                             (useColor && !packed.rgbw.empty()) ? packed.rgbw.data() : nullptr, 0, markUpdated ? 1 : 0, &created));
         return created;
     }
+    // Not in the reference: ONE mesh of every resident chunk over every `stride`-th voxel (chisel_hip_coarse_mesh: stride divides the
+    // chunk size; 1 gives GenerateMesh's triangles of all chunks).  Fills vertices, gradient normals and -- on a map with colour --
+    // colours, chunk after chunk in ascending id order, indices 0 .. n - 1; no grids.  A stride that is refused throws as every refused call does.
+    void GenerateCoarseMesh(int stride, Mesh *mesh) const {
+        chisel_hip_coarse_request req{};
+        req.stride = stride;
+        req.stages = useColor ? 3 : 1;
+        chisel_hip_coarse_totals totals{};
+        hip_check(chisel_hip_coarse_mesh(map, &req, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, &totals));  // the size query
+        std::vector<float> ve, no, co;
+        while (totals.vertices > 0) {
+            const int64_t cap = totals.vertices;
+            ve.resize((size_t)cap * 3);
+            no.resize(ve.size());
+            if (useColor) co.resize(ve.size());
+            const int rc = chisel_hip_coarse_mesh(map, &req, cap, ve.data(), no.data(), useColor ? co.data() : nullptr, 0, nullptr, nullptr, &totals);
+            if (rc == CHISEL_HIP_ERR_INVALID && totals.vertices > cap) continue;  // (the map has grown since the size query: the totals say by how much)
+            hip_check(rc);
+            break;
+        }
+        mesh->Clear();
+        for (int64_t i = 0; i < totals.vertices; i++) {
+            mesh->vertices.push_back(Vec3(ve[3 * i], ve[3 * i + 1], ve[3 * i + 2]));
+            mesh->normals.push_back(Vec3(no[3 * i], no[3 * i + 1], no[3 * i + 2]));
+            if (useColor) mesh->colors.push_back(Vec3(co[3 * i], co[3 * i + 1], co[3 * i + 2]));
+            mesh->indices.push_back((size_t)i);
+        }
+    }
     bool HasMesh(const ChunkID &id) const {
         const int v[3] = {id(0), id(1), id(2)};
         int64_t nv = 0, ng = 0;
@@ -966,6 +994,23 @@ class Chisel {  // Chisel.h:38-230
     // per-mesh copies)
     bool SaveAllMeshesToPLYBinary(const std::string &filename) {
         const int rc = chisel_hip_save_ply_binary(map, filename.c_str());
+        if (rc == CHISEL_HIP_ERR_IO) return false;
+        hip_check(rc);
+        return true;
+    }
+    // the coarse mesh of every chunk (ChunkManager::GenerateCoarseMesh) as SaveMeshPLYASCII writes a mesh
+    bool SaveCoarseMeshToPLY(const std::string &filename, int stride) {
+        Mesh mesh;
+        chunkManager.GenerateCoarseMesh(stride, &mesh);
+        const size_t n = mesh.vertices.size();
+        std::vector<float> v(3 * n), c(mesh.colors.size() == n ? 3 * n : 0);
+        std::vector<int64_t> idx(mesh.indices.begin(), mesh.indices.end());
+        for (size_t i = 0; i < n; i++)
+            for (int k = 0; k < 3; k++) {
+                v[3 * i + k] = mesh.vertices[i](k);
+                if (!c.empty()) c[3 * i + k] = mesh.colors[i](k);
+            }
+        const int rc = chisel_hip_write_mesh_ply(filename.c_str(), v.data(), c.empty() ? nullptr : c.data(), (int64_t)n, idx.data(), (int64_t)idx.size());
         if (rc == CHISEL_HIP_ERR_IO) return false;
         hip_check(rc);
         return true;

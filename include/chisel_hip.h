@@ -48,7 +48,7 @@ extern "C" {
  *      removed or re-typed): chisel_hip_render_view, chisel_hip_query_points, chisel_hip_cast_rays, chisel_hip_align_terms,
  *      chisel_hip_align_solve, chisel_hip_align_depth, chisel_hip_merge_map, chisel_hip_deintegrate_depth, chisel_hip_deintegrate_batch,
  *      chisel_hip_distance_field, chisel_hip_gather_meshes,
- *      chisel_hip_gather_meshes_size, chisel_hip_save_ply_binary, chisel_hip_gather_chunks, chisel_hip_scatter_chunks (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
+ *      chisel_hip_gather_meshes_size, chisel_hip_save_ply_binary, chisel_hip_gather_chunks, chisel_hip_scatter_chunks, chisel_hip_coarse_mesh (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
 #define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -344,6 +344,47 @@ int chisel_hip_gather_chunks(chisel_hip_map *map, const chisel_hip_chunk_request
 int chisel_hip_scatter_chunks(chisel_hip_map *map, const int *ids_xyz, int64_t n,
                               const float *sdf, const float *weight, const uint8_t *rgbw, int on_device,
                               int mark_updated, int64_t *n_created);
+
+/* ---- a coarse marching-cubes mesh at every s-th voxel, packed (DESIGN.md 3.14 "Coarse mesh") ----------------------------
+ * Not in the reference: its mesh exists at the voxel grid alone.  With N the chunk edge, res the voxel resolution, s the stride
+ * (1 <= s <= N, N % s == 0) and M = N / s, a selected resident chunk c has the coarse cubes (i, j, k) in [0, M)^3.  Cube (i, j, k)
+ * has the base voxel b = s (i, j, k); its corner d is the voxel b + s cubeIndexOffsets[d] (ChunkManager.cpp:67-69), a component equal
+ * to N meaning voxel 0 of the chunk one further along that axis (ExtractBorderVoxelMesh's rule, :296-379; + neighbours only, up to
+ * seven).  A cube yields nothing when a corner's chunk is absent or a corner's weight is <= 0.5 (:273, :311, :351); every other cube
+ * is a MESHED cube.  Its coordinates are ((float)b res + half_res) + (float)(N c) res per axis (:50-66, Chunk.cpp:43), corner d lies
+ * at coords + (float)offset_d step with step = (float)s res rounded once to fp32 -- at s = 1 cubeCoordOffsets exactly --, and its
+ * triangles are MarchingCubes::MeshCube's on those eight coordinates and distances: vertices in its push order (t + 2, t + 1, t),
+ * each triangle's face normal three times (as chisel_hip_mesh_cube_values).  Order: chunks in the selection's order, cubes of a
+ * chunk by ascending (k M + j) M + i, vertices of a cube in MeshCube's order -- a pure function of map and request.  At s = 1 a
+ * chunk's triangles are those of chisel_hip_generate_mesh, in another order.  No grid entries.
+ * stages (as chisel_hip_generate_mesh): bit 0 replaces a face normal by ComputeNormalsFromGradients' where the look-up succeeds, bit
+ * 1 gives InterpolateColor's colour -- exactly what chisel_hip_shade_vertices makes of the call's vertices and face normals;
+ * colours without bit 1 are zeros. */
+typedef struct {
+    chisel_hip_chunk_request chunks; /* the selection: all resident / a box / a list, as chisel_hip_gather_chunks */
+    int stride;                      /* s */
+    int stages;                      /* bit 0 gradient normals, bit 1 colours */
+} chisel_hip_coarse_request;         /* 56 bytes */
+typedef struct { int64_t chunks, chunks_nonempty, cubes_meshed, vertices; } chisel_hip_coarse_totals;
+/* Only reads the map; everything runs on the map's stream, behind whatever is queued.  vertices, normals, colors: 3 floats per
+ * vertex, each with room for capacity_vertices vertices; normals and colors may be NULL.  chunk_table (2 per chunk of the
+ * selection: first vertex, vertices; a chunk without a triangle has (first, 0)), chunk_ids_xyz (3 per chunk) and totals are host
+ * memory, may be NULL, and are complete on return.  capacity_vertices == 0 is the size query: the count pass runs, totals is
+ * filled, chunk_table and chunk_ids_xyz when given, and nothing else is written.  Otherwise the host waits once, for the totals,
+ * read through pinned memory (a list's slot look-up is queued in front of the count; "all" and a box wait a second time before it,
+ * for the listing of the resident chunks that the host sorts); with on_device the emit and shade launches follow and nothing is
+ * waited for after them; host arrays are staged through one owned device buffer, copied out once each with exactly their live
+ * data, and are complete on return.  The scratch (per-chunk counts and firsts, the slot list) is kept in the map, grown on demand
+ * and freed with it.
+ * Refused with nothing written: CHISEL_HIP_ERR_INVALID for a null map or request, a stride < 1, > N or that does not divide N,
+ * stages outside 0 .. 3, stage bit 1 or colors on a map without colour, whatever chisel_hip_gather_chunks refuses of a selection,
+ * a negative capacity, the size query without totals, no output at a non-zero capacity, normals or colors without vertices, a
+ * capacity below the total (totals is filled all the same, so that the caller can retry); CHISEL_HIP_ERR_NOT_FOUND for a listed id
+ * that is not resident (the message names its index); CHISEL_HIP_ERR_UNSUPPORTED for a group or one shard of several (a cube on a
+ * + face needs its neighbour's owner) and for more than 2^31 - 1 floats in one array. */
+int chisel_hip_coarse_mesh(chisel_hip_map *map, const chisel_hip_coarse_request *request, int64_t capacity_vertices,
+                           float *vertices, float *normals, float *colors, int on_device,
+                           int64_t *chunk_table, int *chunk_ids_xyz, chisel_hip_coarse_totals *totals);
 
 /* ---- meshing a sharded map (SURVEY.md 8e "meshing across shards") -------------------------------------------------
  * A chunk's mesh reads its 26 neighbours (cube corners: ChunkManager.cpp:316-357; gradient normals and colours of border
