@@ -157,6 +157,7 @@ EXPORTS = [
     "chisel_hip_save_map", "chisel_hip_load_map",
     "chisel_hip_drop_ghost_chunks", "chisel_hip_update_meshes_of", "chisel_hip_condition_depth", "chisel_hip_condition_color", "chisel_hip_publish_cloud",
     "chisel_hip_depth_filter_create", "chisel_hip_depth_filter_destroy", "chisel_hip_depth_filter_update", "chisel_hip_depth_filter_read",
+    "chisel_hip_depth_filter_device",
     "chisel_hip_stereo_default_params", "chisel_hip_stereo_create", "chisel_hip_stereo_destroy", "chisel_hip_stereo_set_reference",
     "chisel_hip_stereo_update", "chisel_hip_stereo_output", "chisel_hip_stereo_clear", "chisel_hip_stereo_read",
     "chisel_hip_stereo_set_camera", "chisel_hip_stereo_set_reference_image", "chisel_hip_stereo_update_image",
@@ -256,6 +257,7 @@ def load_library():
     L.chisel_hip_depth_filter_destroy.argtypes = [vp]
     L.chisel_hip_depth_filter_update.argtypes = [vp, vp, vp, C.c_double, C.c_int, C.c_int]
     L.chisel_hip_depth_filter_read.argtypes = [vp, C.c_int, vp, C.c_int]
+    L.chisel_hip_depth_filter_device.argtypes = [vp, C.POINTER(C.c_int)]
     L.chisel_hip_stereo_default_params.argtypes = [C.POINTER(StereoParams)]
     L.chisel_hip_stereo_default_params.restype = None
     L.chisel_hip_stereo_create.argtypes = [C.c_int, C.c_int, C.POINTER(StereoParams), C.c_int, C.POINTER(vp)]

@@ -1151,6 +1151,10 @@ class DepthFilter:
         self.h = C.c_void_p()
         check(self.L.chisel_hip_depth_filter_create(int(height), int(width), int(device_id), C.byref(self.h)))
         self._keep = None
+        # the device the filter lives on: what a CUDA tensor handed to Update or read must live on
+        dev = C.c_int(-1)
+        check(self.L.chisel_hip_depth_filter_device(self.h, C.byref(dev)))
+        self.device_id = dev.value
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -1163,22 +1167,48 @@ class DepthFilter:
         except Exception:
             pass
 
+    def _map_pointer(self, img, what):
+        """-> (address, on_device, keepalive) of a float64 map of the filter's shape.  Host arrays (numpy, CPU torch) of any
+        number type are converted; a CUDA tensor is read in place as doubles, so it must BE float64 and on the filter's device
+        -- a float32 tensor of the right shape would be read past its end."""
+        if not hasattr(img, "shape"):
+            raise TypeError("%s: a numpy array or a torch tensor, not %s" % (what, type(img).__name__))
+        if tuple(img.shape) != self.shape:
+            raise ValueError("%s: shape %s, the filter's is %s" % (what, tuple(img.shape), self.shape))
+        if not isinstance(img, np.ndarray) and getattr(img, "is_cuda", False):
+            import torch
+            if img.dtype != torch.float64:
+                raise TypeError("%s: a CUDA tensor must be float64, not %s" % (what, img.dtype))
+            if img.device.index != self.device_id:
+                raise ValueError("%s: on %s, the filter is on cuda:%d" % (what, img.device, self.device_id))
+        return _image_pointer(img, np.float64)
+
     def Update(self, update_mu, update_cov, reciprocal=False):
-        """DepthFilter::Update(mUpdateMu, mUpdateCov): float64 maps (numpy or torch CUDA tensors); update_cov may be a scalar."""
-        mu_addr, dev, k1 = _image_pointer(update_mu, np.float64)
-        assert tuple(update_mu.shape) == self.shape
+        """DepthFilter::Update(mUpdateMu, mUpdateCov): float64 maps (numpy or torch CUDA tensors); update_cov may be a scalar.
+        Host maps are consumed when this returns; device maps are kept alive here until the next Update."""
+        mu_addr, dev, k1 = self._map_pointer(update_mu, "update_mu")
         if np.isscalar(update_cov):
             check(self.L.chisel_hip_depth_filter_update(self.h, mu_addr, None, float(update_cov), int(reciprocal), dev))
             self._keep = [k1]
         else:
-            cov_addr, dev2, k2 = _image_pointer(update_cov, np.float64)
-            assert dev2 == dev and tuple(update_cov.shape) == self.shape
+            cov_addr, dev2, k2 = self._map_pointer(update_cov, "update_cov")
+            if dev2 != dev:
+                raise ValueError("update_mu and update_cov: both on the host or both CUDA tensors")
             check(self.L.chisel_hip_depth_filter_update(self.h, mu_addr, cov_addr, 0.0, int(reciprocal), dev))
             self._keep = [k1, k2]
 
     def read(self, which, out=None):
         """-> float64 map; `out`: a torch CUDA tensor to fill in place (stays in HBM), default a new numpy array"""
         if out is not None:
+            import torch
+            if not (isinstance(out, torch.Tensor) and out.is_cuda):
+                raise TypeError("out: a torch CUDA tensor, not %s" % type(out).__name__)
+            if out.dtype != torch.float64:
+                raise TypeError("out: must be float64, not %s" % out.dtype)
+            if tuple(out.shape) != self.shape or not out.is_contiguous():
+                raise ValueError("out: contiguous, of shape %s; got %s" % (self.shape, tuple(out.shape)))
+            if out.device.index != self.device_id:
+                raise ValueError("out: on %s, the filter is on cuda:%d" % (out.device, self.device_id))
             check(self.L.chisel_hip_depth_filter_read(self.h, int(which), out.data_ptr(), 1))
             return out
         a = np.empty(self.shape, np.float64)

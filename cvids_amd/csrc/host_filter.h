@@ -53,6 +53,9 @@ int chisel_hip_depth_filter_update(chisel_hip_depth_filter *f, const double *mu,
     }
     hipLaunchKernelGGL(filter_update_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, f->view, d_mu, d_cov, cov_all, reciprocal);
     HIP_TRY(hipGetLastError());
+    // host form: the staging copies have consumed mu and cov before this returns, so the caller may overwrite or free them (from
+    // page-locked memory the copy is a DMA that is still reading its source when hipMemcpyAsync returns); the device form returns at once
+    if (!on_device) HIP_TRY(hipStreamSynchronize(0));
     return CHISEL_HIP_OK;  // stream 0: ordered against the next call; reads wait
 }
 int chisel_hip_depth_filter_read(chisel_hip_depth_filter *f, int which, double *dst, int dst_on_device) {
@@ -64,6 +67,11 @@ int chisel_hip_depth_filter_read(chisel_hip_depth_filter *f, int which, double *
     HIP_TRY(hipGetLastError());
     if (!dst_on_device) HIP_TRY(hipMemcpyAsync(dst, d_out, n * sizeof(double), hipMemcpyDeviceToHost, 0));
     HIP_TRY(hipStreamSynchronize(0));
+    return CHISEL_HIP_OK;
+}
+int chisel_hip_depth_filter_device(const chisel_hip_depth_filter *f, int *device) {
+    if (!f || !device) return fail(CHISEL_HIP_ERR_INVALID, "null argument");
+    *device = f->device;
     return CHISEL_HIP_OK;
 }
 

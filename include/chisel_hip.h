@@ -440,18 +440,25 @@ int chisel_hip_publish_cloud(const double *depth, const uint8_t *color, int w, i
  *   update   DepthFilter::Update(mUpdateMu, mUpdateCov)         depth_filter.cpp:177-259 (NormPdf :10-16)
  *            cov == NULL: cov_all for every pixel (depth_estimator.cpp:293); reciprocal != 0: the update is 1.0 / mu[i]
  *            (depth_estimator.cpp:286 fused in).  Arrays of width * height doubles, on the host or (flag) in HBM.
+ *            Host arrays (pageable or pinned) have been consumed when update returns: the caller may overwrite or free them
+ *            at once, and several updates may follow each other with no read between them.  Device arrays are read by a
+ *            kernel on the null stream after update returns: they stay alive and unchanged until a later call on that
+ *            stream (a read, say) has returned; mu and cov are both on the host or both in HBM.
  *   read     which = 0 GetA, 1 GetB, 2 GetInvDepth, 3 GetCov, 4 GetRatio (depth_filter.h:66-86), 5 the inverse-depth map
  *            DepthEstimator keeps (1e-5 where the ratio is below 0.5, depth_estimator.cpp:387-398), 6 the depth map 1.0 / that
  *            (server_keyframe.cpp:1117) -- the input of chisel_hip_condition_depth, so depth can stay in HBM from the
  *            matcher to the TSDF.
- * All arithmetic in double in the reference's order; exp() is the device library's (parity unpinned, tolerance in
- * tests/test_gpu_filter.py).  PropogateDepth is not built: its only call site is commented out (server_pose_graph.cpp:891). */
+ *   device   the device the filter lives on (device_id of create, or the device that was current then): where arrays handed
+ *            over with the on_device flags must be.
+ * All arithmetic in double in the reference's order; exp() is the device library's (parity unpinned, tolerances in
+ * tests/filter_cases.py).  PropogateDepth is not built: its only call site is commented out (server_pose_graph.cpp:891). */
 typedef struct chisel_hip_depth_filter chisel_hip_depth_filter;
 int chisel_hip_depth_filter_create(int height, int width, int device_id, chisel_hip_depth_filter **out);
 int chisel_hip_depth_filter_destroy(chisel_hip_depth_filter *filter);
 int chisel_hip_depth_filter_update(chisel_hip_depth_filter *filter, const double *mu, const double *cov, double cov_all, int reciprocal,
                                    int on_device);
 int chisel_hip_depth_filter_read(chisel_hip_depth_filter *filter, int which, double *dst, int dst_on_device);
+int chisel_hip_depth_filter_device(const chisel_hip_depth_filter *filter, int *device);
 
 /* ---- the step before that: the stereo matcher (StereoMapper, the reference's only GPU code) --------------------------------
  * StereoMapper (server_pose_graph/src/dense_mapping/sgm_stereo_mapper.cpp, kernels calc_cost.cu): plane-sweep absolute-difference

@@ -8,16 +8,15 @@ is ill-conditioned in the reference itself; it is compared as a variance (square
 import numpy as np
 import pytest
 
+from tests.filter_cases import close
+
 pytestmark = pytest.mark.gpu
 RTOL = 1e-9
 
 
 def _close(got, want, what, atol=0.0):
-    assert (np.isnan(got) == np.isnan(want)).all(), what
-    ok = np.isfinite(want)
-    err = np.abs(got[ok] - want[ok]) - atol
-    rel = err / np.maximum(np.abs(want[ok]), 1e-300)
-    assert rel.max() <= RTOL, "%s: relative error %g" % (what, rel.max())
+    """NaNs and signed infinities at the same places, every finite value within atol + RTOL |want|: tests/filter_cases.py"""
+    close(got, want, what, rtol=RTOL, atol=atol)
 
 
 def test_filter_matches_the_oracle(hip_lib):
