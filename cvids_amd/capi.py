@@ -142,6 +142,14 @@ class CoarseTotals(C.Structure):
 
 assert C.sizeof(CoarseRequest) == 56 and C.sizeof(CoarseTotals) == 32
 
+
+class IndexedTotals(C.Structure):
+    """chisel_hip_indexed_totals (include/chisel_hip.h): what an indexed mesh of a selection holds, 40 bytes"""
+    _fields_ = [(n, C.c_int64) for n in ("chunks", "owners", "cubes_meshed", "vertices", "triangles")]
+
+
+assert C.sizeof(IndexedTotals) == 40
+
 ALIGN_CONVERGED, ALIGN_ITERATION_LIMIT, ALIGN_TOO_FEW_PIXELS, ALIGN_DEGENERATE = 0, 1, 2, 3  # CHISEL_HIP_ALIGN_*
 ALIGN_STATUS = {0: "CONVERGED", 1: "ITERATION_LIMIT", 2: "TOO_FEW_PIXELS", 3: "DEGENERATE"}
 
@@ -167,7 +175,7 @@ EXPORTS = [
     "chisel_hip_query_points", "chisel_hip_cast_rays", "chisel_hip_align_terms", "chisel_hip_align_solve", "chisel_hip_align_depth",
     "chisel_hip_merge_map", "chisel_hip_deintegrate_depth", "chisel_hip_deintegrate_batch", "chisel_hip_distance_field",
     "chisel_hip_gather_meshes", "chisel_hip_gather_meshes_size", "chisel_hip_save_ply_binary",
-    "chisel_hip_gather_chunks", "chisel_hip_scatter_chunks", "chisel_hip_coarse_mesh",
+    "chisel_hip_gather_chunks", "chisel_hip_scatter_chunks", "chisel_hip_coarse_mesh", "chisel_hip_indexed_mesh",
 ]
 # the device self-tests and debug read-outs include/chisel_hip_selftest.h declares
 SELFTEST_EXPORTS = [
@@ -331,6 +339,8 @@ def load_library():
                         ("chisel_hip_gather_chunks", [vp, C.POINTER(ChunkRequest), C.c_int64, vp, vp, vp, C.c_int, i32p, i64p]),
                         ("chisel_hip_scatter_chunks", [vp, i32p, C.c_int64, vp, vp, vp, C.c_int, C.c_int, i64p]),
                         ("chisel_hip_coarse_mesh", [vp, C.POINTER(CoarseRequest), C.c_int64, vp, vp, vp, C.c_int, i64p, i32p, C.POINTER(CoarseTotals)]),
+                        ("chisel_hip_indexed_mesh", [vp, C.POINTER(CoarseRequest), C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int, i64p, i64p, i32p,
+                                                     C.POINTER(IndexedTotals)]),
                         ("chisel_hip_kat_color_fresh", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_kat_color_any", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_debug_cloud_stats", [vp, i64p]),

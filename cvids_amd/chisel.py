@@ -957,6 +957,116 @@ class Chisel:
         check(rc)
         return True
 
+    _INDEXED_OUTPUTS = ("vertices", "indices", "normals", "colors")
+
+    def _indexed_call(self, req, cap_v, cap_t, ptrs, on_device, table, owner_table, owner_ids):
+        """-> the totals"""
+        t = capi.IndexedTotals()
+        i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64)) if a is not None and a.size else None
+        rc = self.L.chisel_hip_indexed_mesh(self.h, C.byref(req), cap_v, cap_t, *ptrs, on_device, i64(table), i64(owner_table),
+                                            owner_ids.ctypes.data_as(C.POINTER(C.c_int)) if owner_ids is not None and owner_ids.size else None, C.byref(t))
+        if rc == 4:
+            raise KeyError(self.L.chisel_hip_last_error().decode(errors="replace"))
+        check(rc)
+        return {name: int(getattr(t, name)) for name, _ in capi.IndexedTotals._fields_}
+
+    def IndexedMeshSize(self, stride, ids=None, box=None):
+        """chisel_hip_indexed_mesh with both capacities 0: the totals of an indexed mesh (IndexedMesh) -> {"chunks", "owners",
+        "cubes_meshed", "vertices", "triangles"}"""
+        req, keep = self._coarse_request(stride, ids, box, 0)
+        return self._indexed_call(req, 0, 0, [None] * 4, 0, None, None, None)
+
+    def IndexedMesh(self, stride, ids=None, box=None, normals=True, colors=None, out=None):
+        """chisel_hip_indexed_mesh: the coarse mesh's triangles (CoarseMesh: same selection, stride and order) over ONE vertex per
+        crossed lattice edge.  -> {"vertices": (V, 3) float32, "indices": (T, 3) int32, "normals": (V, 3), "colors": (V, 3)} numpy
+        arrays, None for what was not asked for (colors=None: asked for iff the map holds colour; normals are gradient normals, zeros
+        where the look-up fails), plus "table": (n, 2) int64 -- first triangle, triangles of every selected chunk --, "owner_table":
+        (owners, 2) int64 -- first vertex, vertices of every owner: the selected chunks, then the resident + neighbours that are not
+        selected, ascending --, "owner_ids": (owners, 3) int32 and "totals".  The ids of a list are distinct.
+        `out`: a dict of contiguous torch CUDA tensors, "vertices" (rows, 3) float32 among them, "indices" (rows, 3) int32, "normals"
+        and "colors" (rows, 3) float32 with at least V rows: exactly the outputs named in it are filled in place on the map's
+        stream, without a wait after the one the call needs; it is returned with the host tables and "totals" added.  KeyError for a
+        listed id that is not resident."""
+        if out is not None:
+            import torch
+            unknown = set(out) - set(self._INDEXED_OUTPUTS)
+            assert not unknown, "out: unknown outputs %s" % sorted(unknown)
+            assert "vertices" in out, "out: vertices must be named"
+            stages = (1 if "normals" in out else 0) | (2 if "colors" in out else 0)
+            req, keep = self._coarse_request(stride, ids, box, stages)
+            ptrs, cap_v, cap_t = [], None, 0
+            for name in self._INDEXED_OUTPUTS:
+                t = out.get(name)
+                dtype = torch.int32 if name == "indices" else torch.float32
+                assert t is None or (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 3), \
+                    "out[%r]: a contiguous %s CUDA tensor of shape (rows, 3)" % (name, dtype)
+                if t is not None and name == "indices":
+                    cap_t = int(t.shape[0])
+                elif t is not None:
+                    cap_v = int(t.shape[0]) if cap_v is None else min(cap_v, int(t.shape[0]))
+                ptrs.append(t.data_ptr() if t is not None and t.numel() else None)
+            n = len(keep) if keep is not None else self.NumChunks()
+            table, owner_table, owner_ids = np.zeros((n, 2), np.int64), np.zeros((8 * n, 2), np.int64), np.zeros((8 * n, 3), np.int32)
+            if "indices" not in out:
+                cap_t = 1 << 40  # (no index array: its capacity is not in the way)
+            if cap_v:
+                totals = self._indexed_call(req, cap_v, cap_t, ptrs, 1, table, owner_table, owner_ids)
+            else:  # (an empty tensor has no address: it stands for its array only when there is nothing to write)
+                totals = self._indexed_call(req, 0, 0, [None] * 4, 0, table, owner_table, owner_ids)
+                assert totals["vertices"] == 0, "out: tensors without room"
+            self._keep = [out]
+            res = dict(out)
+            res.update(table=table[:totals["chunks"]], owner_table=owner_table[:totals["owners"]], owner_ids=owner_ids[:totals["owners"]], totals=totals)
+            return res
+        if colors is None:
+            colors = self.use_color
+        stages = (1 if normals else 0) | (2 if colors else 0)
+        req, keep = self._coarse_request(stride, ids, box, stages)
+        size = self._indexed_call(req, 0, 0, [None] * 4, 0, None, None, None)
+        n, owners, V, T = size["chunks"], size["owners"], size["vertices"], size["triangles"]
+        asked = {"vertices": True, "indices": True, "normals": normals, "colors": colors}
+        res = {name: (np.empty((T, 3), np.int32) if name == "indices" else np.empty((V, 3), np.float32)) if asked[name] else None for name in self._INDEXED_OUTPUTS}
+        table, owner_table, owner_ids = np.zeros((n, 2), np.int64), np.zeros((owners, 2), np.int64), np.zeros((owners, 3), np.int32)
+        # (nothing has changed the map since the size query; without a vertex the second call is the size query again, with the tables)
+        ptrs = [res[name].ctypes.data if res[name] is not None and res[name].size and V else None for name in self._INDEXED_OUTPUTS]
+        totals = self._indexed_call(req, V, T if V else 0, ptrs, 0, table, owner_table, owner_ids)
+        res.update(table=table, owner_table=owner_table, owner_ids=owner_ids, totals=totals)
+        return res
+
+    def SaveIndexedMeshPLY(self, filename, stride, binary=True):
+        """the indexed mesh of every resident chunk (IndexedMesh) as a PLY file with a real face list: binary=False as SaveMeshPLYASCII
+        writes a mesh (chisel_hip_write_mesh_ply), binary=True with SaveMeshPLYBinary's elements and properties"""
+        mesh = self.IndexedMesh(stride, normals=False, colors=self.use_color)
+        v = np.ascontiguousarray(mesh["vertices"], np.float32)
+        c = np.ascontiguousarray(mesh["colors"], np.float32) if mesh["colors"] is not None else None
+        if not binary:
+            idx = np.ascontiguousarray(mesh["indices"].reshape(-1), np.int64)
+            fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None and a.size else None
+            rc = self.L.chisel_hip_write_mesh_ply(str(filename).encode(), fp(v), fp(c), len(v), idx.ctypes.data_as(C.POINTER(C.c_int64)) if len(idx) else None, len(idx))
+            if rc == 6:
+                return False
+            check(rc)
+            return True
+        any_color = c is not None and len(v) > 0
+        head = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % len(v)
+        if any_color:
+            head += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+        head += "element face %d\nproperty list uchar int vertex_index\nend_header\n" % len(mesh["indices"])
+        vert = np.zeros(len(v), np.dtype([("p", "<f4", 3)] + ([("c", "u1", 3)] if any_color else [])))
+        vert["p"] = v
+        if any_color:
+            vert["c"] = (c * np.float32(255.0)).astype(np.int32).astype(np.uint8)  # (write_ply's conversion)
+        face = np.zeros(len(mesh["indices"]), np.dtype([("n", "u1"), ("i", "<i4", 3)]))
+        face["n"], face["i"] = 3, mesh["indices"]
+        try:
+            with open(str(filename), "wb") as f:
+                f.write(head.encode())
+                f.write(vert.tobytes())
+                f.write(face.tobytes())
+        except OSError:
+            return False
+        return True
+
     def AlignTerms(self, depth, pose, camera, max_residual=0.0, out=None):
         """chisel_hip_align_terms: the normal equations of one Gauss-Newton step that aligns the depth image (numpy, or a torch CUDA
         tensor used in place) taken by `camera` at the guess `pose` (camera -> world) to the map.  -> (32,) float64: [0..20] the upper

@@ -49,6 +49,8 @@
 #include "kernels_chunks.h"
 #include "coarse_checks.h"
 #include "kernels_coarse.h"
+#include "indexed_checks.h"
+#include "kernels_indexed.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
 #include "kernels_stereo_prep.h"
@@ -450,6 +452,13 @@ struct chisel_hip_map {
         PinnedBuffer<long long> host;                                  // [COARSE_HOST_WORDS + 2 n] where totals and table reach the host
         size_t host_words = 0;                                         // entries of `host`
     } coarse_mem;
+    struct IndexedMemory {                                             // chisel_hip_indexed_mesh (host_indexed.h), allocated on first use, grown on demand; ids and slots are chunk_mem's
+        DeviceBuffer<int> counts, owner_counts, owner_of_slot;         // [2 n] triangles and meshed cubes of every selected chunk | [owners] used edges | [committed] slot -> owner index
+        DeviceBuffer<unsigned> masks, prefix;                          // [owners x 3 M^2] the used-edge bits of every row | the used edges of the owner's rows in front
+        DeviceBuffer<long long> owner_first, tri_first;                // [owners] the vertices in front of every owner | [n] the triangles in front of every chunk
+        PinnedBuffer<long long> host;                                  // [INDEXED_HOST_WORDS + 2 n + 2 owners] where totals and tables reach the host
+        size_t host_words = 0;                                         // entries of `host`
+    } indexed_mem;
     // profiling
     bool profiling = false;
     std::vector<ProfEvent> prof_live;
@@ -3018,4 +3027,5 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 #include "host_gather.h"
 #include "host_chunks.h"
 #include "host_coarse.h"
+#include "host_indexed.h"
 #include "host_selftest.h"

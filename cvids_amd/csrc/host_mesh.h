@@ -826,7 +826,7 @@ void write_ply(std::ofstream &stream, const std::vector<MeshView> &views, size_t
         stream << "property uchar green" << std::endl;
         stream << "property uchar blue" << std::endl;
     }
-    stream << "element face " << numPoints / 3 << std::endl;
+    stream << "element face " << (indices ? n_indices / 3 : numPoints / 3) << std::endl;  // (a caller's index list: its own faces -- the same number for a soup)
     stream << "property list uchar int vertex_index" << std::endl;
     stream << "end_header" << std::endl;
     for (const MeshView &mv : views) {

@@ -747,6 +747,37 @@ class ChunkManager {  // ChunkManager.h:57-216 over one chisel_hip_map
             mesh->indices.push_back((size_t)i);
         }
     }
+    // Not in the reference: ONE indexed mesh of every resident chunk over every `stride`-th voxel (chisel_hip_indexed_mesh): the
+    // triangles of GenerateCoarseMesh over one vertex per crossed lattice edge.  Fills vertices, gradient normals (zeros where the
+    // look-up fails) and -- on a map with colour -- colours, one entry per vertex, and indices, three per triangle; no grids.
+    void GenerateIndexedMesh(int stride, Mesh *mesh) const {
+        chisel_hip_coarse_request req{};
+        req.stride = stride;
+        req.stages = useColor ? 3 : 1;
+        chisel_hip_indexed_totals totals{};
+        hip_check(chisel_hip_indexed_mesh(map, &req, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, &totals));  // the size query
+        std::vector<float> ve, no, co;
+        std::vector<int32_t> ix;
+        while (totals.vertices > 0) {
+            const int64_t cap_v = totals.vertices, cap_t = totals.triangles;
+            ve.resize((size_t)cap_v * 3);
+            no.resize(ve.size());
+            if (useColor) co.resize(ve.size());
+            ix.resize((size_t)cap_t * 3);
+            const int rc = chisel_hip_indexed_mesh(map, &req, cap_v, cap_t, ve.data(), ix.data(), no.data(), useColor ? co.data() : nullptr, 0, nullptr, nullptr,
+                                                   nullptr, &totals);
+            if (rc == CHISEL_HIP_ERR_INVALID && (totals.vertices > cap_v || totals.triangles > cap_t)) continue;  // (the map has grown since the size query)
+            hip_check(rc);
+            break;
+        }
+        mesh->Clear();
+        for (int64_t i = 0; i < totals.vertices; i++) {
+            mesh->vertices.push_back(Vec3(ve[3 * i], ve[3 * i + 1], ve[3 * i + 2]));
+            mesh->normals.push_back(Vec3(no[3 * i], no[3 * i + 1], no[3 * i + 2]));
+            if (useColor) mesh->colors.push_back(Vec3(co[3 * i], co[3 * i + 1], co[3 * i + 2]));
+        }
+        for (int64_t i = 0; i < 3 * totals.triangles; i++) mesh->indices.push_back((size_t)ix[(size_t)i]);
+    }
     bool HasMesh(const ChunkID &id) const {
         const int v[3] = {id(0), id(1), id(2)};
         int64_t nv = 0, ng = 0;
@@ -1002,6 +1033,23 @@ class Chisel {  // Chisel.h:38-230
     bool SaveCoarseMeshToPLY(const std::string &filename, int stride) {
         Mesh mesh;
         chunkManager.GenerateCoarseMesh(stride, &mesh);
+        const size_t n = mesh.vertices.size();
+        std::vector<float> v(3 * n), c(mesh.colors.size() == n ? 3 * n : 0);
+        std::vector<int64_t> idx(mesh.indices.begin(), mesh.indices.end());
+        for (size_t i = 0; i < n; i++)
+            for (int k = 0; k < 3; k++) {
+                v[3 * i + k] = mesh.vertices[i](k);
+                if (!c.empty()) c[3 * i + k] = mesh.colors[i](k);
+            }
+        const int rc = chisel_hip_write_mesh_ply(filename.c_str(), v.data(), c.empty() ? nullptr : c.data(), (int64_t)n, idx.data(), (int64_t)idx.size());
+        if (rc == CHISEL_HIP_ERR_IO) return false;
+        hip_check(rc);
+        return true;
+    }
+    // the indexed mesh of every chunk (ChunkManager::GenerateIndexedMesh) as SaveMeshPLYASCII writes a mesh: a real face list
+    bool SaveIndexedMeshToPLY(const std::string &filename, int stride) {
+        Mesh mesh;
+        chunkManager.GenerateIndexedMesh(stride, &mesh);
         const size_t n = mesh.vertices.size();
         std::vector<float> v(3 * n), c(mesh.colors.size() == n ? 3 * n : 0);
         std::vector<int64_t> idx(mesh.indices.begin(), mesh.indices.end());

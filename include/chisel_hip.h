@@ -48,7 +48,8 @@ extern "C" {
  *      removed or re-typed): chisel_hip_render_view, chisel_hip_query_points, chisel_hip_cast_rays, chisel_hip_align_terms,
  *      chisel_hip_align_solve, chisel_hip_align_depth, chisel_hip_merge_map, chisel_hip_deintegrate_depth, chisel_hip_deintegrate_batch,
  *      chisel_hip_distance_field, chisel_hip_gather_meshes,
- *      chisel_hip_gather_meshes_size, chisel_hip_save_ply_binary, chisel_hip_gather_chunks, chisel_hip_scatter_chunks, chisel_hip_coarse_mesh (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
+ *      chisel_hip_gather_meshes_size, chisel_hip_save_ply_binary, chisel_hip_gather_chunks, chisel_hip_scatter_chunks, chisel_hip_coarse_mesh,
+ *      chisel_hip_indexed_mesh (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
 #define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -385,6 +386,42 @@ typedef struct { int64_t chunks, chunks_nonempty, cubes_meshed, vertices; } chis
 int chisel_hip_coarse_mesh(chisel_hip_map *map, const chisel_hip_coarse_request *request, int64_t capacity_vertices,
                            float *vertices, float *normals, float *colors, int on_device,
                            int64_t *chunk_table, int *chunk_ids_xyz, chisel_hip_coarse_totals *totals);
+
+/* ---- an indexed marching-cubes mesh: one vertex per crossed lattice edge (DESIGN.md 3.15 "Indexed mesh") ----------------
+ * Not in the reference: MarchingCubes::MeshCube (MarchingCubes.h:73-106) pushes three private vertices per triangle, and a shared
+ * edge's vertex is recomputed per cube.  Selection, stride s, M = N / s, lattice, MESHED cube and configuration are exactly
+ * chisel_hip_coarse_mesh's.  A lattice point l = (li, lj, lk) in [0, M)^3 of a resident chunk o -- the OWNER -- owns three EDGES,
+ * one per axis a, from l to l + e_a; the upper end may be lattice point 0 of the + neighbour.  An edge is USED when it is crossed
+ * ((sdf_lo < 0) != (sdf_hi < 0), CalculateVertexConfiguration's comparison, MarchingCubes.h:108-118) and at least one MESHED cube
+ * of a selected chunk has it among its twelve (edgeIndexPairs, MarchingCubes.cpp:289-303); exactly the used edges get a vertex.
+ * Its position is InterpolateVertex(P, Q, sdf_lo, sdf_hi) (MarchingCubes.h:135-146, the |difference| < 1e-6 branch included),
+ * always from the lower end to the upper: P the centre of voxel s l of the owner, ((float)(s l) res + half_res) + (float)(N o) res
+ * per axis (ChunkManager.cpp:50-66, Chunk.cpp:43), Q = P with step = (float)s res added on axis a only -- a function of the edge
+ * alone, never of the selection or of the cube that asks.
+ * Owners: the selected chunks in the selection's order, then the EXTRAS -- the resident + neighbours (up to seven per selected
+ * chunk) that are not selected, each once, ascending by x, then y, then z ("all resident" has none).  Vertex ids: owners in that
+ * order, inside an owner ascending (a, lk, lj, li).  Triangles: selected chunks in order, cubes by ascending (k M + j) M + i,
+ * MeshCube's triangles in table order, the three ids in its push order (t + 2, t + 1, t) -- row for row the coarse mesh's.
+ * normals (stage bit 0) are zeros overwritten by ComputeNormalsFromGradients (ChunkManager.cpp:609-626) where its look-up succeeds,
+ * colors (stage bit 1) InterpolateColor's: bit for bit what chisel_hip_shade_vertices makes of the vertices with zero normals;
+ * colours without bit 1 are zeros.  Face normals have no per-vertex meaning and are not offered. */
+typedef struct { int64_t chunks, owners, cubes_meshed, vertices, triangles; } chisel_hip_indexed_totals;
+/* Only reads the map; everything runs on the map's stream, behind whatever is queued.  vertices, normals, colors: 3 floats per
+ * vertex with room for capacity_vertices; indices: 3 int32 per triangle with room for capacity_triangles; normals, colors and
+ * indices may be NULL.  chunk_table (2 per selected chunk: first triangle, triangles), owner_table (2 per owner: first vertex,
+ * vertices), owner_ids_xyz (3 per owner; at most 8 per selected chunk) and totals are host memory, may be NULL, and are complete
+ * on return.  Both capacities 0 is the size query: totals and the tables are filled and nothing else is written.  The host waits
+ * once, for the totals (pinned memory), plus the wait "all" and a box cost the coarse mesh; with on_device nothing is waited for
+ * after the launches.  The scratch (row masks and prefixes per owner, counts, the slot -> owner table) is kept in the map, grown
+ * on demand and freed with it.
+ * Refused with nothing written: everything chisel_hip_coarse_mesh refuses; CHISEL_HIP_ERR_INVALID for an id that repeats an
+ * earlier one of the list (an owner is unique; the message names its index), normals without stage bit 0, indices without
+ * vertices, either capacity below its total (totals is filled all the same); CHISEL_HIP_ERR_NOT_FOUND for a listed id that is not
+ * resident; CHISEL_HIP_ERR_UNSUPPORTED for a group or one shard of several and for more than 2^31 - 1 vertices or index entries. */
+int chisel_hip_indexed_mesh(chisel_hip_map *map, const chisel_hip_coarse_request *request, int64_t capacity_vertices,
+                            int64_t capacity_triangles, float *vertices, int32_t *indices, float *normals, float *colors,
+                            int on_device, int64_t *chunk_table, int64_t *owner_table, int *owner_ids_xyz,
+                            chisel_hip_indexed_totals *totals);
 
 /* ---- meshing a sharded map (SURVEY.md 8e "meshing across shards") -------------------------------------------------
  * A chunk's mesh reads its 26 neighbours (cube corners: ChunkManager.cpp:316-357; gradient normals and colours of border
