@@ -663,7 +663,7 @@ class Chisel:
 
     @staticmethod
     def _totals_dict(t):
-        return {name: int(getattr(t, name)) for name, _ in capi.MeshTotals._fields_}
+        return {name: int(getattr(t, name)) for name, _ in t._fields_}
 
     def GatherMeshesSize(self, ids=None, lights=None):
         """chisel_hip_gather_meshes_size: the totals of a selection (GatherMeshes) without a launch -> {"meshes", "meshes_nonempty",
@@ -865,7 +865,10 @@ class Chisel:
         self._keep = [arrays]
         return created.value
 
-    _COARSE_OUTPUTS = ("vertices", "normals", "colors")
+    # the outputs of CoarseMesh and of IndexedMesh: (name, torch's dtype, the dtype as the entry's message spells it, the capacity its rows bound)
+    _COARSE_OUTPUTS = (("vertices", "float32", "float32", "vertices"), ("normals", "float32", "float32", "vertices"), ("colors", "float32", "float32", "vertices"))
+    _INDEXED_OUTPUTS = (("vertices", "float32", "torch.float32", "vertices"), ("indices", "int32", "torch.int32", "triangles"),
+                        ("normals", "float32", "torch.float32", "vertices"), ("colors", "float32", "torch.float32", "vertices"))
 
     def _coarse_request(self, stride, ids, box, stages):
         """-> (chisel_hip_coarse_request, what it points at)"""
@@ -874,16 +877,54 @@ class Chisel:
         req.stride, req.stages = int(stride), int(stages)
         return req, keep
 
-    def _coarse_call(self, req, capacity, ptrs, on_device, table, ids_out):
-        """-> (totals, refused for a capacity below them)"""
-        t = capi.CoarseTotals()
-        rc = self.L.chisel_hip_coarse_mesh(self.h, C.byref(req), capacity, *ptrs, on_device,
-                                           table.ctypes.data_as(C.POINTER(C.c_int64)) if table is not None and table.size else None,
-                                           ids_out.ctypes.data_as(C.POINTER(C.c_int)) if ids_out is not None and ids_out.size else None, C.byref(t))
+    @staticmethod
+    def _out_named(out, outputs):
+        """the names of the `out` dict of CoarseMesh / IndexedMesh against the entry's table of outputs"""
+        unknown = set(out) - {row[0] for row in outputs}
+        assert not unknown, "out: unknown outputs %s" % sorted(unknown)
+        assert "vertices" in out, "out: vertices must be named"
+
+    @staticmethod
+    def _out_tensors(out, outputs):
+        """the tensors of the `out` dict against the entry's table -> (the pointers in the table's order, None for an output that is
+        not named or empty; {capacity: the fewest rows of the tensors that bound it}, a capacity that no tensor bounds missing)"""
+        import torch
+        ptrs, caps = [], {}
+        for name, dtype, spelled, cap in outputs:
+            t = out.get(name)
+            assert t is None or (t.is_cuda and t.dtype == getattr(torch, dtype) and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 3), \
+                "out[%r]: a contiguous %s CUDA tensor of shape (rows, 3)" % (name, spelled)
+            if t is not None:
+                caps[cap] = min(caps.get(cap, int(t.shape[0])), int(t.shape[0]))
+            ptrs.append(t.data_ptr() if t is not None and t.numel() else None)
+        return ptrs, caps
+
+    @staticmethod
+    def _table_ptr(a, ctype):
+        """a numpy table as the C ABI takes it; an empty array has no address"""
+        return a.ctypes.data_as(C.POINTER(ctype)) if a is not None and a.size else None
+
+    def _mesh_call(self, entry, totals, *args):
+        """chisel_hip_coarse_mesh / _indexed_mesh -> the totals; KeyError for a listed id that is not resident"""
+        rc = entry(self.h, *args, C.byref(totals))
         if rc == 4:
             raise KeyError(self.L.chisel_hip_last_error().decode(errors="replace"))
         check(rc)
-        return {name: int(getattr(t, name)) for name, _ in capi.CoarseTotals._fields_}
+        return self._totals_dict(totals)
+
+    def _coarse_call(self, req, capacity, ptrs, on_device, table, ids_out):
+        """-> the totals"""
+        return self._mesh_call(self.L.chisel_hip_coarse_mesh, capi.CoarseTotals(), C.byref(req), capacity, *ptrs, on_device,
+                               self._table_ptr(table, C.c_int64), self._table_ptr(ids_out, C.c_int))
+
+    def _write_mesh_ply(self, filename, v, c, idx):
+        """chisel_hip_write_mesh_ply: float32 vertices and colours (or None), flat int64 indices -> False when the file cannot be written"""
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None and a.size else None
+        rc = self.L.chisel_hip_write_mesh_ply(str(filename).encode(), fp(v), fp(c), len(v), idx.ctypes.data_as(C.POINTER(C.c_int64)) if len(idx) else None, len(idx))
+        if rc == 6:
+            return False
+        check(rc)
+        return True
 
     def CoarseMeshSize(self, stride, ids=None, box=None):
         """chisel_hip_coarse_mesh with a capacity of 0: the totals of a coarse mesh (CoarseMesh) -> {"chunks", "chunks_nonempty",
@@ -902,25 +943,15 @@ class Chisel:
         exactly the outputs named in it are filled in place on the map's stream, without a wait after the one the call needs; it is
         returned with "table", "ids" and "totals" (numpy, host) added.  KeyError for a listed id that is not resident."""
         if out is not None:
-            import torch
-            unknown = set(out) - set(self._COARSE_OUTPUTS)
-            assert not unknown, "out: unknown outputs %s" % sorted(unknown)
-            assert "vertices" in out, "out: vertices must be named"
+            self._out_named(out, self._COARSE_OUTPUTS)
             if stages is None:
                 stages = (1 if "normals" in out else 0) | (2 if "colors" in out else 0)
             req, keep = self._coarse_request(stride, ids, box, stages)
-            ptrs, cap = [], None
-            for name in self._COARSE_OUTPUTS:
-                t = out.get(name)
-                assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 3), \
-                    "out[%r]: a contiguous float32 CUDA tensor of shape (rows, 3)" % name
-                if t is not None:
-                    cap = int(t.shape[0]) if cap is None else min(cap, int(t.shape[0]))
-                ptrs.append(t.data_ptr() if t is not None and t.numel() else None)
+            ptrs, caps = self._out_tensors(out, self._COARSE_OUTPUTS)
             n = len(keep) if keep is not None else self.NumChunks()
             table, ids_out = np.zeros((n, 2), np.int64), np.zeros((n, 3), np.int32)
-            if cap:
-                totals = self._coarse_call(req, cap, ptrs, 1, table, ids_out)
+            if caps.get("vertices"):
+                totals = self._coarse_call(req, caps["vertices"], ptrs, 1, table, ids_out)
             else:  # (an empty tensor has no address: it stands for its array only when there is nothing to write)
                 totals = self._coarse_call(req, 0, [None, None, None], 0, table, ids_out)
                 assert totals["vertices"] == 0, "out: tensors without room"
@@ -936,10 +967,10 @@ class Chisel:
         size = self._coarse_call(req, 0, [None, None, None], 0, None, None)
         n, V = size["chunks"], size["vertices"]
         asked = {"vertices": True, "normals": normals, "colors": colors}
-        res = {name: (np.empty((V, 3), np.float32) if asked[name] else None) for name in self._COARSE_OUTPUTS}
+        res = {name: (np.empty((V, 3), np.float32) if asked[name] else None) for name, *_ in self._COARSE_OUTPUTS}
         table, ids_out = np.zeros((n, 2), np.int64), np.zeros((n, 3), np.int32)
         # (nothing has changed the map since the size query; without a vertex the second call is the size query again, with the tables)
-        ptrs = [res[name].ctypes.data if res[name] is not None and V else None for name in self._COARSE_OUTPUTS]
+        ptrs = [res[name].ctypes.data if res[name] is not None and V else None for name, *_ in self._COARSE_OUTPUTS]
         totals = self._coarse_call(req, V, ptrs, 0, table, ids_out)
         res.update(table=table, ids=ids_out, totals=totals)
         return res
@@ -949,26 +980,12 @@ class Chisel:
         mesh = self.CoarseMesh(stride, normals=False, colors=self.use_color)
         v = np.ascontiguousarray(mesh["vertices"], np.float32)
         c = np.ascontiguousarray(mesh["colors"], np.float32) if mesh["colors"] is not None else None
-        idx = np.arange(len(v), dtype=np.int64)
-        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None and a.size else None
-        rc = self.L.chisel_hip_write_mesh_ply(str(filename).encode(), fp(v), fp(c), len(v), idx.ctypes.data_as(C.POINTER(C.c_int64)) if len(v) else None, len(idx))
-        if rc == 6:
-            return False
-        check(rc)
-        return True
-
-    _INDEXED_OUTPUTS = ("vertices", "indices", "normals", "colors")
+        return self._write_mesh_ply(filename, v, c, np.arange(len(v), dtype=np.int64))
 
     def _indexed_call(self, req, cap_v, cap_t, ptrs, on_device, table, owner_table, owner_ids):
         """-> the totals"""
-        t = capi.IndexedTotals()
-        i64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64)) if a is not None and a.size else None
-        rc = self.L.chisel_hip_indexed_mesh(self.h, C.byref(req), cap_v, cap_t, *ptrs, on_device, i64(table), i64(owner_table),
-                                            owner_ids.ctypes.data_as(C.POINTER(C.c_int)) if owner_ids is not None and owner_ids.size else None, C.byref(t))
-        if rc == 4:
-            raise KeyError(self.L.chisel_hip_last_error().decode(errors="replace"))
-        check(rc)
-        return {name: int(getattr(t, name)) for name, _ in capi.IndexedTotals._fields_}
+        return self._mesh_call(self.L.chisel_hip_indexed_mesh, capi.IndexedTotals(), C.byref(req), cap_v, cap_t, *ptrs, on_device,
+                               self._table_ptr(table, C.c_int64), self._table_ptr(owner_table, C.c_int64), self._table_ptr(owner_ids, C.c_int))
 
     def IndexedMeshSize(self, stride, ids=None, box=None):
         """chisel_hip_indexed_mesh with both capacities 0: the totals of an indexed mesh (IndexedMesh) -> {"chunks", "owners",
@@ -988,25 +1005,13 @@ class Chisel:
         stream, without a wait after the one the call needs; it is returned with the host tables and "totals" added.  KeyError for a
         listed id that is not resident."""
         if out is not None:
-            import torch
-            unknown = set(out) - set(self._INDEXED_OUTPUTS)
-            assert not unknown, "out: unknown outputs %s" % sorted(unknown)
-            assert "vertices" in out, "out: vertices must be named"
+            self._out_named(out, self._INDEXED_OUTPUTS)
             stages = (1 if "normals" in out else 0) | (2 if "colors" in out else 0)
             req, keep = self._coarse_request(stride, ids, box, stages)
-            ptrs, cap_v, cap_t = [], None, 0
-            for name in self._INDEXED_OUTPUTS:
-                t = out.get(name)
-                dtype = torch.int32 if name == "indices" else torch.float32
-                assert t is None or (t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.dim() == 2 and t.shape[1] == 3), \
-                    "out[%r]: a contiguous %s CUDA tensor of shape (rows, 3)" % (name, dtype)
-                if t is not None and name == "indices":
-                    cap_t = int(t.shape[0])
-                elif t is not None:
-                    cap_v = int(t.shape[0]) if cap_v is None else min(cap_v, int(t.shape[0]))
-                ptrs.append(t.data_ptr() if t is not None and t.numel() else None)
+            ptrs, caps = self._out_tensors(out, self._INDEXED_OUTPUTS)
             n = len(keep) if keep is not None else self.NumChunks()
             table, owner_table, owner_ids = np.zeros((n, 2), np.int64), np.zeros((8 * n, 2), np.int64), np.zeros((8 * n, 3), np.int32)
+            cap_v, cap_t = caps.get("vertices"), caps.get("triangles", 0)
             if "indices" not in out:
                 cap_t = 1 << 40  # (no index array: its capacity is not in the way)
             if cap_v:
@@ -1025,10 +1030,10 @@ class Chisel:
         size = self._indexed_call(req, 0, 0, [None] * 4, 0, None, None, None)
         n, owners, V, T = size["chunks"], size["owners"], size["vertices"], size["triangles"]
         asked = {"vertices": True, "indices": True, "normals": normals, "colors": colors}
-        res = {name: (np.empty((T, 3), np.int32) if name == "indices" else np.empty((V, 3), np.float32)) if asked[name] else None for name in self._INDEXED_OUTPUTS}
+        res = {name: (np.empty((T, 3), np.int32) if name == "indices" else np.empty((V, 3), np.float32)) if asked[name] else None for name, *_ in self._INDEXED_OUTPUTS}
         table, owner_table, owner_ids = np.zeros((n, 2), np.int64), np.zeros((owners, 2), np.int64), np.zeros((owners, 3), np.int32)
         # (nothing has changed the map since the size query; without a vertex the second call is the size query again, with the tables)
-        ptrs = [res[name].ctypes.data if res[name] is not None and res[name].size and V else None for name in self._INDEXED_OUTPUTS]
+        ptrs = [res[name].ctypes.data if res[name] is not None and res[name].size and V else None for name, *_ in self._INDEXED_OUTPUTS]
         totals = self._indexed_call(req, V, T if V else 0, ptrs, 0, table, owner_table, owner_ids)
         res.update(table=table, owner_table=owner_table, owner_ids=owner_ids, totals=totals)
         return res
@@ -1040,13 +1045,7 @@ class Chisel:
         v = np.ascontiguousarray(mesh["vertices"], np.float32)
         c = np.ascontiguousarray(mesh["colors"], np.float32) if mesh["colors"] is not None else None
         if not binary:
-            idx = np.ascontiguousarray(mesh["indices"].reshape(-1), np.int64)
-            fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float)) if a is not None and a.size else None
-            rc = self.L.chisel_hip_write_mesh_ply(str(filename).encode(), fp(v), fp(c), len(v), idx.ctypes.data_as(C.POINTER(C.c_int64)) if len(idx) else None, len(idx))
-            if rc == 6:
-                return False
-            check(rc)
-            return True
+            return self._write_mesh_ply(filename, v, c, np.ascontiguousarray(mesh["indices"].reshape(-1), np.int64))
         any_color = c is not None and len(v) > 0
         head = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % len(v)
         if any_color:

@@ -449,15 +449,13 @@ struct chisel_hip_map {
     struct CoarseMemory {                                              // chisel_hip_coarse_mesh (host_coarse.h), allocated on first use, grown on demand; the slot list is chunk_mem's
         DeviceBuffer<int> counts;                                      // [2 n] vertices and meshed cubes of every chunk of the call
         DeviceBuffer<long long> first;                                 // [n] the vertices in front of every chunk
-        PinnedBuffer<long long> host;                                  // [COARSE_HOST_WORDS + 2 n] where totals and table reach the host
-        size_t host_words = 0;                                         // entries of `host`
+        PinnedWords host;                                              // [COARSE_HOST_WORDS + 2 n] where totals and table reach the host
     } coarse_mem;
     struct IndexedMemory {                                             // chisel_hip_indexed_mesh (host_indexed.h), allocated on first use, grown on demand; ids and slots are chunk_mem's
         DeviceBuffer<int> counts, owner_counts, owner_of_slot;         // [2 n] triangles and meshed cubes of every selected chunk | [owners] used edges | [committed] slot -> owner index
         DeviceBuffer<unsigned> masks, prefix;                          // [owners x 3 M^2] the used-edge bits of every row | the used edges of the owner's rows in front
         DeviceBuffer<long long> owner_first, tri_first;                // [owners] the vertices in front of every owner | [n] the triangles in front of every chunk
-        PinnedBuffer<long long> host;                                  // [INDEXED_HOST_WORDS + 2 n + 2 owners] where totals and tables reach the host
-        size_t host_words = 0;                                         // entries of `host`
+        PinnedWords host;                                              // [INDEXED_HOST_WORDS + 2 n + 2 owners] where totals and tables reach the host
     } indexed_mem;
     // profiling
     bool profiling = false;
@@ -635,6 +633,13 @@ int grow_buffer(DeviceBuffer<T> &buf, size_t n, hipStream_t stream, T **view = n
     if (view) *view = buf.get();
     HIP_TRY(e);
     return CHISEL_HIP_OK;
+}
+
+// a call's totals into the caller's struct of chisel_hip.h, which has the host's layout (null: not asked for)
+template <class Totals, class Public>
+void copy_totals(const Totals &T, Public *out) {
+    static_assert(sizeof(Public) == sizeof(Totals), "the totals of chisel_hip.h and the host's are one layout");
+    if (out) memcpy(out, &T, sizeof(T));
 }
 
 // a block of pinned memory for n entries of a per-call table whose last upload is over (a new one when all are busy)

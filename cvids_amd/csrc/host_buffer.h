@@ -64,6 +64,26 @@ private:
     T *p_ = nullptr, *dev_ = nullptr;
 };
 
+// Pinned 64-bit words that a kernel on `stream` writes -- totals, then a table whose length the call sets -- and the host reads after
+// its wait; grown on demand (doubled).
+struct PinnedWords {
+    hipError_t ensure(size_t need, hipStream_t stream) {
+        if (need <= words_) return hipSuccess;
+        hipError_t e = hipStreamSynchronize(stream);  // (a scan of an earlier call may still write the block that goes)
+        if (e != hipSuccess) return e;
+        words_ = 0;
+        e = block_.alloc(2 * need);
+        if (e == hipSuccess) words_ = 2 * need;
+        return e;
+    }
+    volatile long long *get() const { return block_.get(); }
+    long long *dev() const { return block_.dev(); }
+
+private:
+    PinnedBuffer<long long> block_;
+    size_t words_ = 0;
+};
+
 inline size_t round16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 
 // The host arrays of one read-only call, staged through ONE device allocation that lives as long as this object.  The caller hands

@@ -10,6 +10,10 @@
 // (chunks::select), which is sorted on the host, before the count can be queued: two waits.
 //
 // Scratch the map owns (chisel_hip_map::coarse_mem; the slot list: chunk_mem), grown on demand, freed with the map.
+//
+// The steps that chisel_hip_indexed_mesh (host_indexed.h) repeats are functions of this file, as host_rewrite.h's are for the
+// entries that rewrite voxels: begin, wait_for_totals, shade_and_finish, copy_rows.  The pinned words are a PinnedWords
+// (host_buffer.h), the totals leave through copy_totals (chisel_hip.hip), which the mesh gather uses too.
 #pragma once
 
 namespace {
@@ -19,10 +23,47 @@ struct Totals {
     int64_t chunks, chunks_nonempty, cubes_meshed, vertices;
 };
 
-inline void copy_totals(const Totals &T, chisel_hip_coarse_totals *out) {
-    static_assert(sizeof(chisel_hip_coarse_totals) == sizeof(Totals), "chisel_hip_coarse_totals and Totals are one layout");
-    if (out) memcpy(out, &T, sizeof(T));
+// ---- the steps of the frame that the indexed mesh (host_indexed.h) takes as they are
+
+// what both entries refuse behind their request checks (`query`: both capacities are 0), then the device and the recompute in flight
+int begin(chisel_hip_map *m, const char *name, bool query, bool has_totals) {
+    if (query && !has_totals) return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": the size query without totals");
+    HIP_TRY(hipSetDevice(m->device));
+    return check_mesh_totals(m);  // a recompute in flight reads the voxels as they are
 }
+
+// THE WAIT of a call, behind its scan kernel: `words` are complete; a listed id that is not resident is refused with its index
+int wait_for_totals(chisel_hip_map *m, const char *name, volatile long long *words, int absent_word, bool listed) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(m->stream));
+    note_stream_idle(m);
+    std::atomic_thread_fence(std::memory_order_acquire);
+    if (listed && words[absent_word] >= 0)
+        return fail(CHISEL_HIP_ERR_NOT_FOUND, chunks::with_index(name, (int64_t)words[absent_word], "chunk not resident (ChunkManager::GetChunk would throw std::out_of_range)"));
+    return CHISEL_HIP_OK;
+}
+
+// The tail behind the entry's own kernels (`e`: what their launches said): zeros for colours without their stage, as the mesher
+// leaves them, shade_vertices_kernel for the stages asked for, and the staged arrays' way out.
+int shade_and_finish(chisel_hip_map *m, const char *name, Staging &st, hipError_t e, const MeshParams &P, int stages, int64_t n_vertices, const float *dv, float *dn, float *dc) {
+    if (e == hipSuccess && dc && !(stages & 2)) e = hipMemsetAsync(dc, 0, (size_t)n_vertices * 3 * sizeof(float), m->stream);
+    float *sn = (stages & 1) ? dn : nullptr, *sc = (stages & 2) ? dc : nullptr;
+    if (e == hipSuccess && (sn || sc)) {
+        const dim3 per_vertex((unsigned)((n_vertices + 255) / 256));
+        FOR_CHUNK_SIZE(m->N, hipLaunchKernelGGL(shade_vertices_kernel<N>, per_vertex, dim3(256), 0, m->stream, m->view, P, dv, (long long)n_vertices, sn, sc, stages));
+        e = hipGetLastError();
+    }
+    e = st.finish(e);
+    if (e != hipSuccess) return fail(CHISEL_HIP_ERR_HIP, std::string(name) + ": " + hipGetErrorString(e));
+    return CHISEL_HIP_OK;
+}
+
+// n rows of a pinned table (first, count) into the caller's, when it asked for it
+inline void copy_rows(volatile const long long *rows, int64_t n, int64_t *out) {
+    for (int64_t i = 0; out && i < 2 * n; i++) out[i] = rows[i];
+}
+
+// ---- the entry
 
 // counts, firsts and the pinned words for a call of n chunks (doubled when they grow)
 int ensure_memory(chisel_hip_map *m, size_t n) {
@@ -34,12 +75,7 @@ int ensure_memory(chisel_hip_map *m, size_t n) {
         rc = grow_buffer(C.first, want, m->stream);
         if (rc) return rc;
     }
-    if (COARSE_HOST_WORDS + 2 * n > C.host_words) {
-        HIP_TRY(hipStreamSynchronize(m->stream));  // (a scan of an earlier call may still write the block that goes)
-        C.host_words = 0;
-        HIP_TRY(C.host.alloc(COARSE_HOST_WORDS + 2 * want));
-        C.host_words = COARSE_HOST_WORDS + 2 * want;
-    }
+    HIP_TRY(C.host.ensure(COARSE_HOST_WORDS + 2 * n, m->stream));
     return CHISEL_HIP_OK;
 }
 
@@ -51,9 +87,7 @@ int run(chisel_hip_map *m, const char *name, const chisel_hip_coarse_request *re
     int64_t bad_id = -1;
     if (const char *why = coarse_request_refusal(req, m->N, capacity_vertices, vertices, normals, colors, chunk_table, chunk_ids_xyz, m->cfg.use_color != 0, ID_BIAS - 2, &bad_id))
         return fail(CHISEL_HIP_ERR_INVALID, chunks::with_index(name, bad_id, why));
-    if (capacity_vertices == 0 && !totals) return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": the size query without totals");
-    HIP_TRY(hipSetDevice(m->device));
-    rc = check_mesh_totals(m);  // a recompute in flight reads the voxels as they are
+    rc = begin(m, name, capacity_vertices == 0, totals != nullptr);
     if (rc) return rc;
 
     // ---- the selection: its slots into chunk_mem.slots
@@ -97,13 +131,9 @@ int run(chisel_hip_map *m, const char *name, const chisel_hip_coarse_request *re
     const dim3 grid((unsigned)coarse_grid(n));
     FOR_CHUNK_SIZE(m->N, hipLaunchKernelGGL(coarse_count_kernel<N>, grid, dim3(COARSE_THREADS), 0, m->stream, m->view, (const int *)O.slots.get(), (int)n, s, C.counts.get()));
     hipLaunchKernelGGL(coarse_scan_kernel, dim3(1), dim3(COARSE_THREADS), 0, m->stream, (const int *)O.slots.get(), (const int *)C.counts.get(), (int)n, C.first.get(), C.host.dev());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(m->stream));  // the wait of a coarse mesh
-    note_stream_idle(m);
-    std::atomic_thread_fence(std::memory_order_acquire);
     volatile long long *words = C.host.get();
-    if (listed && words[CO_ABSENT] >= 0)
-        return fail(CHISEL_HIP_ERR_NOT_FOUND, chunks::with_index(name, (int64_t)words[CO_ABSENT], "chunk not resident (ChunkManager::GetChunk would throw std::out_of_range)"));
+    rc = wait_for_totals(m, name, words, CO_ABSENT, listed);
+    if (rc) return rc;
     T.chunks_nonempty = words[CO_NONEMPTY];
     T.cubes_meshed = words[CO_CUBES];
     T.vertices = words[CO_VERTICES];
@@ -127,22 +157,12 @@ int run(chisel_hip_map *m, const char *name, const chisel_hip_coarse_request *re
             const MeshParams P = mesh_params(m);
             FOR_CHUNK_SIZE(m->N, hipLaunchKernelGGL(coarse_emit_kernel<N>, grid, dim3(COARSE_THREADS), 0, m->stream, m->view, P, (const int *)O.slots.get(), (int)n, s,
                                                     (const long long *)C.first.get(), (const int *)C.counts.get(), dv, dn));
-            hipError_t e = hipGetLastError();
-            const int stages = req->stages;
-            if (e == hipSuccess && dc && !(stages & 2)) e = hipMemsetAsync(dc, 0, f3, m->stream);  // (colours without their stage: zeros, as the mesher leaves them)
-            float *sn = (stages & 1) ? dn : nullptr, *sc = (stages & 2) ? dc : nullptr;
-            if (e == hipSuccess && (sn || sc)) {
-                const dim3 per_vertex((unsigned)((T.vertices + 255) / 256));
-                FOR_CHUNK_SIZE(m->N, hipLaunchKernelGGL(shade_vertices_kernel<N>, per_vertex, dim3(256), 0, m->stream, m->view, P, (const float *)dv, (long long)T.vertices, sn, sc, stages));
-                e = hipGetLastError();
-            }
-            e = st.finish(e);
-            if (e != hipSuccess) return fail(CHISEL_HIP_ERR_HIP, std::string(name) + ": " + hipGetErrorString(e));
+            rc = shade_and_finish(m, name, st, hipGetLastError(), P, req->stages, T.vertices, dv, dn, dc);
+            if (rc) return rc;
         }
     }
     // ---- what the host owns
-    if (chunk_table)
-        for (int64_t i = 0; i < 2 * n; i++) chunk_table[i] = words[COARSE_HOST_WORDS + i];
+    copy_rows(words + COARSE_HOST_WORDS, n, chunk_table);
     if (chunk_ids_xyz) memcpy(chunk_ids_xyz, listed ? sel->ids_xyz : ids.data(), (size_t)n * 3 * sizeof(int));
     copy_totals(T, totals);
     return CHISEL_HIP_OK;

@@ -45,11 +45,6 @@ int select(chisel_hip_map *m, const char *name, const chisel_hip_mesh_request *r
     return CHISEL_HIP_OK;
 }
 
-inline void copy_totals(const GatherTotals &T, chisel_hip_mesh_totals *out) {
-    static_assert(sizeof(chisel_hip_mesh_totals) == sizeof(GatherTotals), "chisel_hip_mesh_totals and GatherTotals are one layout");
-    if (out) memcpy(out, &T, sizeof(T));
-}
-
 int run(chisel_hip_map *m, const char *name, const chisel_hip_mesh_request *req, int64_t capacity_vertices, int64_t capacity_grids, float *const outputs[GATHER_ARRAYS],
         int on_device, int64_t *mesh_table, int *mesh_ids_xyz, chisel_hip_mesh_totals *totals) {
     // ---- refusals that need no device
@@ -155,7 +150,7 @@ int chisel_hip_gather_meshes_size(chisel_hip_map *m, const chisel_hip_mesh_reque
     int code = 0;
     if (const char *why = gather_plan(src.data(), (int64_t)src.size(), could, false, false, 0, 0, &plan, &code))
         return fail(code == GATHER_REFUSED_UNSUPPORTED ? CHISEL_HIP_ERR_UNSUPPORTED : CHISEL_HIP_ERR_INVALID, std::string(name) + ": " + why);
-    gather::copy_totals(plan.totals, totals);
+    copy_totals(plan.totals, totals);
     return CHISEL_HIP_OK;
 }
 

@@ -5,6 +5,8 @@
 // that are not selected, ascending -- candidates: whether one is resident is looked up on the device and read with the totals), the
 // scratch, mark / rows / scan, THE WAIT for the totals (pinned memory), the capacities, then vertices, indices and shade -- with device
 // pointers nothing is waited for behind them; host arrays are staged through one owned device buffer and are complete on return.
+// The frame's steps are the coarse mesh's own functions (coarse::begin, wait_for_totals, shade_and_finish, copy_rows); what stands
+// written out here is what only this entry does.
 //
 // Waits: a list of ids costs the one wait for the totals; "every resident chunk" and a box also wait for the listing of the resident
 // chunks (chunks::select), as the coarse mesh does.
@@ -19,11 +21,6 @@ struct Totals {
     int64_t chunks, owners, cubes_meshed, vertices, triangles;
 };
 
-inline void copy_totals(const Totals &T, chisel_hip_indexed_totals *out) {
-    static_assert(sizeof(chisel_hip_indexed_totals) == sizeof(Totals), "chisel_hip_indexed_totals and Totals are one layout");
-    if (out) memcpy(out, &T, sizeof(T));
-}
-
 // the scratch of a call of n selected chunks and n_owners owners with `words` mask words (doubled when it grows)
 int ensure_memory(chisel_hip_map *m, size_t n, size_t n_owners, size_t words) {
     chisel_hip_map::IndexedMemory &X = m->indexed_mem;
@@ -36,13 +33,7 @@ int ensure_memory(chisel_hip_map *m, size_t n, size_t n_owners, size_t words) {
     if (!rc) rc = grow_buffer(X.masks, doubled(words, X.masks.size()), m->stream);
     if (!rc) rc = grow_buffer(X.prefix, doubled(words, X.prefix.size()), m->stream);
     if (rc) return rc;
-    const size_t host_words = INDEXED_HOST_WORDS + 2 * n + 2 * n_owners;
-    if (host_words > X.host_words) {
-        HIP_TRY(hipStreamSynchronize(m->stream));  // (a scan of an earlier call may still write the block that goes)
-        X.host_words = 0;
-        HIP_TRY(X.host.alloc(2 * host_words));
-        X.host_words = 2 * host_words;
-    }
+    HIP_TRY(X.host.ensure(INDEXED_HOST_WORDS + 2 * n + 2 * n_owners, m->stream));
     return CHISEL_HIP_OK;
 }
 
@@ -57,31 +48,25 @@ int run(chisel_hip_map *m, const char *name, const chisel_hip_coarse_request *re
                                                   owner_ids_xyz, m->cfg.use_color != 0, ID_BIAS - 2, &bad_id))
         return fail(CHISEL_HIP_ERR_INVALID, chunks::with_index(name, bad_id, why));
     const bool query = capacity_vertices == 0 && capacity_triangles == 0;
-    if (query && !totals) return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": the size query without totals");
-    HIP_TRY(hipSetDevice(m->device));
-    rc = check_mesh_totals(m);  // a recompute in flight reads the voxels as they are
+    rc = coarse::begin(m, name, query, totals != nullptr);
     if (rc) return rc;
 
     // ---- the selection and the owners: ids on the host, slots by a look-up queued in front of the mark
     const chisel_hip_chunk_request *sel = &req->chunks;
     const bool listed = sel->ids_xyz != nullptr;
     std::vector<int> ids;
-    int64_t n = 0;
-    if (listed) {
-        n = sel->n_ids;
-        if (n > CHUNK_MAX_CHUNKS / 8) return fail(CHISEL_HIP_ERR_UNSUPPORTED, std::string(name) + ": more chunks than one call takes (2^28 - 1)");
-        ids.assign(sel->ids_xyz, sel->ids_xyz + 3 * (size_t)n);
-    } else {  // (the listing is sorted on the host: a wait of its own)
+    int64_t n = listed ? sel->n_ids : 0;
+    if (!listed) {  // (the listing is sorted on the host: a wait of its own)
         std::vector<int> slots;
         bool table_ready = false;
         rc = chunks::select(m, name, sel, ids, slots, table_ready);
         if (rc) return rc;
         n = (int64_t)slots.size();
-        if (n > CHUNK_MAX_CHUNKS / 8) return fail(CHISEL_HIP_ERR_UNSUPPORTED, std::string(name) + ": more chunks than one call takes (2^28 - 1)");
     }
+    if (n > CHUNK_MAX_CHUNKS / 8) return fail(CHISEL_HIP_ERR_UNSUPPORTED, std::string(name) + ": more chunks than one call takes (2^28 - 1)");
+    if (listed) ids.assign(sel->ids_xyz, sel->ids_xyz + 3 * (size_t)n);
     Totals T{n, n, 0, 0, 0};
     if (n == 0) {  // an empty map, a box without chunks: nothing is launched
-        T.owners = 0;
         copy_totals(T, totals);
         return CHISEL_HIP_OK;
     }
@@ -117,13 +102,9 @@ int run(chisel_hip_map *m, const char *name, const chisel_hip_coarse_request *re
     hipLaunchKernelGGL(indexed_rows_kernel, owner_grid, dim3(COARSE_THREADS), 0, m->stream, (const unsigned *)X.masks.get(), (int)n_owners, rows, X.prefix.get(), X.owner_counts.get());
     hipLaunchKernelGGL(indexed_scan_kernel, dim3(1), dim3(COARSE_THREADS), 0, m->stream, (const int *)O.slots.get(), (const int *)X.counts.get(), (int)n,
                        (const int *)X.owner_counts.get(), (int)n_owners, X.owner_first.get(), X.tri_first.get(), X.host.dev());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(m->stream));  // the wait of an indexed mesh
-    note_stream_idle(m);
-    std::atomic_thread_fence(std::memory_order_acquire);
     volatile long long *words_h = X.host.get();
-    if (listed && words_h[IX_ABSENT] >= 0)
-        return fail(CHISEL_HIP_ERR_NOT_FOUND, chunks::with_index(name, (int64_t)words_h[IX_ABSENT], "chunk not resident (ChunkManager::GetChunk would throw std::out_of_range)"));
+    rc = coarse::wait_for_totals(m, name, words_h, IX_ABSENT, listed);
+    if (rc) return rc;
     volatile long long *owner_rows = words_h + INDEXED_HOST_WORDS + 2 * n;
     T.owners = 0;
     for (int64_t o = 0; o < n_owners; o++) T.owners += owner_rows[2 * o + 1] >= 0 ? 1 : 0;  // (an extra that is not resident is no owner; it has no vertex)
@@ -158,22 +139,13 @@ int run(chisel_hip_map *m, const char *name, const chisel_hip_coarse_request *re
                                                         (const int *)X.owner_of_slot.get(), pool, (const unsigned *)X.masks.get(), (const unsigned *)X.prefix.get(),
                                                         (const long long *)X.owner_first.get(), (const long long *)X.tri_first.get(), (const int *)X.counts.get(), di));
             hipError_t e = hipGetLastError();
-            const int stages = req->stages;
             if (e == hipSuccess && dn) e = hipMemsetAsync(dn, 0, f3, m->stream);  // (zeros where the gradient look-up fails)
-            if (e == hipSuccess && dc && !(stages & 2)) e = hipMemsetAsync(dc, 0, f3, m->stream);  // (colours without their stage: zeros, as the coarse mesh leaves them)
-            float *sn = (stages & 1) ? dn : nullptr, *sc = (stages & 2) ? dc : nullptr;
-            if (e == hipSuccess && (sn || sc)) {
-                const dim3 per_vertex((unsigned)((T.vertices + 255) / 256));
-                FOR_CHUNK_SIZE(m->N, hipLaunchKernelGGL(shade_vertices_kernel<N>, per_vertex, dim3(256), 0, m->stream, m->view, P, (const float *)dv, (long long)T.vertices, sn, sc, stages));
-                e = hipGetLastError();
-            }
-            e = st.finish(e);
-            if (e != hipSuccess) return fail(CHISEL_HIP_ERR_HIP, std::string(name) + ": " + hipGetErrorString(e));
+            rc = coarse::shade_and_finish(m, name, st, e, P, req->stages, T.vertices, dv, dn, dc);
+            if (rc) return rc;
         }
     }
     // ---- what the host owns
-    if (chunk_table)
-        for (int64_t i = 0; i < 2 * n; i++) chunk_table[i] = words_h[INDEXED_HOST_WORDS + i];
+    coarse::copy_rows(words_h + INDEXED_HOST_WORDS, n, chunk_table);
     int64_t at = 0;
     for (int64_t o = 0; o < n_owners; o++) {
         if (owner_rows[2 * o + 1] < 0) continue;

@@ -1,7 +1,8 @@
 // kernels_indexed.h -- chisel_hip_indexed_mesh: the coarse mesh's triangles (kernels_coarse.h) over ONE vertex per crossed lattice edge
 // (the host side: host_indexed.h; the request checks, the extras and the size arithmetic: indexed_checks.h; the definition:
-// DESIGN.md 3.15).  Beside the coarse mesh, whose kernels it does not touch: coarse_neighbours, coarse_stage and coarse_cube are used
-// as they are, and shade_vertices_kernel runs on the vertices unchanged.
+// DESIGN.md 3.15).  Built from the coarse mesh's pieces: CoarseLattice, coarse_walk_strided, coarse_walk_batched, block_exclusive_scan
+// and scan_chunks are used as they are, and shade_vertices_kernel runs on the vertices unchanged.  What this file adds is what a walk's
+// callable does with a cube, the owners (indexed_owners) and the rows.
 //
 // A lattice point l = (li, lj, lk) in [0, M)^3 of an OWNER chunk owns the three edges l -> l + e_a.  An owner keeps R = 3 M^2 ROWS, row
 // (a M + lk) M + lj, a 32-bit mask each (bit li: the edge is used) and an exclusive prefix each (used edges of the owner's rows in
@@ -9,7 +10,7 @@
 // an owner ascending (a, lk, lj, li).  owner_of_slot turns a pool slot into the owner's index.
 //
 //   indexed_owner_kernel     a thread per owner: owner_of_slot[slot] = index
-//   indexed_mark_kernel<N>   a workgroup per selected chunk at a time, the coarse count kernel's walk: every MESHED cube ORs the bits
+//   indexed_mark_kernel<N>   a workgroup per selected chunk at a time, the strided walk: every MESHED cube ORs the bits
 //                            of its crossed edges into the owners' rows (global vector atomics; an edge has up to four cubes) and
 //                            counts its triangles; per chunk two ints: triangles, meshed cubes
 //   indexed_rows_kernel      a workgroup per owner at a time: the exclusive sum of its rows' popcounts, and the owner's vertices
@@ -17,7 +18,7 @@
 //   indexed_vertex_kernel<N> a workgroup per owner at a time, a lane per row: one position per set bit, interpolate_vertex from the
 //                            lower end P (the owner's voxel s l) to the upper Q = P + step e_a, the two distances read from the
 //                            owner and, for an upper end at N, from voxel 0 of its + neighbour along a
-//   indexed_index_kernel<N>  the coarse emit kernel's walk (cube batches, workgroup prefix sums of triangle counts): three ids per
+//   indexed_index_kernel<N>  the batched walk over triangle counts: three ids per
 //                            triangle in MeshCube's push order (t + 2, t + 1, t), looked up through masks and prefixes
 #pragma once
 #include "kernels_coarse.h"
@@ -26,7 +27,7 @@
 namespace chisel_hip {
 
 // edge `ed` of cube (i, j, k): the lower lattice point of the edge, wrapped into its owner, and the axis.  d: which of the cube's
-// eight chunks (coarse_neighbours' numbering) owns it.
+// eight chunks (CoarseLattice::nb's numbering) owns it.
 struct LatticeEdge {
     int d, row, li;
 };
@@ -49,50 +50,43 @@ __global__ __launch_bounds__(256) void indexed_owner_kernel(const int *__restric
     if (slot >= 0 && slot < pool) owner_of_slot[slot] = o;
 }
 
+// the owner index of each of the lattice's eight slots (-1: no owner), by lanes 0 .. 7 behind lat.neighbours without a barrier: lane d
+// reads the word it wrote itself
+template <int N>
+__device__ inline void indexed_owners(const CoarseLattice<N> &lat, const int *__restrict__ owner_of_slot, int pool, int *s_owner) {
+    if (threadIdx.x >= 8) return;
+    const int ns = lat.nb[threadIdx.x];
+    s_owner[threadIdx.x] = (ns >= 0 && ns < pool) ? owner_of_slot[ns] : -1;
+}
+
 // counts: two ints per selected chunk -- triangles, meshed cubes (a listed id that is not resident: 0, 0)
 template <int N>
 __global__ __launch_bounds__(COARSE_THREADS) void indexed_mark_kernel(MapView M, const int *__restrict__ slots, int n_chunks, int s, const int *__restrict__ owner_of_slot, int pool,
                                                                       unsigned *masks, int *__restrict__ counts) {
-    __shared__ float s_val[CoarseGeom<N>::SAMPLES];
-    __shared__ unsigned char s_ok[CoarseGeom<N>::SAMPLES];
-    __shared__ int s_nb[8], s_owner[8];
+    __shared__ CoarseLattice<N> lat;
+    __shared__ int s_owner[8];
     __shared__ unsigned s_triangles, s_cubes;
-    const int Mc = N / s, L = Mc + 1;
+    const int Mc = N / s;
     const size_t R = (size_t)(3 * Mc * Mc);
     for (int c = (int)blockIdx.x; c < n_chunks; c += (int)gridDim.x) {
-        __syncthreads();  // (the chunk before: its slots, its sums and its last slab have been read)
-        const int slot = slots[c];
-        coarse_neighbours(M, slot, s_nb);
+        __syncthreads();  // (the chunk before: its slots, its owners, its sums and its last slab have been read)
         if (threadIdx.x == 8) { s_triangles = 0u; s_cubes = 0u; }
-        __syncthreads();
-        if (threadIdx.x < 8) {
-            const int ns = s_nb[threadIdx.x];
-            s_owner[threadIdx.x] = (ns >= 0 && ns < pool) ? owner_of_slot[ns] : -1;
-        }
         unsigned nt = 0u, nc = 0u;
-        for (int k0 = 0; k0 < Mc && slot >= 0; k0 += COARSE_SLAB) {  // (slot: workgroup-uniform)
-            const int layers = min(COARSE_SLAB, Mc - k0);
-            __syncthreads();  // the slots and owners are there; the slab before has been read
-            coarse_stage<N>(M, s_nb, s, Mc, k0, layers + 1, s_val, s_ok);
-            __syncthreads();
-            for (int t = (int)threadIdx.x; t < layers * Mc * Mc; t += COARSE_THREADS) {
-                float sdf[8];
-                const int i = t % Mc, j = (t / Mc) % Mc, lz = t / (Mc * Mc);
-                const int index = coarse_cube(s_val, s_ok, L, i, j, lz, sdf);
-                if (index < 0) continue;
+        coarse_walk_strided<N>(
+            M, lat, slots[c], s, Mc, [&] { indexed_owners(lat, owner_of_slot, pool, s_owner); },
+            [&](int i, int j, int k, int index, const float *) {
                 nc++;
                 nt += c_mc_counts[index] / 3;
-                if (index == 0 || index == 255) continue;
+                if (index == 0 || index == 255) return;
 #pragma unroll
                 for (int ed = 0; ed < 12; ed++) {
                     const int e0 = c_mc_edges[ed] & 0xF, e1 = c_mc_edges[ed] >> 4;
                     if ((((index >> e0) ^ (index >> e1)) & 1) == 0) continue;  // (crossed: the corners' bits differ)
-                    const LatticeEdge E = lattice_edge(ed, i, j, k0 + lz, Mc);
+                    const LatticeEdge E = lattice_edge(ed, i, j, k, Mc);
                     const int owner = s_owner[E.d];
                     if (owner >= 0) atomicOr(&masks[(size_t)owner * R + (size_t)E.row], 1u << E.li);  // (a meshed cube's chunks are resident owners)
                 }
-            }
-        }
+            });
         __syncthreads();  // (s_triangles, s_cubes are zero for everybody)
         tally_count(nt, &s_triangles);
         tally_count(nc, &s_cubes);
@@ -102,28 +96,6 @@ __global__ __launch_bounds__(COARSE_THREADS) void indexed_mark_kernel(MapView M,
             counts[2 * (size_t)c + 1] = (int)s_cubes;
         }
     }
-}
-
-// the exclusive sum of `mine` over the workgroup's lanes (COARSE_THREADS), and its total; a barrier on each side of s_wave
-__device__ inline long long indexed_block_scan(long long mine, long long *s_wave, long long &total) {
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    long long incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long up = __shfl_up(incl, o);
-        if (lane >= o) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    long long before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < COARSE_THREADS / 64; w++) {
-        before += w < wave ? s_wave[w] : 0;
-        total += s_wave[w];
-    }
-    __syncthreads();  // (s_wave is free again)
-    return before + incl - mine;
 }
 
 // prefix[o R + r] = used edges of owner o in the rows in front of r; owner_counts[o] = its used edges (<= 3 M^3 = 98 304)
@@ -137,7 +109,7 @@ __global__ __launch_bounds__(COARSE_THREADS) void indexed_rows_kernel(const unsi
             const int r = base + (int)threadIdx.x;
             const long long mine = r < rows ? (long long)__popc(masks[at + r]) : 0;
             long long total;
-            const long long before = indexed_block_scan(mine, s_wave, total);
+            const long long before = block_exclusive_scan(mine, s_wave, total);
             if (r < rows) prefix[at + r] = (unsigned)(run + before);
             run += total;
         }
@@ -155,31 +127,15 @@ __global__ __launch_bounds__(COARSE_THREADS) void indexed_scan_kernel(const int 
     __shared__ int s_absent;
     if (threadIdx.x == 0) { s_cubes = 0; s_absent = 0x7fffffff; }
     __syncthreads();
-    long long run = 0, cubes = 0;
-    for (int base = 0; base < n_chunks; base += COARSE_THREADS) {
-        const int c = base + (int)threadIdx.x;
-        const long long mine = c < n_chunks ? (long long)counts[2 * (size_t)c] : 0;
-        if (c < n_chunks) {
-            cubes += counts[2 * (size_t)c + 1];
-            if (slots[c] < 0) atomicMin(&s_absent, c);
-        }
-        long long total;
-        const long long at = run + indexed_block_scan(mine, s_wave, total);
-        if (c < n_chunks) {
-            tri_first[c] = at;
-            host[INDEXED_HOST_WORDS + 2 * (size_t)c] = at;
-            host[INDEXED_HOST_WORDS + 2 * (size_t)c + 1] = mine;
-        }
-        run += total;
-    }
-    const long long triangles = run;
+    long long cubes = 0;
+    const long long triangles = scan_chunks(slots, counts, n_chunks, tri_first, host + INDEXED_HOST_WORDS, s_wave, &s_absent, cubes, nullptr);
     long long *owner_rows = host + INDEXED_HOST_WORDS + 2 * (size_t)n_chunks;
-    run = 0;
+    long long run = 0;
     for (int base = 0; base < n_owners; base += COARSE_THREADS) {
         const int o = base + (int)threadIdx.x;
         const long long mine = o < n_owners ? (long long)owner_counts[o] : 0;
         long long total;
-        const long long at = run + indexed_block_scan(mine, s_wave, total);
+        const long long at = run + block_exclusive_scan(mine, s_wave, total);
         if (o < n_owners) {
             owner_first[o] = at;
             owner_rows[2 * (size_t)o] = at;
@@ -259,60 +215,42 @@ __global__ __launch_bounds__(COARSE_THREADS) void indexed_index_kernel(MapView M
                                                                        const unsigned *__restrict__ masks, const unsigned *__restrict__ prefix,
                                                                        const long long *__restrict__ owner_first, const long long *__restrict__ tri_first,
                                                                        const int *__restrict__ counts, int *__restrict__ indices) {
-    __shared__ float s_val[CoarseGeom<N>::SAMPLES];
-    __shared__ unsigned char s_ok[CoarseGeom<N>::SAMPLES];
-    __shared__ int s_nb[8], s_owner[8];
+    __shared__ CoarseLattice<N> lat;
+    __shared__ int s_owner[8];
     __shared__ long long s_first[8];
-    __shared__ long long s_wave[COARSE_THREADS / 64];
-    const int Mc = N / s, L = Mc + 1;
+    __shared__ int s_wave[COARSE_THREADS / 64];
+    const int Mc = N / s;
     const size_t R = (size_t)(3 * Mc * Mc);
     for (int c = (int)blockIdx.x; c < n_chunks; c += (int)gridDim.x) {
         const int slot = slots[c];
         if (slot < 0 || counts[2 * (size_t)c] == 0) continue;  // (workgroup-uniform)
-        __syncthreads();  // (the chunk before: its slots and its last slab have been read)
-        coarse_neighbours(M, slot, s_nb);
-        __syncthreads();
-        if (threadIdx.x < 8) {
-            const int ns = s_nb[threadIdx.x];
-            const int owner = (ns >= 0 && ns < pool) ? owner_of_slot[ns] : -1;
-            s_owner[threadIdx.x] = owner;
-            s_first[threadIdx.x] = owner >= 0 ? owner_first[owner] : 0;
-        }
-        long long run = tri_first[c];
-        for (int k0 = 0; k0 < Mc; k0 += COARSE_SLAB) {
-            const int layers = min(COARSE_SLAB, Mc - k0), cubes = layers * Mc * Mc;
-            __syncthreads();  // the slots and owners are there; the slab before has been read
-            coarse_stage<N>(M, s_nb, s, Mc, k0, layers + 1, s_val, s_ok);
-            __syncthreads();
-            for (int base = 0; base < cubes; base += COARSE_THREADS) {  // (cube order: (k M + j) M + i ascending)
-                const int t = base + (int)threadIdx.x;
-                const int i = t % Mc, j = (t / Mc) % Mc, lz = t / (Mc * Mc);
-                float sdf[8];
-                const int index = t < cubes ? coarse_cube(s_val, s_ok, L, i, j, lz, sdf) : -1;
-                const int nv = index >= 0 ? (int)c_mc_counts[index] : 0;
-                long long total;
-                const long long before = indexed_block_scan((long long)(nv / 3), s_wave, total);
-                if (nv) {
-                    int *out = indices + 3 * (size_t)(run + before);
-                    const unsigned long long row = c_mc_cases[index];
-                    for (int tv = 0; tv < nv; tv += 3) {
+        __syncthreads();  // (the chunk before: its slots, its owners and its last slab have been read)
+        coarse_walk_batched<N>(
+            M, lat, s_wave, slot, s, Mc, tri_first[c],
+            [&] {
+                indexed_owners(lat, owner_of_slot, pool, s_owner);
+                if (threadIdx.x < 8) s_first[threadIdx.x] = s_owner[threadIdx.x] >= 0 ? owner_first[s_owner[threadIdx.x]] : 0;
+            },
+            [](int index) { return (int)c_mc_counts[index] / 3; },
+            [&](int i, int j, int k, int index, const float *, long long at) {
+                int *out = indices + 3 * (size_t)at;
+                const int nv = (int)c_mc_counts[index];
+                const unsigned long long row = c_mc_cases[index];
+                for (int tv = 0; tv < nv; tv += 3) {
 #pragma unroll
-                        for (int a = 0; a < 3; a++) {
-                            const int ed = (int)((row >> (4 * (tv + 2 - a))) & 0xF);
-                            const LatticeEdge E = lattice_edge(ed, i, j, k0 + lz, Mc);
-                            const int owner = s_owner[E.d];
-                            int id = -1;
-                            if (owner >= 0) {
-                                const size_t w = (size_t)owner * R + (size_t)E.row;
-                                id = (int)(s_first[E.d] + (long long)prefix[w] + (long long)__popc(masks[w] & ((1u << E.li) - 1u)));
-                            }
-                            out[tv + a] = id;
+                    for (int a = 0; a < 3; a++) {
+                        const int ed = (int)((row >> (4 * (tv + 2 - a))) & 0xF);
+                        const LatticeEdge E = lattice_edge(ed, i, j, k, Mc);
+                        const int owner = s_owner[E.d];
+                        int id = -1;
+                        if (owner >= 0) {
+                            const size_t w = (size_t)owner * R + (size_t)E.row;
+                            id = (int)(s_first[E.d] + (long long)prefix[w] + (long long)__popc(masks[w] & ((1u << E.li) - 1u)));
                         }
+                        out[tv + a] = id;
                     }
                 }
-                run += total;
-            }
-        }
+            });
     }
 }
 

@@ -113,6 +113,50 @@ def test_bit_for_bit_against_the_restatement(built, family, N, s, base):
         assert want["totals"]["cubes_meshed"] <= 1
 
 
+# ---- a selection beyond one batch of the scan and beyond the grid ---------------------------------------------------------------------------
+BIG = 13  # 13^3 = 2197 chunks of 8^3 voxels: 8 x 256 + 149 for the scan's carry, 149 more than the grid of 2048 workgroups
+
+
+@pytest.fixture(scope="module")
+def big():
+    """-> (field, its sorted ids, the map): made once, only read"""
+    N = 8
+    field = vf.dense(N, BIG, SEED, res=RES[N])
+    ids = sorted(field)
+    gm = new_map(N, max_chunks=4096)
+    gm.ScatterChunks(ids, *(np.stack([field[c][k] for c in ids]) for k in range(3)))
+    yield field, ids, gm
+    gm.close()
+
+
+@pytest.mark.parametrize("s", [4, 8])
+def test_every_chunk_of_a_large_map(big, oracle_mod, s):
+    """the scan carries its sum over eight full batches of chunks, and every chunk kernel strides over its grid; at s = 8 the empty
+    chunks among the others are skipped inside the emit kernel's strided loop"""
+    field, ids, gm = big
+    want = cr.coarse_mesh(oracle_mod, field, 8, RES[8], s)
+    assert want["totals"]["chunks"] == BIG ** 3 == 2197 > 8 * 256 and want["totals"]["chunks"] > 2048
+    assert (want["totals"]["chunks_nonempty"] == 2197) if s == 4 else (0 < want["totals"]["chunks_nonempty"] < 2197)
+    assert_mesh(gm.CoarseMesh(s, colors=False, stages=0), want, "13^3 chunks, s %d" % s)
+    assert gm.CoarseMeshSize(s) == want["totals"]
+
+
+def test_a_long_scrambled_list_with_repetitions(big, oracle_mod):
+    field, ids, gm = big
+    s = 4
+    pick = [ids[i] for i in np.random.default_rng(SEED).integers(0, len(ids), 2100)]
+    assert len(set(pick)) < len(pick) and pick != sorted(pick)
+    assert_mesh(gm.CoarseMesh(s, ids=pick, colors=False, stages=0), cr.coarse_mesh(oracle_mod, field, 8, RES[8], s, pick), "a list of 2100")
+    # a non-resident id in the last batch of the scan
+    pick[2099] = (BIG + 7, BIG + 7, BIG + 7)
+    with pytest.raises(KeyError) as e:
+        gm.CoarseMesh(s, ids=pick, colors=False, stages=0)
+    assert "id 2099 " in str(e.value)
+    with pytest.raises(KeyError) as e:
+        gm.CoarseMeshSize(s, ids=pick)
+    assert "id 2099 " in str(e.value)
+
+
 # ---- shading ----------------------------------------------------------------------------------------------------------------------------
 def shade(gm, vertices, face_normals, stages):
     """chisel_hip_shade_vertices on the call's own vertices and face normals; colours start as zeros"""

@@ -133,6 +133,48 @@ def test_bit_for_bit_against_the_restatement(built, family, N, s):
         assert want["owner_table"][0, 1] > 32 * 32 * 32
 
 
+# ---- a selection beyond one batch of the scans and beyond the grid -------------------------------------------------------------------------
+BIG = 13  # 13^3 = 2197 chunks of 8^3 voxels: 8 x 256 + 149 for the scans' carry, 149 more than the grid of 2048 workgroups
+
+
+@pytest.fixture(scope="module")
+def big():
+    """-> (field, its sorted ids, the map): made once, only read"""
+    N = 8
+    field = vf.dense(N, BIG, SEED, res=RES[N])
+    ids = sorted(field)
+    gm = new_map(N, max_chunks=4096)
+    gm.ScatterChunks(ids, *(np.stack([field[c][k] for c in ids]) for k in range(3)))
+    yield field, ids, gm
+    gm.close()
+
+
+@pytest.mark.parametrize("s", [4, 8])
+def test_every_chunk_of_a_large_map(big, oracle_mod, s):
+    """both scans carry their sums over eight full batches, and every chunk and owner kernel strides over its grid"""
+    field, ids, gm = big
+    want = ir.indexed_mesh(oracle_mod, field, 8, RES[8], s)
+    assert want["totals"]["owners"] == want["totals"]["chunks"] == BIG ** 3 == 2197 > 2048
+    assert_mesh(gm.IndexedMesh(s, normals=False, colors=False), want, "13^3 chunks, s %d" % s)
+    assert gm.IndexedMeshSize(s) == want["totals"]
+
+
+def test_a_long_scrambled_list(big, oracle_mod):
+    field, ids, gm = big
+    s = 4
+    pick = [ids[i] for i in np.random.default_rng(SEED).permutation(len(ids))[:300]]
+    assert len(set(pick)) == 300 and pick != sorted(pick)
+    want = ir.indexed_mesh(oracle_mod, field, 8, RES[8], s, selection=pick)
+    # the extras carry the owners' scan into further batches, and some of them own vertices
+    assert want["totals"]["chunks"] == 300 and want["totals"]["owners"] > 3 * 256 and int((want["owner_table"][300:, 1] > 0).sum()) > 0
+    assert_mesh(gm.IndexedMesh(s, ids=pick, normals=False, colors=False), want, "a list of 300")
+    # a non-resident id in the last batch of the chunks' scan
+    pick[299] = (BIG + 7, BIG + 7, BIG + 7)
+    with pytest.raises(KeyError) as e:
+        gm.IndexedMesh(s, ids=pick, normals=False, colors=False)
+    assert "id 299 " in str(e.value)
+
+
 @pytest.mark.parametrize("family,N,s", [("dense", 8, 1), ("thresholds", 8, 2), ("dense", 16, 4)])
 def test_far_from_the_origin(built, family, N, s):
     assert_mesh(built.map(family, N, FAR).IndexedMesh(s, normals=False, colors=False), built.want(family, N, s, FAR), "far %s N %d s %d" % (family, N, s))
