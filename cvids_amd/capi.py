@@ -150,6 +150,15 @@ class IndexedTotals(C.Structure):
 
 assert C.sizeof(IndexedTotals) == 40
 
+
+class ComponentsTotals(C.Structure):
+    """chisel_hip_components_totals (include/chisel_hip.h): what chisel_hip_mesh_components / _filter_mesh found and kept, 64 bytes"""
+    _fields_ = [(n, C.c_int64) for n in ("vertices", "triangles", "invalid_triangles", "components", "largest_triangles", "kept_components",
+                                         "kept_vertices", "kept_triangles")]
+
+
+assert C.sizeof(ComponentsTotals) == 64
+
 ALIGN_CONVERGED, ALIGN_ITERATION_LIMIT, ALIGN_TOO_FEW_PIXELS, ALIGN_DEGENERATE = 0, 1, 2, 3  # CHISEL_HIP_ALIGN_*
 ALIGN_STATUS = {0: "CONVERGED", 1: "ITERATION_LIMIT", 2: "TOO_FEW_PIXELS", 3: "DEGENERATE"}
 
@@ -176,6 +185,7 @@ EXPORTS = [
     "chisel_hip_merge_map", "chisel_hip_deintegrate_depth", "chisel_hip_deintegrate_batch", "chisel_hip_distance_field",
     "chisel_hip_gather_meshes", "chisel_hip_gather_meshes_size", "chisel_hip_save_ply_binary",
     "chisel_hip_gather_chunks", "chisel_hip_scatter_chunks", "chisel_hip_coarse_mesh", "chisel_hip_indexed_mesh",
+    "chisel_hip_mesh_components", "chisel_hip_filter_mesh",
 ]
 # the device self-tests and debug read-outs include/chisel_hip_selftest.h declares
 SELFTEST_EXPORTS = [
@@ -341,6 +351,9 @@ def load_library():
                         ("chisel_hip_coarse_mesh", [vp, C.POINTER(CoarseRequest), C.c_int64, vp, vp, vp, C.c_int, i64p, i32p, C.POINTER(CoarseTotals)]),
                         ("chisel_hip_indexed_mesh", [vp, C.POINTER(CoarseRequest), C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int, i64p, i64p, i32p,
                                                      C.POINTER(IndexedTotals)]),
+                        ("chisel_hip_mesh_components", [vp, C.c_int64, C.c_int64, vp, C.c_int, vp, vp, C.c_int64, i64p, C.POINTER(ComponentsTotals)]),
+                        ("chisel_hip_filter_mesh", [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp,
+                                                    vp, vp, C.c_int, C.POINTER(ComponentsTotals)]),
                         ("chisel_hip_kat_color_fresh", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_kat_color_any", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_debug_cloud_stats", [vp, i64p]),

@@ -1041,7 +1041,10 @@ class Chisel:
     def SaveIndexedMeshPLY(self, filename, stride, binary=True):
         """the indexed mesh of every resident chunk (IndexedMesh) as a PLY file with a real face list: binary=False as SaveMeshPLYASCII
         writes a mesh (chisel_hip_write_mesh_ply), binary=True with SaveMeshPLYBinary's elements and properties"""
-        mesh = self.IndexedMesh(stride, normals=False, colors=self.use_color)
+        return self._write_indexed_ply(filename, self.IndexedMesh(stride, normals=False, colors=self.use_color), binary)
+
+    def _write_indexed_ply(self, filename, mesh, binary):
+        """the writer of SaveIndexedMeshPLY and SaveCleanMeshPLY: a dict with "vertices", "indices" and "colors" (or None), numpy"""
         v = np.ascontiguousarray(mesh["vertices"], np.float32)
         c = np.ascontiguousarray(mesh["colors"], np.float32) if mesh["colors"] is not None else None
         if not binary:
@@ -1065,6 +1068,136 @@ class Chisel:
         except OSError:
             return False
         return True
+
+    @staticmethod
+    def _is_tensor(a):
+        return a is not None and not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
+
+    @staticmethod
+    def _device_rows(t, name, dtype, width, rows):
+        """a contiguous CUDA tensor of (>= rows, width) (width 0: one dimension) -> its address, None without a row to write"""
+        import torch
+        if t is None:
+            return None
+        shape_ok = (t.dim() == 2 and t.shape[1] == width) if width else t.dim() == 1
+        assert t.is_cuda and t.dtype == getattr(torch, dtype) and t.is_contiguous() and shape_ok, \
+            "%s: a contiguous torch.%s CUDA tensor of shape (rows%s)" % (name, dtype, ", %d" % width if width else "")
+        assert t.shape[0] >= rows, "%s: %d rows, %d are needed" % (name, t.shape[0], rows)
+        return t.data_ptr() if rows and t.numel() else None
+
+    def _components_call(self, entry, *args):
+        """chisel_hip_mesh_components / _filter_mesh -> the totals"""
+        totals = capi.ComponentsTotals()
+        check(entry(self.h, *args, C.byref(totals)))
+        return self._totals_dict(totals)
+
+    def MeshComponents(self, indices, n_vertices=None, out=None):
+        """chisel_hip_mesh_components: the connected components of the graph whose vertices are 0 ... n_vertices - 1 and whose edges
+        are the sides of the triangles `indices` -- a numpy (T, 3) int32 array (n_vertices=None: indices.max() + 1) or a contiguous
+        torch CUDA int32 tensor (n_vertices is required), for instance IndexedMesh's.  A triangle with an id outside [0, n_vertices)
+        joins nothing and has component -1.  Components are numbered by ascending smallest vertex id.  -> {"vertex_component": (V,)
+        int32, "triangle_component": (T,) int32, "table": (C, 3) int64 -- root, vertices, triangles of every component --, "totals"};
+        the labels are numpy arrays for numpy indices and CUDA tensors for a tensor.  `out`: a dict of contiguous CUDA int32 tensors
+        "vertex_component" (>= V rows) and / or "triangle_component" (>= T rows): exactly those are filled in place on the map's
+        stream; it is returned with "table" and "totals" (host) added.  The map itself is not touched."""
+        entry = self.L.chisel_hip_mesh_components
+        names = ("vertex_component", "triangle_component")
+        if self._is_tensor(indices):
+            import torch
+            assert n_vertices is not None, "n_vertices is required for a tensor"
+            V, T = int(n_vertices), int(indices.shape[0])
+            src = self._device_rows(indices, "indices", "int32", 3, T)
+            if out is None:
+                out = {"vertex_component": torch.empty(V, dtype=torch.int32, device=indices.device),
+                       "triangle_component": torch.empty(T, dtype=torch.int32, device=indices.device)}
+            assert not set(out) - set(names), "out: unknown outputs %s" % sorted(set(out) - set(names))
+            ptrs = [self._device_rows(out.get(name), "out[%r]" % name, "int32", 0, rows) for name, rows in zip(names, (V, T))]
+            table = np.zeros((V, 3), np.int64)
+            totals = self._components_call(entry, V, T, src, 1, ptrs[0], ptrs[1], V, self._table_ptr(table, C.c_int64))
+            self._keep = [indices, out]
+            res = dict(out)
+            res.update(table=table[:totals["components"]], totals=totals)
+            return res
+        assert out is None, "out: device tensors go with a tensor of indices"
+        idx = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
+        T = len(idx)
+        V = int(n_vertices) if n_vertices is not None else (max(int(idx.max()) + 1, 0) if T else 0)
+        vc, tc, table = np.empty(V, np.int32), np.empty(T, np.int32), np.zeros((V, 3), np.int64)
+        totals = self._components_call(entry, V, T, idx.ctypes.data if T else None, 0, vc.ctypes.data if V else None, tc.ctypes.data if T else None, V,
+                                       self._table_ptr(table, C.c_int64))
+        return {"vertex_component": vc, "triangle_component": tc, "table": table[:totals["components"]], "totals": totals}
+
+    _FILTER_OUTPUTS = (("vertices", "float32", 3, "V"), ("indices", "int32", 3, "T"), ("normals", "float32", 3, "V"), ("colors", "float32", 3, "V"),
+                       ("vertex_map", "int32", 0, "V"), ("triangle_map", "int32", 0, "T"))
+
+    def FilterMesh(self, mesh, min_triangles=1, largest_only=False, out=None):
+        """chisel_hip_filter_mesh: `mesh` -- the dict IndexedMesh returns, numpy or its `out` form with CUDA tensors; the number of
+        vertices and triangles is its "totals" entry where it has one, else the arrays' rows -- without the connected components
+        (MeshComponents) of fewer than `min_triangles` triangles; with largest_only only the component with the most triangles, the
+        lowest-numbered of equals, if it has min_triangles.  Kept vertices and triangles keep their order, ids are renumbered, the
+        rows of "vertices", "normals" and "colors" are copied bit for bit.  -> {"vertices", "indices", "normals", "colors" (None where
+        the mesh has none), "vertex_map": (V,) int32, "triangle_map": (T,) int32 -- old -> new, -1 when dropped --, "totals"}, of the
+        mesh's kind (numpy arrays, or CUDA tensors narrowed to the kept rows).  `out`: a dict of contiguous CUDA tensors named like
+        the result: exactly those are filled in place on the map's stream, without a wait behind the one for the totals; it is
+        returned with "totals" added.  The per-chunk tables are not carried over; the map itself is not touched."""
+        entry = self.L.chisel_hip_filter_mesh
+        v, idx, tot = mesh["vertices"], mesh["indices"], mesh.get("totals")
+        have = {"vertices": v, "indices": idx, "normals": mesh.get("normals"), "colors": mesh.get("colors")}
+        V = int(tot["vertices"]) if tot and "vertices" in tot else int(v.shape[0])
+        T = int(tot["triangles"]) if tot and "triangles" in tot else int(idx.shape[0])
+        head = (V, T)
+        knobs = (int(min_triangles), int(largest_only))
+        if self._is_tensor(v):
+            import torch
+            narrowed = out is None
+            if narrowed:
+                rows = {"V": V, "T": T}
+                out = {name: torch.empty((rows[n], width) if width else (rows[n],), dtype=getattr(torch, dtype), device=v.device)
+                       for name, dtype, width, n in self._FILTER_OUTPUTS if name not in have or have[name] is not None}
+            unknown = set(out) - {row[0] for row in self._FILTER_OUTPUTS}
+            assert not unknown, "out: unknown outputs %s" % sorted(unknown)
+            src = [self._device_rows(have[name], "mesh[%r]" % name, dtype, 3, V if n == "V" else T) if (name in out or name == "indices") else None
+                   for name, dtype, _, n in self._FILTER_OUTPUTS[:4]]
+            cap = {"V": None, "T": None}
+            for name, dtype, width, n in self._FILTER_OUTPUTS[:4]:
+                if name in out:
+                    cap[n] = min(cap[n], int(out[name].shape[0])) if cap[n] is not None else int(out[name].shape[0])
+            cap_v = cap["V"] if cap["V"] is not None else 1  # (maps alone: any capacity but the size query's)
+            cap_t = cap["T"] if cap["T"] is not None else 1
+            for name, dtype, width, n in self._FILTER_OUTPUTS[:4]:  # (kind and shape; the rows are the capacity)
+                self._device_rows(out.get(name), "out[%r]" % name, dtype, width, 0)
+            dst = [out[name].data_ptr() if name in out and out[name].numel() else None for name, *_ in self._FILTER_OUTPUTS[:4]]
+            maps = [self._device_rows(out.get(name), "out[%r]" % name, "int32", 0, V if n == "V" else T) for name, _, _, n in self._FILTER_OUTPUTS[4:]]
+            totals = self._components_call(entry, *head, src[1], src[0], src[2], src[3], *knobs, cap_v, cap_t, dst[0], dst[1], dst[2], dst[3], maps[0], maps[1], 1)
+            assert (cap["V"] is None or totals["kept_vertices"] <= cap_v) and (cap["T"] is None or totals["kept_triangles"] <= cap_t), "out: tensors without room"
+            self._keep = [mesh, out]
+            res = dict(out)
+            if narrowed:
+                for name, _, _, n in self._FILTER_OUTPUTS[:4]:
+                    res[name] = out[name][:totals["kept_vertices" if n == "V" else "kept_triangles"]] if name in out else None
+            res["totals"] = totals
+            return res
+        assert out is None, "out: device tensors go with a mesh of tensors"
+        arr = {"vertices": np.ascontiguousarray(v, np.float32).reshape(-1, 3)[:V], "indices": np.ascontiguousarray(idx, np.int32).reshape(-1, 3)[:T]}
+        for name in ("normals", "colors"):
+            arr[name] = np.ascontiguousarray(have[name], np.float32).reshape(-1, 3)[:V] if have[name] is not None else None
+        res = {name: (np.empty_like(arr[name]) if arr[name] is not None else None) for name in arr}
+        res["vertex_map"], res["triangle_map"] = np.empty(V, np.int32), np.empty(T, np.int32)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        totals = self._components_call(entry, *head, ptr(arr["indices"]), ptr(arr["vertices"]), ptr(arr["normals"]), ptr(arr["colors"]), *knobs, max(V, 1), max(T, 1),
+                                       ptr(res["vertices"]), ptr(res["indices"]), ptr(res["normals"]), ptr(res["colors"]), ptr(res["vertex_map"]),
+                                       ptr(res["triangle_map"]), 0)
+        for name, _, _, n in self._FILTER_OUTPUTS[:4]:
+            if res[name] is not None:
+                res[name] = res[name][:totals["kept_vertices" if n == "V" else "kept_triangles"]]
+        res["totals"] = totals
+        return res
+
+    def SaveCleanMeshPLY(self, filename, stride, min_triangles, largest_only=False, binary=True):
+        """SaveIndexedMeshPLY without the connected components of fewer than `min_triangles` triangles (FilterMesh): the indexed mesh
+        of every resident chunk, filtered on the device, through the same writer"""
+        mesh = self.IndexedMesh(stride, normals=False, colors=self.use_color)
+        return self._write_indexed_ply(filename, self.FilterMesh(mesh, min_triangles, largest_only), binary)
 
     def AlignTerms(self, depth, pose, camera, max_residual=0.0, out=None):
         """chisel_hip_align_terms: the normal equations of one Gauss-Newton step that aligns the depth image (numpy, or a torch CUDA

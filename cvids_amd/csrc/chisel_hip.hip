@@ -51,6 +51,8 @@
 #include "kernels_coarse.h"
 #include "indexed_checks.h"
 #include "kernels_indexed.h"
+#include "components_checks.h"
+#include "kernels_components.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
 #include "kernels_stereo_prep.h"
@@ -457,6 +459,11 @@ struct chisel_hip_map {
         DeviceBuffer<long long> owner_first, tri_first;                // [owners] the vertices in front of every owner | [n] the triangles in front of every chunk
         PinnedWords host;                                              // [INDEXED_HOST_WORDS + 2 n + 2 owners] where totals and tables reach the host
     } indexed_mem;
+    struct ComponentsMemory {                                          // chisel_hip_mesh_components / _filter_mesh (host_components.h), allocated on first use, grown on demand
+        DeviceBuffer<int> words;                                       // [6 V + T + tiles] parent, root_of, both counts per root, number and kept-vertex prefix | kept-triangle prefix | tile sums
+        DeviceBuffer<unsigned long long> ctl;                          // [COMPONENTS_HOST_WORDS] the control words (CC_*)
+        PinnedWords host, table_host;                                  // where the control words reach the host | [3 components] the table's rows
+    } components_mem;
     // profiling
     bool profiling = false;
     std::vector<ProfEvent> prof_live;
@@ -3033,4 +3040,5 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 #include "host_chunks.h"
 #include "host_coarse.h"
 #include "host_indexed.h"
+#include "host_components.h"
 #include "host_selftest.h"

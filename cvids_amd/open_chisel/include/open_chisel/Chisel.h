@@ -778,6 +778,37 @@ class ChunkManager {  // ChunkManager.h:57-216 over one chisel_hip_map
         }
         for (int64_t i = 0; i < 3 * totals.triangles; i++) mesh->indices.push_back((size_t)ix[(size_t)i]);
     }
+    // Not in the reference: `in` (an indexed mesh: GenerateIndexedMesh's, or any whose indices name its vertices) without the
+    // connected components of fewer than minTriangles triangles (chisel_hip_filter_mesh); with largestOnly only the component with
+    // the most triangles.  Kept vertices and triangles keep their order, indices are renumbered, normals and colours are carried
+    // over where `in` has one per vertex; no grids.  `in` and `out` may be the same mesh.  totals: what was found and kept.
+    void FilterMesh(const Mesh &in, int64_t minTriangles, bool largestOnly, Mesh *out, chisel_hip_components_totals *totals = nullptr) const {
+        const size_t n = in.vertices.size(), t = in.indices.size() / 3;
+        const bool hasNormals = in.normals.size() == n && n > 0, hasColors = in.colors.size() == n && n > 0;
+        std::vector<float> ve(3 * n), no(hasNormals ? 3 * n : 0), co(hasColors ? 3 * n : 0);
+        std::vector<int32_t> ix(3 * t);
+        for (size_t i = 0; i < n; i++)
+            for (int k = 0; k < 3; k++) {
+                ve[3 * i + k] = in.vertices[i](k);
+                if (hasNormals) no[3 * i + k] = in.normals[i](k);
+                if (hasColors) co[3 * i + k] = in.colors[i](k);
+            }
+        for (size_t i = 0; i < 3 * t; i++) ix[i] = in.indices[i] > (size_t)INT32_MAX ? -1 : (int32_t)in.indices[i];  // (an id no vertex has: an invalid triangle)
+        std::vector<float> ove(ve.size()), ono(no.size()), oco(co.size());
+        std::vector<int32_t> oix(ix.size());
+        chisel_hip_components_totals found{};
+        hip_check(chisel_hip_filter_mesh(map, (int64_t)n, (int64_t)t, ix.data(), ve.data(), hasNormals ? no.data() : nullptr, hasColors ? co.data() : nullptr, minTriangles,
+                                         largestOnly ? 1 : 0, (int64_t)std::max<size_t>(n, 1), (int64_t)std::max<size_t>(t, 1), n ? ove.data() : nullptr,
+                                         n && t ? oix.data() : nullptr, hasNormals ? ono.data() : nullptr, hasColors ? oco.data() : nullptr, nullptr, nullptr, 0, &found));
+        out->Clear();
+        for (int64_t i = 0; i < found.kept_vertices; i++) {
+            out->vertices.push_back(Vec3(ove[3 * i], ove[3 * i + 1], ove[3 * i + 2]));
+            if (hasNormals) out->normals.push_back(Vec3(ono[3 * i], ono[3 * i + 1], ono[3 * i + 2]));
+            if (hasColors) out->colors.push_back(Vec3(oco[3 * i], oco[3 * i + 1], oco[3 * i + 2]));
+        }
+        for (int64_t i = 0; i < 3 * found.kept_triangles; i++) out->indices.push_back((size_t)oix[(size_t)i]);
+        if (totals) *totals = found;
+    }
     bool HasMesh(const ChunkID &id) const {
         const int v[3] = {id(0), id(1), id(2)};
         int64_t nv = 0, ng = 0;
@@ -1050,6 +1081,24 @@ class Chisel {  // Chisel.h:38-230
     bool SaveIndexedMeshToPLY(const std::string &filename, int stride) {
         Mesh mesh;
         chunkManager.GenerateIndexedMesh(stride, &mesh);
+        const size_t n = mesh.vertices.size();
+        std::vector<float> v(3 * n), c(mesh.colors.size() == n ? 3 * n : 0);
+        std::vector<int64_t> idx(mesh.indices.begin(), mesh.indices.end());
+        for (size_t i = 0; i < n; i++)
+            for (int k = 0; k < 3; k++) {
+                v[3 * i + k] = mesh.vertices[i](k);
+                if (!c.empty()) c[3 * i + k] = mesh.colors[i](k);
+            }
+        const int rc = chisel_hip_write_mesh_ply(filename.c_str(), v.data(), c.empty() ? nullptr : c.data(), (int64_t)n, idx.data(), (int64_t)idx.size());
+        if (rc == CHISEL_HIP_ERR_IO) return false;
+        hip_check(rc);
+        return true;
+    }
+    // SaveIndexedMeshToPLY without the connected components of fewer than minTriangles triangles (ChunkManager::FilterMesh)
+    bool SaveCleanMeshToPLY(const std::string &filename, int stride, int64_t minTriangles) {
+        Mesh mesh;
+        chunkManager.GenerateIndexedMesh(stride, &mesh);
+        chunkManager.FilterMesh(mesh, minTriangles, false, &mesh);
         const size_t n = mesh.vertices.size();
         std::vector<float> v(3 * n), c(mesh.colors.size() == n ? 3 * n : 0);
         std::vector<int64_t> idx(mesh.indices.begin(), mesh.indices.end());

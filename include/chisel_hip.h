@@ -49,7 +49,8 @@ extern "C" {
  *      chisel_hip_align_solve, chisel_hip_align_depth, chisel_hip_merge_map, chisel_hip_deintegrate_depth, chisel_hip_deintegrate_batch,
  *      chisel_hip_distance_field, chisel_hip_gather_meshes,
  *      chisel_hip_gather_meshes_size, chisel_hip_save_ply_binary, chisel_hip_gather_chunks, chisel_hip_scatter_chunks, chisel_hip_coarse_mesh,
- *      chisel_hip_indexed_mesh (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
+ *      chisel_hip_indexed_mesh, chisel_hip_mesh_components, chisel_hip_filter_mesh (no slot in the hipEvent profiler:
+ *      CHISEL_HIP_NUM_KERNELS stays) */
 #define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -422,6 +423,56 @@ int chisel_hip_indexed_mesh(chisel_hip_map *map, const chisel_hip_coarse_request
                             int64_t capacity_triangles, float *vertices, int32_t *indices, float *normals, float *colors,
                             int on_device, int64_t *chunk_table, int64_t *owner_table, int *owner_ids_xyz,
                             chisel_hip_indexed_totals *totals);
+
+/* ---- connected components of an indexed mesh, and the mesh without its small ones (DESIGN.md 3.16 "Mesh components") ----
+ * Not in the reference, whose meshes share no vertex.  Input: n_vertices = V, n_triangles = T, indices: 3 int32 per triangle (what
+ * chisel_hip_indexed_mesh writes, or any index array).  A triangle is VALID when all three ids lie in [0, V); an invalid one joins
+ * nothing, has component -1, is never kept and is counted in totals.invalid_triangles -- the kernels test the three ids before they
+ * use any as an address: an array of garbage gives a wrong answer, never a fault.  The COMPONENTS are those of the graph on the V
+ * vertices whose edges are the sides of the valid triangles; a triangle with repeated ids is valid and joins what it names; a vertex
+ * in no valid triangle is a component of its own with 0 triangles.  A component's ROOT is its smallest vertex id; components are
+ * numbered 0 ... C - 1 by ascending root.  vertex_component[v]: the number of v's component; triangle_component[t]: that of its
+ * first id, or -1; component_table: 3 int64 per component -- root, vertices, valid triangles.  FILTER: component c is KEPT when
+ * triangles(c) >= min_triangles (>= 1); with largest_only it must in addition be the component with the most triangles, the lowest
+ * number winning a tie.  Kept vertices keep their order and are renumbered 0 ... V' - 1, kept triangles keep theirs and their ids
+ * are renumbered; the rows of vertices, normals and colors are copied bit for bit; vertex_map[V] and triangle_map[T] say old -> new,
+ * -1 when dropped.  Everything is a pure function of (V, T, indices, min_triangles, largest_only): no float is computed. */
+typedef struct { int64_t vertices, triangles, invalid_triangles, components, largest_triangles, kept_components, kept_vertices, kept_triangles; } chisel_hip_components_totals;
+/* The map is neither read nor written: it lends its device, its stream and its scratch (a group is refused with
+ * CHISEL_HIP_ERR_UNSUPPORTED; hand in a map of one shard).  Everything is queued on the map's stream behind what is queued, a
+ * chisel_hip_indexed_mesh(on_device) whose outputs are this call's inputs included.  on_device says where ALL array arguments live,
+ * inputs and outputs alike; component_table and totals are always host memory.  Host arrays are staged through owned device buffers,
+ * copied out once with exactly their live rows, and complete on return.  The host waits once, for the totals (pinned memory); with
+ * on_device nothing is waited for behind the launches that write the arrays -- except for component_table, whose rows (their number
+ * is a total) are written to pinned memory behind that wait and waited for.  vertex_component (V), triangle_component (T) and
+ * component_table (room for capacity_components rows; capacity 0: not asked for) may be NULL; with none of them asked for the call
+ * is the size query: totals is filled and nothing else is written.  A table capacity below the number of components is refused
+ * with totals filled.  totals: vertices, triangles, invalid_triangles, components, largest_triangles (the most valid triangles of
+ * one component); kept_* are 0 (no filter is applied).  V = 0 and T = 0 succeed with zero totals and nothing launched.  The scratch
+ * (6 ints per vertex, 1 per triangle, tile sums) is kept in the map, grown on demand and freed with it.
+ * Refused with nothing written: CHISEL_HIP_ERR_INVALID for a null map, negative sizes or capacity, null indices with T > 0, a
+ * capacity without a table, the size query without totals; CHISEL_HIP_ERR_UNSUPPORTED for V or 3 T above 2^31 - 1. */
+int chisel_hip_mesh_components(chisel_hip_map *map, int64_t n_vertices, int64_t n_triangles, const int32_t *indices, int on_device,
+                               int32_t *vertex_component, int32_t *triangle_component,
+                               int64_t capacity_components, int64_t *component_table,
+                               chisel_hip_components_totals *totals);
+/* The frame of chisel_hip_mesh_components.  vertices, normals, colors: 3 floats per vertex, read only where the matching output is
+ * written; out_vertices, out_normals, out_colors have room for capacity_vertices rows, out_indices for capacity_triangles; the
+ * outputs must not overlap the inputs.  vertex_map (V) and triangle_map (T) are optional and sized by the input.  Both capacities
+ * 0 is the size query: totals (all eight) is filled and nothing else is written.  A capacity below its total, of an array that is
+ * asked for, is refused with totals filled, so that the caller can retry.  With on_device nothing is waited for behind the
+ * compaction launches.
+ * Refused with nothing written: what chisel_hip_mesh_components refuses about sizes and indices; min_triangles < 1; largest_only
+ * outside 0 / 1; negative capacities; the size query without totals; an output (vertices, normals, colors) without the matching
+ * input; normals or colors in without the matching output where out_vertices is asked for; out_indices, out_normals or out_colors
+ * without out_vertices. */
+int chisel_hip_filter_mesh(chisel_hip_map *map, int64_t n_vertices, int64_t n_triangles, const int32_t *indices,
+                           const float *vertices, const float *normals, const float *colors,
+                           int64_t min_triangles, int largest_only,
+                           int64_t capacity_vertices, int64_t capacity_triangles,
+                           float *out_vertices, int32_t *out_indices, float *out_normals, float *out_colors,
+                           int32_t *vertex_map, int32_t *triangle_map, int on_device,
+                           chisel_hip_components_totals *totals);
 
 /* ---- meshing a sharded map (SURVEY.md 8e "meshing across shards") -------------------------------------------------
  * A chunk's mesh reads its 26 neighbours (cube corners: ChunkManager.cpp:316-357; gradient normals and colours of border
