@@ -159,6 +159,17 @@ class ComponentsTotals(C.Structure):
 
 assert C.sizeof(ComponentsTotals) == 64
 
+
+class AdjacencyTotals(C.Structure):
+    """chisel_hip_adjacency_totals (include/chisel_hip.h): what chisel_hip_mesh_adjacency / _mesh_vertex_normals / _smooth_mesh found, 96 bytes"""
+    _fields_ = [(n, C.c_int64) for n in ("vertices", "triangles", "invalid_triangles", "incidences", "neighbors", "max_incident", "max_neighbors",
+                                         "boundary_vertices", "nonmanifold_vertices", "isolated_vertices", "pinned_vertices", "reserved")]
+
+
+assert C.sizeof(AdjacencyTotals) == 96
+MESH_MAX_INCIDENT = 32  # CHISEL_HIP_MESH_MAX_INCIDENT
+MESH_BOUNDARY, MESH_NONMANIFOLD, MESH_ISOLATED = 1, 2, 4  # CHISEL_HIP_MESH_*
+
 ALIGN_CONVERGED, ALIGN_ITERATION_LIMIT, ALIGN_TOO_FEW_PIXELS, ALIGN_DEGENERATE = 0, 1, 2, 3  # CHISEL_HIP_ALIGN_*
 ALIGN_STATUS = {0: "CONVERGED", 1: "ITERATION_LIMIT", 2: "TOO_FEW_PIXELS", 3: "DEGENERATE"}
 
@@ -186,6 +197,7 @@ EXPORTS = [
     "chisel_hip_gather_meshes", "chisel_hip_gather_meshes_size", "chisel_hip_save_ply_binary",
     "chisel_hip_gather_chunks", "chisel_hip_scatter_chunks", "chisel_hip_coarse_mesh", "chisel_hip_indexed_mesh",
     "chisel_hip_mesh_components", "chisel_hip_filter_mesh",
+    "chisel_hip_mesh_adjacency", "chisel_hip_mesh_vertex_normals", "chisel_hip_smooth_mesh",
 ]
 # the device self-tests and debug read-outs include/chisel_hip_selftest.h declares
 SELFTEST_EXPORTS = [
@@ -354,6 +366,10 @@ def load_library():
                         ("chisel_hip_mesh_components", [vp, C.c_int64, C.c_int64, vp, C.c_int, vp, vp, C.c_int64, i64p, C.POINTER(ComponentsTotals)]),
                         ("chisel_hip_filter_mesh", [vp, C.c_int64, C.c_int64, vp, vp, vp, vp, C.c_int64, C.c_int, C.c_int64, C.c_int64, vp, vp, vp, vp,
                                                     vp, vp, C.c_int, C.POINTER(ComponentsTotals)]),
+                        ("chisel_hip_mesh_adjacency", [vp, C.c_int64, C.c_int64, vp, C.c_int, vp, C.c_int64, vp, vp, C.c_int64, vp, vp, C.POINTER(AdjacencyTotals)]),
+                        ("chisel_hip_mesh_vertex_normals", [vp, C.c_int64, C.c_int64, vp, vp, C.c_int, vp, C.POINTER(AdjacencyTotals)]),
+                        ("chisel_hip_smooth_mesh", [vp, C.c_int64, C.c_int64, vp, vp, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, vp, vp,
+                                                    C.POINTER(AdjacencyTotals)]),
                         ("chisel_hip_kat_color_fresh", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_kat_color_any", [C.POINTER(C.c_uint)]),
                         ("chisel_hip_debug_cloud_stats", [vp, i64p]),

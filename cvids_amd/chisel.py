@@ -1199,6 +1199,137 @@ class Chisel:
         mesh = self.IndexedMesh(stride, normals=False, colors=self.use_color)
         return self._write_indexed_ply(filename, self.FilterMesh(mesh, min_triangles, largest_only), binary)
 
+    MESH_BOUNDARY, MESH_NONMANIFOLD, MESH_ISOLATED = capi.MESH_BOUNDARY, capi.MESH_NONMANIFOLD, capi.MESH_ISOLATED
+    _ADJACENCY_OUTPUTS = ("tri_offsets", "tri_items", "nbr_offsets", "nbr_items", "flags")
+
+    def _adjacency_call(self, entry, *args):
+        """chisel_hip_mesh_adjacency / _mesh_vertex_normals / _smooth_mesh -> the totals"""
+        totals = capi.AdjacencyTotals()
+        check(entry(self.h, *args, C.byref(totals)))
+        return self._totals_dict(totals)
+
+    def MeshAdjacency(self, indices, n_vertices=None, out=None):
+        """chisel_hip_mesh_adjacency: the vertex -> triangle incidence and the vertex -> vertex neighbour rows of the triangles
+        `indices` over the vertices 0 ... n_vertices - 1 -- a numpy (T, 3) int32 array (n_vertices=None: indices.max() + 1) or a
+        contiguous torch CUDA int32 tensor (n_vertices is required), for instance IndexedMesh's.  A triangle with an id outside
+        [0, n_vertices) takes part in nothing.  -> {"tri_offsets": (V + 1,), "tri_items": (incidences,), "nbr_offsets": (V + 1,),
+        "nbr_items": (neighbors,), "flags": (V,) int32 -- bit 0 MESH_BOUNDARY, bit 1 MESH_NONMANIFOLD, bit 2 MESH_ISOLATED --,
+        "totals"}: row v of a pair is items[offsets[v]:offsets[v + 1]], ascending; numpy arrays for numpy indices, CUDA tensors for a
+        tensor.  `out`: a dict of contiguous CUDA int32 tensors named like the result (3 T and 6 T items are always enough): exactly
+        those are filled in place on the map's stream; it is returned with "totals" (host) added.  An index array with more than
+        capi.MESH_MAX_INCIDENT triangles at one vertex is refused.  The map itself is not touched."""
+        entry = self.L.chisel_hip_mesh_adjacency
+        names = self._ADJACENCY_OUTPUTS
+        if self._is_tensor(indices):
+            import torch
+            assert n_vertices is not None, "n_vertices is required for a tensor"
+            V, T = int(n_vertices), int(indices.shape[0])
+            src = self._device_rows(indices, "indices", "int32", 3, T)
+            narrowed = out is None
+            if narrowed:
+                size = self._adjacency_call(entry, V, T, src, 1, None, 0, None, None, 0, None, None)
+                rows = {"tri_offsets": V + 1, "tri_items": size["incidences"], "nbr_offsets": V + 1, "nbr_items": size["neighbors"], "flags": V}
+                out = {name: torch.empty(rows[name], dtype=torch.int32, device=indices.device) for name in names}
+            assert not set(out) - set(names), "out: unknown outputs %s" % sorted(set(out) - set(names))
+            need = {"tri_offsets": V + 1, "tri_items": 0, "nbr_offsets": V + 1, "nbr_items": 0, "flags": V}
+            ptrs = {name: self._device_rows(out.get(name), "out[%r]" % name, "int32", 0, need[name]) for name in names}
+            cap = {name: int(out[name].shape[0]) if name in out else 0 for name in ("tri_items", "nbr_items")}
+            for name in cap:  # (an empty tensor has no address: it stands for its array only when there is nothing to write)
+                ptrs[name] = out[name].data_ptr() if cap[name] else None
+            totals = self._adjacency_call(entry, V, T, src, 1, ptrs["tri_offsets"], cap["tri_items"], ptrs["tri_items"], ptrs["nbr_offsets"], cap["nbr_items"],
+                                          ptrs["nbr_items"], ptrs["flags"])
+            assert ("tri_items" not in out or totals["incidences"] <= cap["tri_items"]) and ("nbr_items" not in out or totals["neighbors"] <= cap["nbr_items"]), \
+                "out: tensors without room"
+            self._keep = [indices, out]
+            res = dict(out)
+            res["totals"] = totals
+            return res
+        assert out is None, "out: device tensors go with a tensor of indices"
+        idx = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
+        T = len(idx)
+        V = int(n_vertices) if n_vertices is not None else (max(int(idx.max()) + 1, 0) if T else 0)
+        src = idx.ctypes.data if T else None
+        size = self._adjacency_call(entry, V, T, src, 0, None, 0, None, None, 0, None, None)
+        res = {"tri_offsets": np.empty(V + 1, np.int32), "tri_items": np.empty(size["incidences"], np.int32), "nbr_offsets": np.empty(V + 1, np.int32),
+               "nbr_items": np.empty(size["neighbors"], np.int32), "flags": np.empty(V, np.int32)}
+        ptr = lambda a: a.ctypes.data if a.size else None
+        res["totals"] = self._adjacency_call(entry, V, T, src, 0, ptr(res["tri_offsets"]), size["incidences"], ptr(res["tri_items"]), ptr(res["nbr_offsets"]),
+                                             size["neighbors"], ptr(res["nbr_items"]), ptr(res["flags"]))
+        return res
+
+    def _mesh_arrays(self, mesh):
+        """the "vertices" and "indices" of a mesh dict, and its sizes (its "totals" entry where it has one, else the arrays' rows) ->
+        (V, T, vertices, indices, on_device, their addresses)"""
+        v, idx, tot = mesh["vertices"], mesh["indices"], mesh.get("totals")
+        V = int(tot["kept_vertices" if "kept_vertices" in tot else "vertices"]) if tot and ("vertices" in tot or "kept_vertices" in tot) else int(v.shape[0])
+        T = int(tot["kept_triangles" if "kept_triangles" in tot else "triangles"]) if tot and ("triangles" in tot or "kept_triangles" in tot) else int(idx.shape[0])
+        if self._is_tensor(v):
+            return V, T, v, idx, 1, self._device_rows(v, "mesh['vertices']", "float32", 3, V), self._device_rows(idx, "mesh['indices']", "int32", 3, T)
+        v = np.ascontiguousarray(v, np.float32).reshape(-1, 3)[:V]
+        idx = np.ascontiguousarray(idx, np.int32).reshape(-1, 3)[:T]
+        return V, T, v, idx, 0, v.ctypes.data if V else None, idx.ctypes.data if T else None
+
+    def MeshVertexNormals(self, mesh, out=None):
+        """chisel_hip_mesh_vertex_normals: the normals that belong to the triangles of `mesh` -- a dict with "vertices" and "indices"
+        as IndexedMesh / FilterMesh / SmoothMesh return it, numpy or CUDA tensors --: per vertex the sum of its incident triangles'
+        un-normalised face normals (area-weighted, pointing where the coarse mesh's face normals point), added in ascending triangle
+        order and normalised; zeros for a vertex without a triangle of non-zero area.  -> (V, 3) float32, of the mesh's kind.  `out`:
+        a contiguous CUDA float32 tensor of (>= V, 3), filled in place on the map's stream and returned."""
+        V, T, v, idx, on_device, pv, pi = self._mesh_arrays(mesh)
+        if on_device:
+            import torch
+            if out is None:
+                out = torch.empty((V, 3), dtype=torch.float32, device=v.device)
+            dst = self._device_rows(out, "out", "float32", 3, V)
+            self._adjacency_call(self.L.chisel_hip_mesh_vertex_normals, V, T, pi, pv, 1, dst)
+            self._keep = [mesh, out]
+            return out
+        assert out is None, "out: a device tensor goes with a mesh of tensors"
+        normals = np.empty((V, 3), np.float32)
+        self._adjacency_call(self.L.chisel_hip_mesh_vertex_normals, V, T, pi, pv, 0, normals.ctypes.data if V else None)
+        return normals
+
+    def SmoothMesh(self, mesh, iterations=10, lam=0.5, mu=-0.53, pin=capi.MESH_BOUNDARY | capi.MESH_NONMANIFOLD, normals=True, out=None):
+        """chisel_hip_smooth_mesh: Taubin lambda | mu smoothing of `mesh` -- the dict IndexedMesh / FilterMesh return, numpy or CUDA
+        tensors -- over the 1-ring: an iteration moves every vertex by lam times the way to its neighbours' mean, then by mu times
+        (mu < 0: it does not shrink the surface; mu == 0: plain Laplacian smoothing).  Vertices whose flags (MeshAdjacency) meet `pin`
+        -- by default the open rim and the non-manifold ones -- and those without a neighbour stay where they are.  -> the mesh's
+        dict with "vertices" smoothed, "normals" the vertex normals of the smoothed positions (MeshVertexNormals; None with
+        normals=False), "indices" and "colors" carried over unchanged, and "totals" (pinned_vertices among them).  `out`: a dict of
+        contiguous CUDA float32 tensors "vertices" (>= V, 3) and optionally "normals": filled in place on the map's stream, without a
+        wait behind the one for the totals; it is returned with the carried-over entries and "totals" added."""
+        entry = self.L.chisel_hip_smooth_mesh
+        V, T, v, idx, on_device, pv, pi = self._mesh_arrays(mesh)
+        knobs = (int(iterations), float(lam), float(mu), int(pin))
+        res = {"indices": mesh["indices"], "colors": mesh.get("colors")}
+        if on_device:
+            import torch
+            if out is None:
+                out = {"vertices": torch.empty((V, 3), dtype=torch.float32, device=v.device)}
+                if normals:
+                    out["normals"] = torch.empty((V, 3), dtype=torch.float32, device=v.device)
+            assert "vertices" in out and not set(out) - {"vertices", "normals"}, "out: \"vertices\" and optionally \"normals\""
+            dst = [self._device_rows(out.get(name), "out[%r]" % name, "float32", 3, V) for name in ("vertices", "normals")]
+            totals = self._adjacency_call(entry, V, T, pi, pv, *knobs, 1, dst[0], dst[1])
+            self._keep = [mesh, out]
+            res.update(vertices=out["vertices"], normals=out.get("normals"), totals=totals)
+            return res
+        assert out is None, "out: device tensors go with a mesh of tensors"
+        res["indices"] = idx
+        if res["colors"] is not None:
+            res["colors"] = np.ascontiguousarray(res["colors"], np.float32).reshape(-1, 3)[:V]
+        ov = np.empty((V, 3), np.float32)
+        on = np.empty((V, 3), np.float32) if normals else None
+        totals = self._adjacency_call(entry, V, T, pi, pv, *knobs, 0, ov.ctypes.data if V else None, on.ctypes.data if normals and V else None)
+        res.update(vertices=ov, normals=on, totals=totals)
+        return res
+
+    def SaveSmoothMeshPLY(self, filename, stride, iterations, min_triangles=1, lam=0.5, mu=-0.53, pin=capi.MESH_BOUNDARY | capi.MESH_NONMANIFOLD, binary=True):
+        """SaveCleanMeshPLY with the kept mesh smoothed (SmoothMesh): the indexed mesh of every resident chunk, filtered and smoothed
+        on the device, through the same writer"""
+        mesh = self.FilterMesh(self.IndexedMesh(stride, normals=False, colors=self.use_color), min_triangles)
+        return self._write_indexed_ply(filename, self.SmoothMesh(mesh, iterations, lam, mu, pin, normals=False), binary)
+
     def AlignTerms(self, depth, pose, camera, max_residual=0.0, out=None):
         """chisel_hip_align_terms: the normal equations of one Gauss-Newton step that aligns the depth image (numpy, or a torch CUDA
         tensor used in place) taken by `camera` at the guess `pose` (camera -> world) to the map.  -> (32,) float64: [0..20] the upper

@@ -53,6 +53,8 @@
 #include "kernels_indexed.h"
 #include "components_checks.h"
 #include "kernels_components.h"
+#include "adjacency_checks.h"
+#include "kernels_adjacency.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
 #include "kernels_stereo_prep.h"
@@ -464,6 +466,12 @@ struct chisel_hip_map {
         DeviceBuffer<unsigned long long> ctl;                          // [COMPONENTS_HOST_WORDS] the control words (CC_*)
         PinnedWords host, table_host;                                  // where the control words reach the host | [3 components] the table's rows
     } components_mem;
+    struct AdjacencyMemory {                                           // chisel_hip_mesh_adjacency / _mesh_vertex_normals / _smooth_mesh (host_adjacency.h), allocated on first use, grown on demand
+        DeviceBuffer<int> words;                                       // [adjacency_scratch_ints(V, T)] deg, cursor, neighbour counts, flags | both offset arrays | incidence items | neighbour rows | tile sums
+        DeviceBuffer<float> positions;                                 // [3 V] the second buffer of the smoothing passes' ping-pong
+        DeviceBuffer<unsigned long long> ctl;                          // [ADJACENCY_HOST_WORDS] the control words (AC_*)
+        PinnedWords host;                                              // where the control words reach the host
+    } adjacency_mem;
     // profiling
     bool profiling = false;
     std::vector<ProfEvent> prof_live;
@@ -3041,4 +3049,5 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 #include "host_coarse.h"
 #include "host_indexed.h"
 #include "host_components.h"
+#include "host_adjacency.h"
 #include "host_selftest.h"

@@ -809,6 +809,32 @@ class ChunkManager {  // ChunkManager.h:57-216 over one chisel_hip_map
         for (int64_t i = 0; i < 3 * found.kept_triangles; i++) out->indices.push_back((size_t)oix[(size_t)i]);
         if (totals) *totals = found;
     }
+    // Not in the reference: `in` (an indexed mesh) after `iterations` iterations of Taubin lambda | mu smoothing over the 1-ring
+    // (chisel_hip_smooth_mesh): a pass with lambda, then one with mu where mu != 0; vertices whose flags (CHISEL_HIP_MESH_BOUNDARY,
+    // _NONMANIFOLD, _ISOLATED) meet pinFlags, and those without a neighbour, stay where they are.  out: the smoothed vertices, the
+    // vertex normals of the smoothed positions (the area-weighted sum of the incident triangles' normals), indices and colours
+    // carried over; no grids.  `in` and `out` may be the same mesh.  totals: what the adjacency found and how many were pinned.
+    void SmoothMesh(const Mesh &in, int iterations, float lambda, float mu, int pinFlags, Mesh *out, chisel_hip_adjacency_totals *totals = nullptr) const {
+        const size_t n = in.vertices.size(), t = in.indices.size() / 3;
+        std::vector<float> ve(3 * n), ove(3 * n), ono(3 * n);
+        std::vector<int32_t> ix(3 * t);
+        for (size_t i = 0; i < n; i++)
+            for (int k = 0; k < 3; k++) ve[3 * i + k] = in.vertices[i](k);
+        for (size_t i = 0; i < 3 * t; i++) ix[i] = in.indices[i] > (size_t)INT32_MAX ? -1 : (int32_t)in.indices[i];  // (an id no vertex has: an invalid triangle)
+        chisel_hip_adjacency_totals found{};
+        hip_check(chisel_hip_smooth_mesh(map, (int64_t)n, (int64_t)t, ix.data(), ve.data(), iterations, lambda, mu, pinFlags, 0, n ? ove.data() : nullptr,
+                                         n ? ono.data() : nullptr, &found));
+        const std::vector<size_t> indices = in.indices;  // (`out` may be `in`)
+        const Vec3List colors = in.colors.size() == n ? in.colors : Vec3List();
+        out->Clear();
+        for (size_t i = 0; i < n; i++) {
+            out->vertices.push_back(Vec3(ove[3 * i], ove[3 * i + 1], ove[3 * i + 2]));
+            out->normals.push_back(Vec3(ono[3 * i], ono[3 * i + 1], ono[3 * i + 2]));
+        }
+        out->colors = colors;
+        out->indices = indices;
+        if (totals) *totals = found;
+    }
     bool HasMesh(const ChunkID &id) const {
         const int v[3] = {id(0), id(1), id(2)};
         int64_t nv = 0, ng = 0;
@@ -1099,6 +1125,27 @@ class Chisel {  // Chisel.h:38-230
         Mesh mesh;
         chunkManager.GenerateIndexedMesh(stride, &mesh);
         chunkManager.FilterMesh(mesh, minTriangles, false, &mesh);
+        const size_t n = mesh.vertices.size();
+        std::vector<float> v(3 * n), c(mesh.colors.size() == n ? 3 * n : 0);
+        std::vector<int64_t> idx(mesh.indices.begin(), mesh.indices.end());
+        for (size_t i = 0; i < n; i++)
+            for (int k = 0; k < 3; k++) {
+                v[3 * i + k] = mesh.vertices[i](k);
+                if (!c.empty()) c[3 * i + k] = mesh.colors[i](k);
+            }
+        const int rc = chisel_hip_write_mesh_ply(filename.c_str(), v.data(), c.empty() ? nullptr : c.data(), (int64_t)n, idx.data(), (int64_t)idx.size());
+        if (rc == CHISEL_HIP_ERR_IO) return false;
+        hip_check(rc);
+        return true;
+    }
+    // SaveCleanMeshToPLY with the kept mesh smoothed (ChunkManager::SmoothMesh; the defaults are Taubin's lambda | mu with the open
+    // rim and the non-manifold vertices pinned)
+    bool SaveSmoothMeshToPLY(const std::string &filename, int stride, int iterations, int64_t minTriangles = 1, float lambda = 0.5f, float mu = -0.53f,
+                             int pinFlags = CHISEL_HIP_MESH_BOUNDARY | CHISEL_HIP_MESH_NONMANIFOLD) {
+        Mesh mesh;
+        chunkManager.GenerateIndexedMesh(stride, &mesh);
+        chunkManager.FilterMesh(mesh, minTriangles, false, &mesh);
+        chunkManager.SmoothMesh(mesh, iterations, lambda, mu, pinFlags, &mesh);
         const size_t n = mesh.vertices.size();
         std::vector<float> v(3 * n), c(mesh.colors.size() == n ? 3 * n : 0);
         std::vector<int64_t> idx(mesh.indices.begin(), mesh.indices.end());

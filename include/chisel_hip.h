@@ -49,8 +49,8 @@ extern "C" {
  *      chisel_hip_align_solve, chisel_hip_align_depth, chisel_hip_merge_map, chisel_hip_deintegrate_depth, chisel_hip_deintegrate_batch,
  *      chisel_hip_distance_field, chisel_hip_gather_meshes,
  *      chisel_hip_gather_meshes_size, chisel_hip_save_ply_binary, chisel_hip_gather_chunks, chisel_hip_scatter_chunks, chisel_hip_coarse_mesh,
- *      chisel_hip_indexed_mesh, chisel_hip_mesh_components, chisel_hip_filter_mesh (no slot in the hipEvent profiler:
- *      CHISEL_HIP_NUM_KERNELS stays) */
+ *      chisel_hip_indexed_mesh, chisel_hip_mesh_components, chisel_hip_filter_mesh, chisel_hip_mesh_adjacency,
+ *      chisel_hip_mesh_vertex_normals, chisel_hip_smooth_mesh (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
 #define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -405,7 +405,8 @@ int chisel_hip_coarse_mesh(chisel_hip_map *map, const chisel_hip_coarse_request 
  * MeshCube's triangles in table order, the three ids in its push order (t + 2, t + 1, t) -- row for row the coarse mesh's.
  * normals (stage bit 0) are zeros overwritten by ComputeNormalsFromGradients (ChunkManager.cpp:609-626) where its look-up succeeds,
  * colors (stage bit 1) InterpolateColor's: bit for bit what chisel_hip_shade_vertices makes of the vertices with zero normals;
- * colours without bit 1 are zeros.  Face normals have no per-vertex meaning and are not offered. */
+ * colours without bit 1 are zeros.  Face normals have no per-vertex meaning and are not offered
+ * (the normals of the triangles around a vertex: chisel_hip_mesh_vertex_normals). */
 typedef struct { int64_t chunks, owners, cubes_meshed, vertices, triangles; } chisel_hip_indexed_totals;
 /* Only reads the map; everything runs on the map's stream, behind whatever is queued.  vertices, normals, colors: 3 floats per
  * vertex with room for capacity_vertices; indices: 3 int32 per triangle with room for capacity_triangles; normals, colors and
@@ -473,6 +474,62 @@ int chisel_hip_filter_mesh(chisel_hip_map *map, int64_t n_vertices, int64_t n_tr
                            float *out_vertices, int32_t *out_indices, float *out_normals, float *out_colors,
                            int32_t *vertex_map, int32_t *triangle_map, int on_device,
                            chisel_hip_components_totals *totals);
+
+/* ---- adjacency, vertex normals and smoothing of an indexed mesh (DESIGN.md 3.17 "Mesh adjacency") ----
+ * Not in the reference.  Input as for chisel_hip_mesh_components: n_vertices = V, n_triangles = T, indices: 3 int32 per triangle.  A
+ * triangle is VALID when all three ids lie in [0, V); the ids are tested before any is used as an address (garbage gives a wrong
+ * answer, never a fault); invalid triangles take part in nothing and are counted.
+ * INCIDENCE: row v is the ascending list of the valid triangles that name v, each once even when it names v twice; deg(v) is its
+ * length.  NEIGHBOURS: row v is the ascending list of the distinct ids u != v named by the triangles of v's incidence row; c(v, u)
+ * is the number of triangles of row v that name u.  FLAGS of v: bit 0 BOUNDARY: some u with c(v, u) == 1; bit 1 NONMANIFOLD: some u
+ * with c(v, u) > 2; bit 2 ISOLATED: deg(v) == 0.  Rows are stored CSR-wise: row v is items[offsets[v]] ... items[offsets[v + 1] - 1].
+ * VALENCE LIMIT: an index array with a deg above CHISEL_HIP_MESH_MAX_INCIDENT (marching cubes cannot exceed 20) is refused by all
+ * three entries with CHISEL_HIP_ERR_UNSUPPORTED, totals filled up to max_incident (the neighbour and flag totals then leave the rows
+ * above the limit out); this bounds every per-vertex loop.
+ * VERTEX NORMALS, every step fp32 and rounded on its own: acc = (+0, +0, +0); for each t of v's incidence row in ascending order, with
+ * its ids (i0, i1, i2) as stored, px = P[i1] - P[i0], py = P[i2] - P[i0], n = (px.y py.z - px.z py.y, px.z py.x - px.x py.z,
+ * px.x py.y - px.y py.x) (the coarse mesh's un-normalised face normal), acc = acc + n; len = sqrt((acc.x acc.x + acc.y acc.y) +
+ * acc.z acc.z); the normal is acc / len when len > 0, else (+0, +0, +0).
+ * SMOOTHING (Taubin): a vertex is PINNED when flags & pin_flags is non-zero or it has no neighbour.  One PASS with factor f copies a
+ * pinned vertex bit for bit and gives any other, per component and in ascending neighbour order, m = ((P[u0] + P[u1]) + P[u2]) + ...,
+ * m = m / (float)count, d = m - P[v], Q[v] = P[v] + f d (the product rounded, then the sum).  An iteration is a pass with lambda, then
+ * one with mu when mu != 0 (mu == 0: plain Laplacian smoothing); a pass reads only the positions the pass before it wrote; the
+ * adjacency is the input's; iterations == 0 copies the vertices.  Integers and floats alike are a pure function of the arguments:
+ * no float is added atomically, every sum has one order. */
+#define CHISEL_HIP_MESH_MAX_INCIDENT 32
+enum { CHISEL_HIP_MESH_BOUNDARY = 1, CHISEL_HIP_MESH_NONMANIFOLD = 2, CHISEL_HIP_MESH_ISOLATED = 4 };
+typedef struct {
+    int64_t vertices, triangles, invalid_triangles, incidences, neighbors, max_incident, max_neighbors;
+    int64_t boundary_vertices, nonmanifold_vertices, isolated_vertices, pinned_vertices /* chisel_hip_smooth_mesh; else 0 */, reserved;
+} chisel_hip_adjacency_totals;
+/* The frame of chisel_hip_mesh_components: the map lends its device, its stream and its scratch (a group is refused with
+ * CHISEL_HIP_ERR_UNSUPPORTED), everything is queued on the map's stream behind what is queued, on_device says where ALL array arguments
+ * live, totals is host memory, host arrays are staged through owned device buffers and are complete on return.  The host waits once,
+ * for the totals: the whole structure is built in the map's scratch in front of that wait, so also the compact neighbour arrays cost
+ * no second one; with on_device nothing is waited for behind the launches that write the arrays.  All outputs are optional:
+ * tri_offsets and nbr_offsets (V + 1), tri_items (room for capacity_incidence ids), nbr_items (room for capacity_neighbors),
+ * vertex_flags (V); with none of them it is the size query: totals is filled and nothing else is written.  A capacity below its total,
+ * of an array that is asked for, is refused with totals filled.  3 T bounds the incidences and 6 T the neighbours, so a call with
+ * those capacities never needs a retry.  V = 0 or T = 0 succeeds: every vertex is isolated.  The scratch (6 ints per vertex, 9 per
+ * triangle, tile sums) is kept in the map, grown on demand and freed with it.
+ * Refused with nothing written: what chisel_hip_mesh_components refuses about sizes and indices; CHISEL_HIP_ERR_UNSUPPORTED for 6 T
+ * above 2^31 - 1 and for the valence limit; negative capacities; the size query without totals. */
+int chisel_hip_mesh_adjacency(chisel_hip_map *map, int64_t n_vertices, int64_t n_triangles, const int32_t *indices, int on_device,
+                              int32_t *tri_offsets, int64_t capacity_incidence, int32_t *tri_items,
+                              int32_t *nbr_offsets, int64_t capacity_neighbors, int32_t *nbr_items,
+                              int32_t *vertex_flags, chisel_hip_adjacency_totals *totals);
+/* normals[V]: 3 floats per vertex by the rule above, from vertices[V] (3 floats each).  Without normals it is the size query.  One
+ * host wait, for the totals and the valence verdict.  Refused in addition: null vertices where normals are asked for (V > 0). */
+int chisel_hip_mesh_vertex_normals(chisel_hip_map *map, int64_t n_vertices, int64_t n_triangles, const int32_t *indices,
+                                   const float *vertices, int on_device, float *normals, chisel_hip_adjacency_totals *totals);
+/* out_vertices[V]: the positions after `iterations` iterations; out_normals[V] (optional): the vertex normals of those positions.
+ * pin_flags: a mask over the FLAGS bits; totals.pinned_vertices counts the pinned.  Without out_vertices it is the size query.  One
+ * host wait.  out_vertices must not overlap vertices.  A second position buffer (3 V floats) is kept in the map.
+ * Refused in addition: negative iterations, a lambda or mu that is not finite, pin_flags outside 0 .. 7, out_normals without
+ * out_vertices, null vertices where out_vertices is asked for (V > 0), out_vertices overlapping vertices. */
+int chisel_hip_smooth_mesh(chisel_hip_map *map, int64_t n_vertices, int64_t n_triangles, const int32_t *indices, const float *vertices,
+                           int iterations, float lambda, float mu, int pin_flags, int on_device,
+                           float *out_vertices, float *out_normals, chisel_hip_adjacency_totals *totals);
 
 /* ---- meshing a sharded map (SURVEY.md 8e "meshing across shards") -------------------------------------------------
  * A chunk's mesh reads its 26 neighbours (cube corners: ChunkManager.cpp:316-357; gradient normals and colours of border
