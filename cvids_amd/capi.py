@@ -107,6 +107,22 @@ class DistanceWindow(C.Structure):
 DISTANCE_MAX_RADIUS = 64  # chisel_hip_distance_field's largest radius, voxels
 
 
+class FrontierWindow(C.Structure):
+    """chisel_hip_frontier_window (include/chisel_hip.h): the window and the knobs of chisel_hip_frontiers, 40 bytes"""
+    _fields_ = [("origin", C.c_int * 3), ("dims", C.c_int * 3), ("min_unknown_faces", C.c_int), ("connectivity", C.c_int), ("min_voxels", C.c_int),
+                ("surface_offset", C.c_float)]
+
+
+class FrontierTotals(C.Structure):
+    """chisel_hip_frontier_totals (include/chisel_hip.h): what chisel_hip_frontiers found and kept, 64 bytes"""
+    _fields_ = [(n, C.c_int64) for n in ("unknown", "free", "occupied", "frontier", "clusters", "largest_voxels", "kept_clusters", "kept_voxels")]
+
+
+assert C.sizeof(FrontierWindow) == 40 and C.sizeof(FrontierTotals) == 64
+FRONTIER_MAX_VOXELS = 1 << 26  # chisel_hip_frontiers' largest window, voxels
+FRONTIER_TABLE_COLUMNS = ("root", "voxels", "sum_x", "sum_y", "sum_z", "min_x", "min_y", "min_z", "max_x", "max_y", "max_z", "unknown_faces")
+
+
 class MeshRequest(C.Structure):
     """chisel_hip_mesh_request (include/chisel_hip.h): the selection and the marker colours of chisel_hip_gather_meshes, 56 bytes"""
     _fields_ = [("ids_xyz", C.POINTER(C.c_int)), ("n_ids", C.c_int64), ("marker_colors", C.c_int), ("light0", C.c_float * 3),
@@ -198,6 +214,7 @@ EXPORTS = [
     "chisel_hip_gather_chunks", "chisel_hip_scatter_chunks", "chisel_hip_coarse_mesh", "chisel_hip_indexed_mesh",
     "chisel_hip_mesh_components", "chisel_hip_filter_mesh",
     "chisel_hip_mesh_adjacency", "chisel_hip_mesh_vertex_normals", "chisel_hip_smooth_mesh",
+    "chisel_hip_frontiers",
 ]
 # the device self-tests and debug read-outs include/chisel_hip_selftest.h declares
 SELFTEST_EXPORTS = [
@@ -354,6 +371,7 @@ def load_library():
                         ("chisel_hip_deintegrate_depth", [vp, C.POINTER(DepthFrame), C.c_int, C.POINTER(DeintegrateStats), i32p, C.c_int]),
                         ("chisel_hip_deintegrate_batch", [vp, C.c_int, C.POINTER(DepthFrame), C.c_int, C.POINTER(DeintegrateStats), i32p, C.c_int]),
                         ("chisel_hip_distance_field", [vp, C.POINTER(DistanceWindow), vp, vp, vp, C.c_int]),
+                        ("chisel_hip_frontiers", [vp, C.POINTER(FrontierWindow), vp, vp, C.c_int64, vp, C.c_int64, i64p, C.c_int, C.POINTER(FrontierTotals)]),
                         ("chisel_hip_gather_meshes", [vp, C.POINTER(MeshRequest), C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.c_int, i64p, i32p,
                                                       C.POINTER(MeshTotals)]),
                         ("chisel_hip_gather_meshes_size", [vp, C.POINTER(MeshRequest), C.POINTER(MeshTotals)]),

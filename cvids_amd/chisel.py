@@ -642,6 +642,83 @@ class Chisel:
         check(self.L.chisel_hip_distance_field(self.h, C.byref(w), *[ptr(res[name]) for name, _ in self._DISTANCE_OUTPUTS], 0))
         return res
 
+    def _frontier_window(self, origin, dims, min_unknown_faces, connectivity, min_voxels, surface_offset):
+        w = capi.FrontierWindow()
+        w.origin[:] = [int(v) for v in origin]
+        w.dims[:] = [int(v) for v in dims]
+        w.min_unknown_faces, w.connectivity, w.surface_offset = int(min_unknown_faces), int(connectivity), float(surface_offset)
+        w.min_voxels = max(min(int(min_voxels), (1 << 31) - 1), -1)  # (no cluster has 2^31 - 1 voxels: none is kept)
+        return w
+
+    def _frontier_call(self, w, state, label, capacity_voxels, voxels, capacity_clusters, table, on_device):
+        """chisel_hip_frontiers -> the totals; a refused capacity raises with the totals in the error's `totals`"""
+        totals = capi.FrontierTotals()
+        rc = self.L.chisel_hip_frontiers(self.h, C.byref(w), state, label, int(capacity_voxels), voxels, int(capacity_clusters),
+                                         self._table_ptr(table, C.c_int64), int(on_device), C.byref(totals))
+        if rc:
+            try:
+                check(rc)
+            except capi.ChiselHipError as e:
+                e.totals = self._totals_dict(totals)
+                raise
+        return self._totals_dict(totals)
+
+    def FrontiersSize(self, origin, dims, min_unknown_faces=1, connectivity=26, min_voxels=1, surface_offset=0.0):
+        """chisel_hip_frontiers as the size query: the totals of Frontiers -- {"unknown", "free", "occupied", "frontier", "clusters",
+        "largest_voxels", "kept_clusters", "kept_voxels"} -- with nothing else written"""
+        w = self._frontier_window(origin, dims, min_unknown_faces, connectivity, min_voxels, surface_offset)
+        return self._frontier_call(w, None, None, 0, None, 0, None, 0)
+
+    def FrontierCentres(self, origin, table):
+        """the centres of the clusters of a Frontiers table, (K, 3) float64 metres: ((origin + sum / voxels) + 0.5) * resolution"""
+        table = np.asarray(table, np.int64).reshape(-1, 12)
+        res = float(np.float32(self.voxel_resolution))
+        mean = table[:, 2:5].astype(np.float64) / np.maximum(table[:, 1:2], 1).astype(np.float64)
+        return ((np.asarray(origin, np.float64)[None, :] + mean) + 0.5) * res
+
+    def Frontiers(self, origin, dims, min_unknown_faces=1, connectivity=26, min_voxels=1, surface_offset=0.0, state=False, label=True, voxels=True, out=None):
+        """chisel_hip_frontiers: over the window of dims = (nx, ny, nz) voxels whose first voxel has the global index
+        `origin`, the FRONTIER voxels -- free, with at least min_unknown_faces (1 ... 6) of the six face neighbours unknown; states as
+        DistanceField's, neighbours read from the map beyond the window's rim too --, their clusters under `connectivity` 6, 18 or 26
+        inside the window, numbered by ascending smallest linear index, and of those the ones with at least min_voxels voxels.
+        -> {"state": uint8 (nz, ny, nx), "label": int32 (nz, ny, nx) -- the kept cluster's number, -1 not a frontier voxel, -2 a
+        frontier voxel of a dropped cluster --, "voxels": int32 (kept voxels, 4) -- x, y, z (window-relative), cluster, in ascending
+        linear index --, None for what was not asked for; "table": int64 (K, 12) -- capi.FRONTIER_TABLE_COLUMNS: root, voxels, the
+        sums, minima and maxima of x, y, z, the sum of unknown faces --, "centres": float64 (K, 3) metres, "totals"}.
+        `out`: a dict of contiguous torch CUDA tensors "state", "label" (of that shape) and / or "voxels" ((rows, 4) int32 with at
+        least kept_voxels rows): exactly those are filled in place on the map's stream; it is returned with "table", "centres" and
+        "totals" (host) added.  The sizes come from a size query in front of the call; the map is only read."""
+        w = self._frontier_window(origin, dims, min_unknown_faces, connectivity, min_voxels, surface_offset)
+        size = self._frontier_call(w, None, None, 0, None, 0, None, 0)
+        K, kept = size["kept_clusters"], size["kept_voxels"]
+        table = np.zeros((K, 12), np.int64)
+        shape = (int(dims[2]), int(dims[1]), int(dims[0]))
+        if out is not None:
+            import torch
+            unknown = set(out) - {"state", "label", "voxels"}
+            assert not unknown, "out: unknown outputs %s" % sorted(unknown)
+            ptrs = []
+            for name, want in (("state", torch.uint8), ("label", torch.int32)):
+                t = out.get(name)
+                assert t is None or (t.is_cuda and t.dtype == want and t.is_contiguous() and tuple(t.shape) == shape), \
+                    "out[%r]: a contiguous %s CUDA tensor of shape %s" % (name, want, shape)
+                ptrs.append(t.data_ptr() if t is not None else None)
+            rows = out.get("voxels")
+            cap = int(rows.shape[0]) if rows is not None else 0
+            self._device_rows(rows, "out['voxels']", "int32", 4, 0)  # (kind and shape; the rows are the capacity)
+            list_ptr = rows.data_ptr() if rows is not None and rows.numel() else None
+            totals = self._frontier_call(w, ptrs[0], ptrs[1], cap if list_ptr else 0, list_ptr, K, table, 1)
+            self._keep = [out]
+            res = dict(out)
+        else:
+            res = {"state": np.empty(shape, np.uint8) if state else None, "label": np.empty(shape, np.int32) if label else None,
+                   "voxels": np.empty((kept, 4), np.int32) if voxels else None}
+            ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+            totals = self._frontier_call(w, ptr(res["state"]), ptr(res["label"]), kept if voxels else 0, ptr(res["voxels"]), K, table, 0)
+        assert totals == size, "the map changed between the size query and the call"
+        res.update(table=table, centres=self.FrontierCentres(origin, table), totals=totals)
+        return res
+
     _GATHER_OUTPUTS = (("vertices", 3), ("normals", 3), ("colors", 3), ("rgba", 4), ("grids", 3))
     # ChiselServer's marker lights (chisel_ros/src/ChiselServer.cpp:652-655, :657-658): lightDir normalised twice, lightDir1 as it stands
     MARKER_LIGHTS = {"light0": marker_light_dir(), "light1": (-0.5, 0.2, 0.2), "diffuse": 0.5, "ambient": 0.2}

@@ -55,6 +55,8 @@
 #include "kernels_components.h"
 #include "adjacency_checks.h"
 #include "kernels_adjacency.h"
+#include "frontier_checks.h"
+#include "kernels_frontier.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
 #include "kernels_stereo_prep.h"
@@ -484,6 +486,13 @@ struct chisel_hip_map {
         DeviceBuffer<float> table;                                     // [64^2 + 1] metres by squared voxel distance ...
         PinnedBuffer<float> table_host;                                // ... as the host computed it (written once, before its one upload)
     } distance_mem;
+    struct FrontierMemory {                                            // chisel_hip_frontiers (host_frontier.h), allocated on first use, grown on demand
+        DeviceBuffer<unsigned long long> planes;                       // [FrontierPlan::plane_words] free and unknown over the widened window | frontier, root, kept, kept root over the window | prefix | tile sums
+        DeviceBuffer<int> ints;                                        // [3 voxels] parent, root_of, count per root
+        DeviceBuffer<unsigned long long> ctl;                          // [FRONTIER_HOST_WORDS] the control words (FC_*)
+        DeviceBuffer<long long> acc;                                   // [12 kept clusters] the table's accumulator
+        PinnedWords host, table_host;                                  // where the control words reach the host | [12 kept clusters] the table's rows
+    } frontier_mem;
 };
 
 namespace {
@@ -3050,4 +3059,5 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 #include "host_indexed.h"
 #include "host_components.h"
 #include "host_adjacency.h"
+#include "host_frontier.h"
 #include "host_selftest.h"

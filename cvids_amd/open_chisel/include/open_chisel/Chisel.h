@@ -1257,6 +1257,46 @@ class Chisel {  // Chisel.h:38-230
         hip_check(chisel_hip_distance_field(map, &w, state ? state->data() : nullptr, dist2 ? dist2->data() : nullptr,
                                             distance ? distance->data() : nullptr, 0));
     }
+    // Not in the reference: where the observed space ends (chisel_hip_frontiers).  Over the window of DistanceField, the
+    // FRONTIER voxels -- free, with at least minUnknownFaces (1 ... 6) of the six face neighbours unknown --, their clusters under
+    // `connectivity` 6, 18 or 26 numbered by ascending smallest linear index, and of those the ones with at least minVoxels voxels.
+    // A null vector is not asked for; the others are resized: state and label per voxel (label: the kept cluster's number, -1 not a
+    // frontier voxel, -2 a frontier voxel of a dropped cluster), voxels: 4 ints per kept frontier voxel (x, y, z window-relative,
+    // cluster) in ascending linear index, table: 12 int64 per kept cluster (root, voxels, sums, minima and maxima of x, y, z, the sum
+    // of unknown faces), centres: 3 doubles per kept cluster, metres.  The sizes come from a size query in front of the call.  The map
+    // is only read.  -> the totals
+    chisel_hip_frontier_totals Frontiers(const Eigen::Vector3i &origin, const Eigen::Vector3i &dims, int minUnknownFaces, int connectivity, int minVoxels,
+                                         float surfaceOffset, std::vector<uint8_t> *state, std::vector<int32_t> *label, std::vector<int32_t> *voxels,
+                                         std::vector<int64_t> *table, std::vector<double> *centres = nullptr) const {
+        chisel_hip_frontier_window w;
+        for (int a = 0; a < 3; a++) {
+            w.origin[a] = origin(a);
+            w.dims[a] = dims(a);
+        }
+        w.min_unknown_faces = minUnknownFaces;
+        w.connectivity = connectivity;
+        w.min_voxels = minVoxels;
+        w.surface_offset = surfaceOffset;
+        chisel_hip_frontier_totals size, totals;
+        hip_check(chisel_hip_frontiers(map, &w, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, &size));  // (refuses what cannot be sized)
+        const size_t n = (size_t)dims(0) * dims(1) * dims(2);
+        std::vector<int64_t> rows((size_t)size.kept_clusters * 12);
+        if (state) state->resize(n);
+        if (label) label->resize(n);
+        if (voxels) voxels->resize((size_t)size.kept_voxels * 4);
+        const bool list = voxels && size.kept_voxels > 0, tab = (table || centres) && size.kept_clusters > 0;
+        hip_check(chisel_hip_frontiers(map, &w, state ? state->data() : nullptr, label ? label->data() : nullptr, list ? size.kept_voxels : 0,
+                                       list ? voxels->data() : nullptr, tab ? size.kept_clusters : 0, tab ? rows.data() : nullptr, 0, &totals));
+        if (centres) {
+            centres->resize((size_t)size.kept_clusters * 3);
+            const double res = (double)chunkManager.GetResolution();
+            for (int64_t k = 0; k < size.kept_clusters; k++)
+                for (int a = 0; a < 3; a++)
+                    (*centres)[3 * k + a] = (((double)origin(a) + (double)rows[12 * k + 2 + a] / (double)rows[12 * k + 1]) + 0.5) * res;
+        }
+        if (table) table->swap(rows);
+        return totals;
+    }
     chisel_hip_map *HipMap() const { return map; }
 
   protected:

@@ -50,7 +50,7 @@ extern "C" {
  *      chisel_hip_distance_field, chisel_hip_gather_meshes,
  *      chisel_hip_gather_meshes_size, chisel_hip_save_ply_binary, chisel_hip_gather_chunks, chisel_hip_scatter_chunks, chisel_hip_coarse_mesh,
  *      chisel_hip_indexed_mesh, chisel_hip_mesh_components, chisel_hip_filter_mesh, chisel_hip_mesh_adjacency,
- *      chisel_hip_mesh_vertex_normals, chisel_hip_smooth_mesh (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
+ *      chisel_hip_mesh_vertex_normals, chisel_hip_smooth_mesh, chisel_hip_frontiers (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
 #define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -894,6 +894,54 @@ typedef struct {
  * CHISEL_HIP_ERR_UNSUPPORTED: a widened window of more than 2^30 voxels.  DESIGN.md 3.11 "Distance field" has the definition. */
 int chisel_hip_distance_field(chisel_hip_map *map, const chisel_hip_distance_window *window, uint8_t *state, int32_t *dist2, float *distance,
                               int on_device);
+/* ---- frontier voxels of a window, clustered and tabulated (DESIGN.md 3.18 "Frontiers") ----
+ * Not in the reference: where the observed space ends -- what an exploration planner, a next-best-view step or a task allocator asks
+ * first.  The window is chisel_hip_distance_window's: origin (global voxel index per axis, chunk_id * N + voxel coordinate) and
+ * dims = (nx, ny, nz); element (x, y, z) of a per-voxel output sits at (z ny + y) nx + x, the voxel's LINEAR INDEX.  The STATE of a
+ * voxel (0 unknown, 1 free, 2 occupied) is chisel_hip_distance_field's, bit for bit: the same residency rule, look-up guard and weight
+ * rule, one fp32 compare sdf < surface_offset.  A voxel of the window is a FRONTIER voxel when it is free and at least
+ * min_unknown_faces (1 ... 6) of its six face neighbours are unknown; the neighbours are voxels of the MAP (read over the window
+ * widened by one voxel on every side), and unknown_faces(v) is that count.  The CLUSTERS are the connected components of the frontier
+ * voxels of the window under connectivity 6, 18 or 26 (offsets with 1, <= 2, <= 3 non-zero coordinates, each -1 ... 1); voxels outside
+ * the window join nothing.  A cluster's ROOT is its smallest linear index; clusters are numbered by ascending root; a cluster is KEPT
+ * when it has at least min_voxels (>= 1) voxels, and the kept clusters are renumbered 0 ... K - 1 in the same order. */
+typedef struct {
+    int origin[3];
+    int dims[3];
+    int min_unknown_faces;     /* 1 ... 6 */
+    int connectivity;          /* 6, 18 or 26 */
+    int min_voxels;            /* >= 1: clusters with fewer voxels are dropped */
+    float surface_offset;      /* metres: a voxel is occupied when it is observed with sdf < surface_offset */
+} chisel_hip_frontier_window;   /* 40 bytes */
+typedef struct { int64_t unknown, free, occupied, frontier, clusters, largest_voxels, kept_clusters, kept_voxels; } chisel_hip_frontier_totals;
+/* Outputs, each optional:
+ *   state (uint8 per voxel)   the distance field's, bit for bit
+ *   label (int32 per voxel)   the kept cluster's number; -1 for a voxel that is not a frontier voxel; -2 for a frontier voxel of a
+ *                             cluster that was dropped
+ *   voxels (4 int32 a row, room for capacity_voxels rows)   (x, y, z, cluster) of every kept frontier voxel, window-relative, in
+ *                             ascending linear index
+ *   cluster_table (12 int64 a row, room for capacity_clusters rows, HOST memory whatever on_device says)   per kept cluster: root,
+ *                             voxels, sum x, sum y, sum z (window-relative), min x, y, z, max x, y, z, sum of unknown_faces.  The
+ *                             centre in metres is the caller's arithmetic: ((origin + sum / voxels) + 0.5) * resolution
+ *   totals (required, host)   unknown, free and occupied voxels of the window, frontier voxels, clusters, the largest cluster's
+ *                             voxels, kept clusters, kept voxels
+ * on_device says where state, label and voxels live.  Everything is queued on the map's stream behind what is queued; the host waits
+ * once, for the totals (pinned memory); with on_device nothing is waited for behind the launches that write the arrays -- except for
+ * cluster_table, whose rows are written to pinned memory behind that wait and waited for.  Host arrays are staged, copied out once
+ * with exactly their live rows, and complete on return.  With no array asked for (a list or a table with capacity 0 is not asked
+ * for) the call is the size query: totals is filled and nothing else is written.  A capacity below its total (kept_voxels,
+ * kept_clusters) is refused with CHISEL_HIP_ERR_INVALID, totals filled and nothing else written, so that the caller can retry.  The
+ * map is only read; the scratch (two bits per voxel of the widened window, four bits, 12 bytes and an eighth of a byte per voxel of
+ * the window; 96 bytes per kept cluster when the table is asked for) is kept in the map, grown on demand and freed with it.  No float
+ * is computed after the one compare: the answer is a pure function of the map and the window.
+ * Refused with nothing written, in this order: CHISEL_HIP_ERR_UNSUPPORTED for a group, CHISEL_HIP_ERR_INVALID for a null map,
+ * CHISEL_HIP_ERR_UNSUPPORTED for one shard of several; then CHISEL_HIP_ERR_INVALID for a null window, null totals, a dimension < 1,
+ * min_unknown_faces outside 1 ... 6, a connectivity other than 6 / 18 / 26, min_voxels < 1, a NaN surface_offset, a negative
+ * capacity, a capacity without its array, a coordinate of the widened window beyond +-2^30; then CHISEL_HIP_ERR_UNSUPPORTED for a
+ * window of more than 2^26 voxels. */
+int chisel_hip_frontiers(chisel_hip_map *map, const chisel_hip_frontier_window *window, uint8_t *state, int32_t *label,
+                         int64_t capacity_voxels, int32_t *voxels, int64_t capacity_clusters, int64_t *cluster_table, int on_device,
+                         chisel_hip_frontier_totals *totals);
 /* Not in the reference: the normal equations of one Gauss-Newton step that aligns a depth frame to the map (point-to-surface against the
  * TSDF; DESIGN.md "Aligning a frame to the map" has the definition to the bit).  frame->pose is the guess, camera -> world.  Pixel i
  * with depth z is VALID when z is finite and near <= z <= far; its point p = o + z d lies on chisel_hip_render_view's ray of that pixel;
