@@ -31,6 +31,7 @@
 #include "chisel_device.h"
 #include "host_buffer.h"
 #include "host_frustum.h"
+#include "kernels_workgroup.h"
 #include "kernels_cull.h"
 #include "kernels_integrate.h"
 #include "kernels_map.h"
@@ -465,14 +466,13 @@ struct chisel_hip_map {
     } indexed_mem;
     struct ComponentsMemory {                                          // chisel_hip_mesh_components / _filter_mesh (host_components.h), allocated on first use, grown on demand
         DeviceBuffer<int> words;                                       // [6 V + T + tiles] parent, root_of, both counts per root, number and kept-vertex prefix | kept-triangle prefix | tile sums
-        DeviceBuffer<unsigned long long> ctl;                          // [COMPONENTS_HOST_WORDS] the control words (CC_*)
-        PinnedWords host, table_host;                                  // where the control words reach the host | [3 components] the table's rows
+        ControlWords ctl;                                              // [COMPONENTS_HOST_WORDS] the control words (CC_*)
+        PinnedWords table_host;                                        // [3 components] the table's rows
     } components_mem;
     struct AdjacencyMemory {                                           // chisel_hip_mesh_adjacency / _mesh_vertex_normals / _smooth_mesh (host_adjacency.h), allocated on first use, grown on demand
         DeviceBuffer<int> words;                                       // [adjacency_scratch_ints(V, T)] deg, cursor, neighbour counts, flags | both offset arrays | incidence items | neighbour rows | tile sums
         DeviceBuffer<float> positions;                                 // [3 V] the second buffer of the smoothing passes' ping-pong
-        DeviceBuffer<unsigned long long> ctl;                          // [ADJACENCY_HOST_WORDS] the control words (AC_*)
-        PinnedWords host;                                              // where the control words reach the host
+        ControlWords ctl;                                              // [ADJACENCY_HOST_WORDS] the control words (AC_*)
     } adjacency_mem;
     // profiling
     bool profiling = false;
@@ -489,9 +489,9 @@ struct chisel_hip_map {
     struct FrontierMemory {                                            // chisel_hip_frontiers (host_frontier.h), allocated on first use, grown on demand
         DeviceBuffer<unsigned long long> planes;                       // [FrontierPlan::plane_words] free and unknown over the widened window | frontier, root, kept, kept root over the window | prefix | tile sums
         DeviceBuffer<int> ints;                                        // [3 voxels] parent, root_of, count per root
-        DeviceBuffer<unsigned long long> ctl;                          // [FRONTIER_HOST_WORDS] the control words (FC_*)
+        ControlWords ctl;                                              // [FRONTIER_HOST_WORDS] the control words (FC_*)
         DeviceBuffer<long long> acc;                                   // [12 kept clusters] the table's accumulator
-        PinnedWords host, table_host;                                  // where the control words reach the host | [12 kept clusters] the table's rows
+        PinnedWords table_host;                                        // [12 kept clusters] the table's rows
     } frontier_mem;
 };
 
@@ -3047,6 +3047,7 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 
 }  // extern "C"
 
+#include "host_totals.h"
 #include "host_render.h"
 #include "host_query.h"
 #include "host_align.h"

@@ -1,14 +1,8 @@
 // host_adjacency.h -- chisel_hip_mesh_adjacency, chisel_hip_mesh_vertex_normals and chisel_hip_smooth_mesh (included by
 // chisel_hip.hip; the kernels: kernels_adjacency.h; the refusals, the valence limit and the scratch arithmetic: adjacency_checks.h; the
-// definition: DESIGN.md 3.17).  The frame of host_components.h around another subject: the map is neither read nor written -- it lends
-// its device, its stream and its scratch --, everything is queued on the map's stream behind what was queued before, and a group handle
-// is refused.  All three entries read top to bottom: refusals, the inputs (host arrays are staged through one owned device buffer), the
-// scratch, build() -- count, scan, fill, rows, scan, report: the whole structure, in the map's scratch --, THE WAIT for the totals
-// (pinned memory), the valence limit and the capacities, then what writes the caller's arrays: with device pointers nothing is waited
-// for behind those launches; host arrays are staged through a second owned buffer, copied out once, and are complete on return.
-// Because the rows are built in the scratch in front of the wait, the compact neighbour arrays need no wait of their own.
-//
-// Scratch the map owns (chisel_hip_map::adjacency_mem), grown on demand, freed with the map.
+// definition: DESIGN.md 3.17).  The frame of host_totals.h; the map is neither read nor written.  In front of the wait: build() -- count, scan,
+// fill, rows, scan: the whole structure, in the map's scratch, so that the compact neighbour arrays need no wait of their own.
+// Behind it the valence limit stands in front of the capacities.  Scratch: chisel_hip_map::adjacency_mem.
 #pragma once
 
 namespace {
@@ -21,16 +15,12 @@ struct Totals {
 
 inline unsigned tiles(int64_t n) { return (unsigned)components_tiles(n); }
 
-// the scratch of a call of V vertices and T triangles, carved out of one buffer of ints (doubled when it grows), and the view on it
+// the scratch of a call of V vertices and T triangles, carved out of one buffer of ints, and the view on it
 int ensure_memory(chisel_hip_map *m, int64_t V, int64_t T, AdjacencyView &X) {
     chisel_hip_map::AdjacencyMemory &A = m->adjacency_mem;
-    const size_t v = (size_t)V, t = (size_t)T, need = (size_t)adjacency_scratch_ints(V, T);
-    if (need > A.words.size()) {
-        const int rc = grow_buffer(A.words, std::max<size_t>(std::max<size_t>(need, 2 * A.words.size()), 4096), m->stream);  // (waits for the stream before it replaces the buffer)
-        if (rc) return rc;
-    }
-    if (!A.ctl) HIP_TRY(A.ctl.alloc(ADJACENCY_HOST_WORDS));
-    HIP_TRY(A.host.ensure(ADJACENCY_HOST_WORDS, m->stream));
+    const size_t v = (size_t)V, t = (size_t)T;
+    if (int rc = grow_ints(m, A.words, (size_t)adjacency_scratch_ints(V, T))) return rc;
+    if (int rc = A.ctl.prepare(m, ADJACENCY_HOST_WORDS)) return rc;
     int *p = A.words.get();
     X.deg = p;
     X.cursor = p + v;
@@ -42,7 +32,7 @@ int ensure_memory(chisel_hip_map *m, int64_t V, int64_t T, AdjacencyView &X) {
     X.nbr_rows = p + 6 * v + 2 + 3 * t;
     X.sums = p + 6 * v + 2 + 9 * t;
     X.maxes = X.sums + (size_t)adjacency_scan_tiles(V);
-    X.ctl = A.ctl.get();
+    X.ctl = A.ctl.dev();
     return CHISEL_HIP_OK;
 }
 
@@ -59,7 +49,7 @@ void scan(chisel_hip_map *m, const AdjacencyView &X, const int *values, int n, i
 int build(chisel_hip_map *m, AdjacencyView &X, Totals &T) {
     chisel_hip_map::AdjacencyMemory &A = m->adjacency_mem;
     const dim3 per_triangle(tiles(X.T)), block(COMPONENTS_TILE);
-    HIP_TRY(hipMemsetAsync(X.ctl, 0, ADJACENCY_HOST_WORDS * sizeof(unsigned long long), m->stream));
+    HIP_TRY(A.ctl.zero(m->stream));
     if (X.V) HIP_TRY(hipMemsetAsync(X.deg, 0, 2 * (size_t)X.V * sizeof(int), m->stream));  // deg and cursor
     if (X.T) hipLaunchKernelGGL(adjacency_count_kernel, per_triangle, block, 0, m->stream, X);
     scan(m, X, X.deg, X.V, X.tri_off, AC_INCIDENCES, AC_MAX_INCIDENT);
@@ -67,12 +57,8 @@ int build(chisel_hip_map *m, AdjacencyView &X, Totals &T) {
     if (X.V)
         hipLaunchKernelGGL(adjacency_rows_kernel, dim3((unsigned)((X.V + ADJACENCY_ROWS_THREADS - 1) / ADJACENCY_ROWS_THREADS)), dim3(ADJACENCY_ROWS_THREADS), 0, m->stream, X);
     scan(m, X, X.nbr_count, X.V, X.nbr_off, AC_NEIGHBORS, AC_MAX_NEIGHBORS);
-    hipLaunchKernelGGL(adjacency_report_kernel, dim3(1), dim3(64), 0, m->stream, (const unsigned long long *)X.ctl, A.host.dev());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(m->stream));  // THE WAIT
-    note_stream_idle(m);
-    std::atomic_thread_fence(std::memory_order_acquire);
-    volatile long long *w = A.host.get();
+    volatile long long *w;
+    if (int rc = A.ctl.report_and_wait(m, &w)) return rc;
     T.vertices = X.V;
     T.triangles = X.T;
     T.invalid_triangles = w[AC_INVALID];
@@ -106,25 +92,21 @@ struct Call {
         X.count_pinned = count_pinned ? 1 : 0;
         int rc = ensure_memory(m, V, T_, X);
         if (rc) return rc;
-        rc = wait_for_input(m, m->stream);  // chisel_hip_wait_event / _order_map_after_stream: the arrays are ready behind it
-        if (rc) return rc;
+        if ((rc = wait_for_input(m, m->stream))) return rc;  // chisel_hip_wait_event / _order_map_after_stream: the arrays are ready behind it
         d_indices = T_ ? indices : nullptr;
         d_vertices = V ? vertices : nullptr;
         in.in(d_indices, (size_t)T_ * 3 * sizeof(int32_t));
         in.in(d_vertices, (size_t)V * 3 * sizeof(float));
         HIP_TRY(in.begin());
         X.indices = d_indices;
-        rc = build(m, X, T);
-        if (rc) return rc;
+        if ((rc = build(m, X, T))) return rc;
         if (const char *why = adjacency_valence_refusal(T.max_incident)) {
             copy_totals(T, totals);  // (max_incident says how large it was)
-            return fail(CHISEL_HIP_ERR_UNSUPPORTED, std::string(name) + ": " + why);
+            return refusal(name, why, true);
         }
         return CHISEL_HIP_OK;
     }
 };
-
-int refusal(const char *name, const char *why, bool unsupported) { return fail(unsupported ? CHISEL_HIP_ERR_UNSUPPORTED : CHISEL_HIP_ERR_INVALID, std::string(name) + ": " + why); }
 
 void launch_normals(chisel_hip_map *m, const AdjacencyView &X, const float *P, float *normals) {
     hipLaunchKernelGGL(mesh_vertex_normals_kernel, dim3(tiles(X.V)), dim3(COMPONENTS_TILE), 0, m->stream, X, P, normals);
@@ -132,15 +114,14 @@ void launch_normals(chisel_hip_map *m, const AdjacencyView &X, const float *P, f
 
 int run_adjacency(chisel_hip_map *m, const char *name, int64_t V, int64_t T_, const int32_t *indices, int on_device, int32_t *tri_offsets, int64_t capacity_incidence,
                   int32_t *tri_items, int32_t *nbr_offsets, int64_t capacity_neighbors, int32_t *nbr_items, int32_t *vertex_flags, chisel_hip_adjacency_totals *totals) {
-    int rc = components::begin(m, name);
+    int rc = begin_on_one_device(m, name);
     if (rc) return rc;
     bool unsupported = false;
     if (const char *why = adjacency_request_refusal(V, T_, indices, tri_offsets, capacity_incidence, tri_items, nbr_offsets, capacity_neighbors, nbr_items, vertex_flags,
                                                     totals, &unsupported))
         return refusal(name, why, unsupported);
     Call call(m, name, on_device);
-    rc = call.run(V, T_, indices, nullptr, 0, false, totals);
-    if (rc) return rc;
+    if ((rc = call.run(V, T_, indices, nullptr, 0, false, totals))) return rc;
     const Totals &T = call.T;
     const AdjacencyView &X = call.X;
     if (const char *why = adjacency_capacity_refusal(T.incidences, T.neighbors, capacity_incidence, tri_items, capacity_neighbors, nbr_items)) {
@@ -171,7 +152,7 @@ int run_adjacency(chisel_hip_map *m, const char *name, int64_t V, int64_t T_, co
             e = hipGetLastError();
         }
         e = out.finish(e);
-        if (e != hipSuccess) return components::hip_failure(name, e);
+        if (e != hipSuccess) return hip_failure(name, e);
     }
     copy_totals(T, totals);
     return CHISEL_HIP_OK;
@@ -179,13 +160,12 @@ int run_adjacency(chisel_hip_map *m, const char *name, int64_t V, int64_t T_, co
 
 int run_normals(chisel_hip_map *m, const char *name, int64_t V, int64_t T_, const int32_t *indices, const float *vertices, int on_device, float *normals,
                 chisel_hip_adjacency_totals *totals) {
-    int rc = components::begin(m, name);
+    int rc = begin_on_one_device(m, name);
     if (rc) return rc;
     bool unsupported = false;
     if (const char *why = normals_request_refusal(V, T_, indices, vertices, normals, totals, &unsupported)) return refusal(name, why, unsupported);
     Call call(m, name, on_device);
-    rc = call.run(V, T_, indices, normals ? vertices : nullptr, 0, false, totals);  // (the positions are read only where normals are written)
-    if (rc) return rc;
+    if ((rc = call.run(V, T_, indices, normals ? vertices : nullptr, 0, false, totals))) return rc;  // (the positions are read only where normals are written)
     float *d_normals = V ? normals : nullptr;
     if (d_normals) {
         Staging out(m->stream, on_device != 0);
@@ -193,7 +173,7 @@ int run_normals(chisel_hip_map *m, const char *name, int64_t V, int64_t T_, cons
         HIP_TRY(out.begin());
         launch_normals(m, call.X, call.d_vertices, d_normals);
         const hipError_t e = out.finish(hipGetLastError());
-        if (e != hipSuccess) return components::hip_failure(name, e);
+        if (e != hipSuccess) return hip_failure(name, e);
     }
     copy_totals(call.T, totals);
     return CHISEL_HIP_OK;
@@ -201,19 +181,17 @@ int run_normals(chisel_hip_map *m, const char *name, int64_t V, int64_t T_, cons
 
 int run_smooth(chisel_hip_map *m, const char *name, int64_t V, int64_t T_, const int32_t *indices, const float *vertices, int64_t iterations, float lambda, float mu,
                int pin_flags, int on_device, float *out_vertices, float *out_normals, chisel_hip_adjacency_totals *totals) {
-    int rc = components::begin(m, name);
+    int rc = begin_on_one_device(m, name);
     if (rc) return rc;
     bool unsupported = false;
     if (const char *why = smooth_request_refusal(V, T_, indices, vertices, iterations, lambda, mu, pin_flags, out_vertices, out_normals, totals, &unsupported))
         return refusal(name, why, unsupported);
     const int64_t passes = smooth_passes(iterations, mu);
     if (out_vertices && V && passes > 1) {  // the other buffer of the ping-pong
-        rc = grow_buffer(m->adjacency_mem.positions, 3 * (size_t)V, m->stream);
-        if (rc) return rc;
+        if ((rc = grow_buffer(m->adjacency_mem.positions, 3 * (size_t)V, m->stream))) return rc;
     }
     Call call(m, name, on_device);
-    rc = call.run(V, T_, indices, out_vertices ? vertices : nullptr, pin_flags, true, totals);
-    if (rc) return rc;
+    if ((rc = call.run(V, T_, indices, out_vertices ? vertices : nullptr, pin_flags, true, totals))) return rc;
     float *d_out = V ? out_vertices : nullptr, *d_normals = V ? out_normals : nullptr;
     if (d_out) {
         const size_t bytes = (size_t)V * 3 * sizeof(float);
@@ -234,7 +212,7 @@ int run_smooth(chisel_hip_map *m, const char *name, int64_t V, int64_t T_, const
         if (d_normals) launch_normals(m, call.X, d_out, d_normals);
         if (e == hipSuccess) e = hipGetLastError();
         e = out.finish(e);
-        if (e != hipSuccess) return components::hip_failure(name, e);
+        if (e != hipSuccess) return hip_failure(name, e);
     }
     copy_totals(call.T, totals);
     return CHISEL_HIP_OK;

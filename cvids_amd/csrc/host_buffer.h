@@ -8,6 +8,8 @@
 #include <stddef.h>
 #include <utility>
 
+struct chisel_hip_map;
+
 namespace chisel_hip {
 
 // n elements of device memory (hipMalloc / hipFree)
@@ -82,6 +84,19 @@ struct PinnedWords {
 private:
     PinnedBuffer<long long> block_;
     size_t words_ = 0;
+};
+
+// [n] 64-bit control words of a pass on the device -- zeroed by the call's one memset, added to by its kernels -- and where they
+// reach the host.  The two members that need the map (its stream, its progress) are defined in host_totals.h.
+struct ControlWords {
+    int prepare(chisel_hip_map *m, size_t n);  // allocated once, with the pinned words beside them
+    hipError_t zero(hipStream_t stream) { return hipMemsetAsync(ctl_.get(), 0, ctl_.size() * sizeof(unsigned long long), stream); }
+    unsigned long long *dev() const { return ctl_.get(); }  // what the views take as ctl
+    int report_and_wait(chisel_hip_map *m, volatile long long **words);  // the report kernel and THE WAIT of the call; *words: complete
+
+private:
+    DeviceBuffer<unsigned long long> ctl_;
+    PinnedWords host_;
 };
 
 inline size_t round16(size_t bytes) { return (bytes + 15) & ~(size_t)15; }

@@ -34,10 +34,7 @@ int begin(chisel_hip_map *m, const char *name, bool query, bool has_totals) {
 
 // THE WAIT of a call, behind its scan kernel: `words` are complete; a listed id that is not resident is refused with its index
 int wait_for_totals(chisel_hip_map *m, const char *name, volatile long long *words, int absent_word, bool listed) {
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    note_stream_idle(m);
-    std::atomic_thread_fence(std::memory_order_acquire);
+    if (int rc = wait_for_words(m)) return rc;
     if (listed && words[absent_word] >= 0)
         return fail(CHISEL_HIP_ERR_NOT_FOUND, chunks::with_index(name, (int64_t)words[absent_word], "chunk not resident (ChunkManager::GetChunk would throw std::out_of_range)"));
     return CHISEL_HIP_OK;

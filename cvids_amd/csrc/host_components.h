@@ -1,15 +1,8 @@
 // host_components.h -- chisel_hip_mesh_components and chisel_hip_filter_mesh (included by chisel_hip.hip; the kernels:
-// kernels_components.h; the refusals and the size arithmetic: components_checks.h; the definition: DESIGN.md 3.16).  The indexed
-// mesh's frame (host_indexed.h) around another subject: the map is neither read nor written -- it lends its device, its stream and its
-// scratch --, and everything is queued on the map's stream behind what was queued before, a chisel_hip_indexed_mesh(on_device) whose
-// outputs are this call's inputs included.  A group handle is refused, as chisel_hip_indexed_mesh refuses it.  Both entries read top
-// to bottom: refusals, the inputs (host arrays are staged through one owned device buffer), the scratch, label() -- init, hook,
-// label, the scans, report --, THE WAIT for the totals (pinned memory), the capacities, then what writes the caller's arrays: with
-// device pointers nothing is waited for behind those launches; host arrays are staged through a second owned buffer sized by the
-// totals, copied out once with exactly their live rows, and are complete on return.  The component table is host memory whatever
-// on_device says: its rows are written into pinned memory behind the wait (their number is a total), which costs a wait of its own.
-//
-// Scratch the map owns (chisel_hip_map::components_mem), grown on demand, freed with the map.
+// kernels_components.h; the refusals and the size arithmetic: components_checks.h; the definition: DESIGN.md 3.16).  The frame
+// of host_totals.h; the map is neither read nor written, and a chisel_hip_indexed_mesh(on_device) queued before, whose outputs are
+// this call's inputs, is in front of it on the stream.  In front of the wait: label() -- init, hook, label, the scans.  The component
+// table is host memory whatever on_device says (the number of its rows is a total).  Scratch: chisel_hip_map::components_mem.
 #pragma once
 
 namespace {
@@ -21,25 +14,12 @@ struct Totals {
 
 inline unsigned tiles(int64_t n) { return (unsigned)components_tiles(n); }
 
-// null map, a group, then the device
-int begin(chisel_hip_map *m, const char *name) {
-    if (!m) return fail(CHISEL_HIP_ERR_INVALID, "null map");
-    if (m->is_group) return fail(CHISEL_HIP_ERR_UNSUPPORTED, std::string(name) + " runs on one device and one stream: a group has several (hand it a map of one shard)");
-    HIP_TRY(hipSetDevice(m->device));
-    return CHISEL_HIP_OK;
-}
-
-// the scratch of a call of V vertices and T triangles, carved out of one buffer of ints (doubled when it grows), and the view on it
+// the scratch of a call of V vertices and T triangles, carved out of one buffer of ints, and the view on it
 int ensure_memory(chisel_hip_map *m, int64_t V, int64_t T, ComponentsView &X) {
     chisel_hip_map::ComponentsMemory &C = m->components_mem;
     const size_t v = (size_t)V, t = (size_t)T, n_sums = (size_t)components_tiles(std::max(V, T));
-    const size_t need = 6 * v + t + n_sums;
-    if (need > C.words.size()) {
-        const int rc = grow_buffer(C.words, std::max<size_t>(std::max<size_t>(need, 2 * C.words.size()), 4096), m->stream);  // (waits for the stream before it replaces the buffer)
-        if (rc) return rc;
-    }
-    if (!C.ctl) HIP_TRY(C.ctl.alloc(COMPONENTS_HOST_WORDS));
-    HIP_TRY(C.host.ensure(COMPONENTS_HOST_WORDS, m->stream));
+    if (int rc = grow_ints(m, C.words, 6 * v + t + n_sums)) return rc;
+    if (int rc = C.ctl.prepare(m, COMPONENTS_HOST_WORDS)) return rc;
     int *p = C.words.get();
     X.parent = p;
     X.root_of = p + v;
@@ -49,7 +29,7 @@ int ensure_memory(chisel_hip_map *m, int64_t V, int64_t T, ComponentsView &X) {
     X.vertex_prefix = p + 5 * v;
     X.tri_prefix = p + 6 * v;
     X.sums = p + 6 * v + t;
-    X.ctl = C.ctl.get();
+    X.ctl = C.ctl.dev();
     return CHISEL_HIP_OK;
 }
 
@@ -63,10 +43,10 @@ void scan(chisel_hip_map *m, const ComponentsView &X, int64_t n, int word) {
 }
 
 // Everything in front of the wait, then the wait: the components of X.indices, with `filter` the kept flags' prefixes too. -> T
-int label(chisel_hip_map *m, const char *name, ComponentsView &X, bool filter, Totals &T) {
+int label(chisel_hip_map *m, ComponentsView &X, bool filter, Totals &T) {
     chisel_hip_map::ComponentsMemory &C = m->components_mem;
     const dim3 per_vertex(tiles(X.V)), per_triangle(tiles(X.T)), block(COMPONENTS_TILE);
-    HIP_TRY(hipMemsetAsync(X.ctl, 0, COMPONENTS_HOST_WORDS * sizeof(unsigned long long), m->stream));
+    HIP_TRY(C.ctl.zero(m->stream));
     if (X.V) hipLaunchKernelGGL(components_init_kernel, per_vertex, block, 0, m->stream, X);
     if (X.V && X.T) hipLaunchKernelGGL(components_hook_kernel, per_triangle, block, 0, m->stream, X);
     if (X.V) hipLaunchKernelGGL(components_label_vertices_kernel, per_vertex, block, 0, m->stream, X);
@@ -76,12 +56,8 @@ int label(chisel_hip_map *m, const char *name, ComponentsView &X, bool filter, T
         scan<FLAG_KEPT_VERTEX>(m, X, X.V, CC_KEPT_VERTICES);
         if (X.V) scan<FLAG_KEPT_TRIANGLE>(m, X, X.T, CC_KEPT_TRIANGLES);  // (without a vertex no triangle is valid)
     }
-    hipLaunchKernelGGL(components_report_kernel, dim3(1), dim3(64), 0, m->stream, (const unsigned long long *)X.ctl, C.host.dev());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(m->stream));  // THE WAIT
-    note_stream_idle(m);
-    std::atomic_thread_fence(std::memory_order_acquire);
-    volatile long long *w = C.host.get();
+    volatile long long *w;
+    if (int rc = C.ctl.report_and_wait(m, &w)) return rc;
     T.vertices = X.V;
     T.triangles = X.T;
     T.invalid_triangles = w[CC_INVALID];
@@ -90,20 +66,17 @@ int label(chisel_hip_map *m, const char *name, ComponentsView &X, bool filter, T
     T.kept_components = w[CC_KEPT_COMPONENTS];
     T.kept_vertices = w[CC_KEPT_VERTICES];
     T.kept_triangles = w[CC_KEPT_TRIANGLES];
-    (void)name;
     return CHISEL_HIP_OK;
 }
-
-int hip_failure(const char *name, hipError_t e) { return fail(CHISEL_HIP_ERR_HIP, std::string(name) + ": " + hipGetErrorString(e)); }
 
 int run_components(chisel_hip_map *m, const char *name, int64_t V, int64_t T_, const int32_t *indices, int on_device, int32_t *vertex_component,
                    int32_t *triangle_component, int64_t capacity_components, int64_t *component_table, chisel_hip_components_totals *totals) {
     // ---- refusals that need no device
-    int rc = begin(m, name);
+    int rc = begin_on_one_device(m, name);
     if (rc) return rc;
     bool unsupported = false;
     if (const char *why = components_request_refusal(V, T_, indices, vertex_component, triangle_component, capacity_components, component_table, totals, &unsupported))
-        return fail(unsupported ? CHISEL_HIP_ERR_UNSUPPORTED : CHISEL_HIP_ERR_INVALID, std::string(name) + ": " + why);
+        return refusal(name, why, unsupported);
     Totals T{V, T_, 0, 0, 0, 0, 0, 0};
     if (V == 0 && T_ == 0) {  // nothing is launched
         copy_totals(T, totals);
@@ -114,20 +87,17 @@ int run_components(chisel_hip_map *m, const char *name, int64_t V, int64_t T_, c
     X.V = (int)V;
     X.T = (int)T_;
     X.min_triangles = 1;
-    rc = ensure_memory(m, V, T_, X);
-    if (rc) return rc;
-    rc = wait_for_input(m, m->stream);  // chisel_hip_wait_event / _order_map_after_stream: the arrays are ready behind it
-    if (rc) return rc;
+    if ((rc = ensure_memory(m, V, T_, X))) return rc;
+    if ((rc = wait_for_input(m, m->stream))) return rc;  // chisel_hip_wait_event / _order_map_after_stream: the arrays are ready behind it
     const int32_t *d_indices = T_ ? indices : nullptr;
     Staging in(m->stream, on_device != 0);
     in.in(d_indices, (size_t)T_ * 3 * sizeof(int32_t));
     HIP_TRY(in.begin());
     X.indices = d_indices;
-    rc = label(m, name, X, false, T);
-    if (rc) return rc;
+    if ((rc = label(m, X, false, T))) return rc;
     if (const char *why = components_capacity_refusal(T.components, capacity_components, component_table)) {
         copy_totals(T, totals);  // (the caller can retry)
-        return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": " + why);
+        return refusal(name, why, false);
     }
     // ---- the labels and the table
     chisel_hip_map::ComponentsMemory &C = m->components_mem;
@@ -144,12 +114,7 @@ int run_components(chisel_hip_map *m, const char *name, int64_t V, int64_t T_, c
         if (dt) hipLaunchKernelGGL(components_write_triangles_kernel, dim3(tiles(T_)), block, 0, m->stream, X, dt);
         if (table) hipLaunchKernelGGL(components_write_table_kernel, dim3(tiles(V)), block, 0, m->stream, X, C.table_host.dev(), (long long)T.components);
         hipError_t e = out.finish(hipGetLastError());
-        if (e == hipSuccess && table) {  // (host arrays have waited in finish; device arrays are left on the stream, the table is not)
-            if (on_device) e = hipStreamSynchronize(m->stream);
-            std::atomic_thread_fence(std::memory_order_acquire);
-            volatile long long *rows = C.table_host.get();
-            for (int64_t i = 0; e == hipSuccess && i < 3 * T.components; i++) component_table[i] = rows[i];
-        }
+        if (table) e = read_pinned_table(m, C.table_host, 3 * (size_t)T.components, on_device != 0, e, component_table);
         if (e != hipSuccess) return hip_failure(name, e);
     }
     copy_totals(T, totals);
@@ -160,12 +125,12 @@ int run_filter(chisel_hip_map *m, const char *name, int64_t V, int64_t T_, const
                int64_t min_triangles, int largest_only, int64_t capacity_vertices, int64_t capacity_triangles, float *out_vertices, int32_t *out_indices,
                float *out_normals, float *out_colors, int32_t *vertex_map, int32_t *triangle_map, int on_device, chisel_hip_components_totals *totals) {
     // ---- refusals that need no device
-    int rc = begin(m, name);
+    int rc = begin_on_one_device(m, name);
     if (rc) return rc;
     bool unsupported = false;
     if (const char *why = filter_request_refusal(V, T_, indices, vertices, normals, colors, min_triangles, largest_only, capacity_vertices, capacity_triangles,
                                                  out_vertices, out_indices, out_normals, out_colors, totals, &unsupported))
-        return fail(unsupported ? CHISEL_HIP_ERR_UNSUPPORTED : CHISEL_HIP_ERR_INVALID, std::string(name) + ": " + why);
+        return refusal(name, why, unsupported);
     const bool query = capacity_vertices == 0 && capacity_triangles == 0;
     Totals T{V, T_, 0, 0, 0, 0, 0, 0};
     if (V == 0 && T_ == 0) {  // nothing is launched
@@ -178,10 +143,8 @@ int run_filter(chisel_hip_map *m, const char *name, int64_t V, int64_t T_, const
     X.T = (int)T_;
     X.min_triangles = (int)std::min<int64_t>(min_triangles, COMPONENTS_MAX_INTS);  // (no component has 2^31 - 1 triangles: none is kept)
     X.largest_only = largest_only;
-    rc = ensure_memory(m, V, T_, X);
-    if (rc) return rc;
-    rc = wait_for_input(m, m->stream);
-    if (rc) return rc;
+    if ((rc = ensure_memory(m, V, T_, X))) return rc;
+    if ((rc = wait_for_input(m, m->stream))) return rc;
     const bool rows = !query && out_vertices && V;  // (the float rows are read only where they are written)
     const size_t f3 = (size_t)V * 3 * sizeof(float);
     const int32_t *d_indices = T_ ? indices : nullptr;
@@ -193,12 +156,11 @@ int run_filter(chisel_hip_map *m, const char *name, int64_t V, int64_t T_, const
     in.in(sc, f3);
     HIP_TRY(in.begin());
     X.indices = d_indices;
-    rc = label(m, name, X, true, T);
-    if (rc) return rc;
+    if ((rc = label(m, X, true, T))) return rc;
     if (!query) {
         if (const char *why = filter_capacity_refusal(T.kept_vertices, T.kept_triangles, capacity_vertices, capacity_triangles, out_vertices, out_indices)) {
             copy_totals(T, totals);  // (the caller can retry)
-            return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": " + why);
+            return refusal(name, why, false);
         }
         // ---- the maps, the renumbered ids, the copied rows
         const size_t k3 = (size_t)T.kept_vertices * 3 * sizeof(float);

@@ -1,12 +1,8 @@
 // host_frontier.h -- chisel_hip_frontiers (included by chisel_hip.hip; the kernels: kernels_frontier.h; the refusals, the widened
 // window, the tile grid and the scratch sizes: frontier_checks.h; the definition: DESIGN.md 3.18).  chisel_hip_distance_field's frame
-// (host_distance.h) in front of the wait -- the map is only read, everything goes on the map's stream behind whatever was queued
-// before --, chisel_hip_filter_mesh's behind it (host_components.h): THE WAIT for the totals (pinned memory), the capacities, then what
-// writes the caller's arrays.  With device pointers nothing is waited for behind those launches; host arrays are staged through one
-// owned buffer sized by the totals, copied out once with exactly their live rows, and are complete on return.  The cluster table is
-// host memory whatever on_device says: its rows are written into pinned memory behind the wait, which costs a wait of its own.
-//
-// Scratch the map owns (chisel_hip_map::frontier_mem), grown on demand, freed with the map.
+// (host_distance.h) in front of the wait -- the map is only read, and a group is answered by query_refusal --, the frame of
+// host_totals.h from the control words on.  The cluster table is host memory whatever on_device says.  Scratch:
+// chisel_hip_map::frontier_mem.
 #pragma once
 
 namespace {
@@ -23,8 +19,7 @@ int ensure_memory(chisel_hip_map *m, const FrontierPlan &plan, FrontierView &X) 
     chisel_hip_map::FrontierMemory &F = m->frontier_mem;
     if (int rc = grow_buffer(F.planes, (size_t)plan.plane_words, m->stream)) return rc;  // (waits for the stream before it replaces a buffer)
     if (int rc = grow_buffer(F.ints, (size_t)plan.ints, m->stream)) return rc;
-    if (!F.ctl) HIP_TRY(F.ctl.alloc(FRONTIER_HOST_WORDS));
-    HIP_TRY(F.host.ensure(FRONTIER_HOST_WORDS, m->stream));
+    if (int rc = F.ctl.prepare(m, FRONTIER_HOST_WORDS)) return rc;
     unsigned long long *p = F.planes.get();
     const size_t wide = (size_t)plan.wide_words, words = (size_t)plan.words;
     X.wide_free = p;
@@ -40,7 +35,7 @@ int ensure_memory(chisel_hip_map *m, const FrontierPlan &plan, FrontierView &X) 
     X.parent = q;
     X.root_of = q + (size_t)plan.voxels;
     X.count = q + 2 * (size_t)plan.voxels;
-    X.ctl = F.ctl.get();
+    X.ctl = F.ctl.dev();
     return CHISEL_HIP_OK;
 }
 
@@ -55,21 +50,15 @@ int chisel_hip_frontiers(chisel_hip_map *m, const chisel_hip_frontier_window *wi
     static_assert(sizeof(chisel_hip_frontier_window) == 40, "chisel_hip_frontier_window is 40 bytes");
     const char *name = "chisel_hip_frontiers";
     SETTLE(m);
-    {
-        int rc_r = query_refusal(m, name, "reads the voxels of the window and of a margin around it");
-        if (rc_r) return rc_r;
-    }
+    if (int rc = query_refusal(m, name, "reads the voxels of the window and of a margin around it")) return rc;
     FrontierPlan plan;
     {
         int code = 0;
         if (const char *why = frontier_refusal(window, totals, capacity_voxels, voxels, capacity_clusters, cluster_table, &code, &plan))
-            return fail(code == FRONTIER_REFUSED_UNSUPPORTED ? CHISEL_HIP_ERR_UNSUPPORTED : CHISEL_HIP_ERR_INVALID, std::string(name) + ": " + why);
+            return refusal(name, why, code == FRONTIER_REFUSED_UNSUPPORTED);
     }
     HIP_TRY(hipSetDevice(m->device));
-    {
-        int rc_m = check_mesh_totals(m);  // a recompute in flight reads the voxels as they are
-        if (rc_m) return rc_m;
-    }
+    if (int rc = check_mesh_totals(m)) return rc;  // a recompute in flight reads the voxels as they are
     // ---- the scratch, everything in front of the wait, the wait
     FrontierView X{};
     for (int a = 0; a < 3; a++) {
@@ -85,18 +74,12 @@ int chisel_hip_frontiers(chisel_hip_map *m, const chisel_hip_frontier_window *wi
     X.wide_words_per_row = (int)plan.wide_words_per_row;
     X.words_per_row = (int)plan.words_per_row;
     X.words = plan.words;
-    {
-        int rc_s = frontier::ensure_memory(m, plan, X);
-        if (rc_s) return rc_s;
-    }
-    {
-        int rc_w = wait_for_input(m, m->stream);  // chisel_hip_wait_event / _order_map_after_stream: the outputs may be written behind it
-        if (rc_w) return rc_w;
-    }
+    if (int rc = frontier::ensure_memory(m, plan, X)) return rc;
+    if (int rc = wait_for_input(m, m->stream)) return rc;  // chisel_hip_wait_event / _order_map_after_stream: the outputs may be written behind it
     chisel_hip_map::FrontierMemory &F = m->frontier_mem;
     const dim3 block(FRONTIER_THREADS);
     const dim3 per_word(frontier::blocks(plan.words, FRONTIER_THREADS)), per_voxel(frontier::blocks(plan.words, 4)), per_tile((unsigned)plan.n_tiles);
-    HIP_TRY(hipMemsetAsync(X.ctl, 0, FRONTIER_HOST_WORDS * sizeof(unsigned long long), m->stream));
+    HIP_TRY(F.ctl.zero(m->stream));
     const long long n_runs = plan.wide_words;  // (a run holds a voxel of the widened window)
     FOR_CHUNK_SIZE(m->N, hipLaunchKernelGGL(frontier_seed_kernel<N>, dim3(frontier::blocks(n_runs, 4)), dim3(256), 0, m->stream, m->view, X, n_runs));
     hipLaunchKernelGGL(frontier_mark_kernel, per_word, block, 0, m->stream, X);
@@ -107,14 +90,10 @@ int chisel_hip_frontiers(chisel_hip_map *m, const chisel_hip_frontier_window *wi
     hipLaunchKernelGGL(frontier_sums_kernel, per_word, block, 0, m->stream, X);
     hipLaunchKernelGGL(frontier_scan_sums_kernel, dim3(1), block, 0, m->stream, X.sums, (long long)plan.scan_tiles, X.ctl);
     hipLaunchKernelGGL(frontier_prefix_kernel, per_word, block, 0, m->stream, X);
-    hipLaunchKernelGGL(frontier_report_kernel, dim3(1), dim3(64), 0, m->stream, (const unsigned long long *)X.ctl, F.host.dev());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(m->stream));  // THE WAIT
-    note_stream_idle(m);
-    std::atomic_thread_fence(std::memory_order_acquire);
     frontier::Totals T;
     {
-        volatile long long *w = F.host.get();
+        volatile long long *w;
+        if (int rc = F.ctl.report_and_wait(m, &w)) return rc;
         T.unknown = w[FC_UNKNOWN];
         T.free = w[FC_FREE];
         T.occupied = plan.voxels - T.unknown - T.free;
@@ -130,14 +109,13 @@ int chisel_hip_frontiers(chisel_hip_map *m, const chisel_hip_frontier_window *wi
     }
     if (const char *why = frontier_capacity_refusal(T.kept_voxels, T.kept_clusters, capacity_voxels, voxels, capacity_clusters, cluster_table)) {
         copy_totals(T, totals);  // (the caller can retry)
-        return fail(CHISEL_HIP_ERR_INVALID, std::string(name) + ": " + why);
+        return refusal(name, why, false);
     }
     // ---- the per-voxel arrays, the list and the table
     const bool table = cluster_table && capacity_clusters > 0 && T.kept_clusters > 0;
     const size_t table_words = (size_t)T.kept_clusters * FRONTIER_TABLE_WORDS;
     if (table) {
-        int rc_t = grow_buffer(F.acc, table_words, m->stream);
-        if (rc_t) return rc_t;
+        if (int rc = grow_buffer(F.acc, table_words, m->stream)) return rc;
         HIP_TRY(F.table_host.ensure(table_words, m->stream));
     }
     uint8_t *ds = state;
@@ -155,13 +133,8 @@ int chisel_hip_frontiers(chisel_hip_map *m, const chisel_hip_frontier_window *wi
                            F.table_host.dev(), (long long)table_words);
     }
     hipError_t e = out.finish(hipGetLastError());
-    if (e == hipSuccess && table) {  // (host arrays have waited in finish; device arrays are left on the stream, the table is not)
-        if (on_device) e = hipStreamSynchronize(m->stream);
-        std::atomic_thread_fence(std::memory_order_acquire);
-        volatile long long *rows = F.table_host.get();
-        for (size_t i = 0; e == hipSuccess && i < table_words; i++) cluster_table[i] = rows[i];
-    }
-    if (e != hipSuccess) return fail(CHISEL_HIP_ERR_HIP, std::string(name) + ": " + hipGetErrorString(e));
+    if (table) e = read_pinned_table(m, F.table_host, table_words, on_device != 0, e, cluster_table);
+    if (e != hipSuccess) return hip_failure(name, e);
     copy_totals(T, totals);
     return CHISEL_HIP_OK;
 }

@@ -4,11 +4,11 @@
 // DESIGN.md 3.17).  Every step is a launch of its own on the map's stream, nothing crosses workgroups inside a kernel, and no float is
 // ever added atomically: the rows are SORTED before a float is summed along them, so every sum has one order.
 //
-//   adjacency_count_kernel      a thread per triangle: a VALID triangle (all three ids in [0, V), tested before any is used as an
-//                               address) adds 1 to deg[] of each DISTINCT id it names (int32 vector atomics); the invalid are counted
+//   adjacency_count_kernel      a thread per triangle: a VALID triangle (mesh_triangle of kernels_workgroup.h) adds 1 to deg[] of each
+//                               DISTINCT id it names (int32 vector atomics); the invalid are counted
 //   adjacency_sums_kernel / adjacency_scan_sums_kernel / adjacency_prefix_kernel
-//                               the reduce-then-scan of kernels_components.h over an int per element instead of a flag, V + 1
-//                               elements (the last one 0: its prefix is the total, offsets[V]); the maximum rides in the same two
+//                               a reduce-then-scan over tiles of COMPONENTS_TILE (scan_tile_sums in the middle) of an int per element,
+//                               V + 1 elements (the last one 0: its prefix is the total, offsets[V]); the maximum rides in the same two
 //                               passes, a tile's maximum beside a tile's sum: no atomic
 //   adjacency_fill_kernel       a thread per triangle: a slot of each named row through the row's atomic cursor; the order inside a
 //                               row is whatever the scheduling made it
@@ -20,10 +20,9 @@
 //   adjacency_compact_kernel    the neighbour rows to their offsets in the caller's array
 //   mesh_vertex_normals_kernel  a thread per vertex: the face normals of its row, added in ascending triangle order, normalised
 //   mesh_smooth_pass_kernel     a thread per vertex: one umbrella step with factor f from P into Q; a pinned vertex is copied
-//   adjacency_report_kernel     the control words into pinned memory: what the host reads after its one wait
 #pragma once
-#include "kernels_components.h"  // block_exclusive_scan, components_element
-#include "adjacency_checks.h"
+#include "kernels_workgroup.h"
+#include "adjacency_checks.h"  // (the tile is components_checks.h's COMPONENTS_TILE: WORKGROUP_THREADS, as kernels_components.h asserts)
 
 namespace chisel_hip {
 
@@ -41,17 +40,11 @@ struct AdjacencyView {
     int count_pinned;
 };
 
-__device__ inline bool adjacency_triangle(const AdjacencyView &X, long long t, int &a, int &b, int &c) {
-    const int *p = X.indices + 3 * (size_t)t;
-    a = p[0]; b = p[1]; c = p[2];
-    return (unsigned)a < (unsigned)X.V && (unsigned)b < (unsigned)X.V && (unsigned)c < (unsigned)X.V;
-}
-
 __global__ __launch_bounds__(COMPONENTS_TILE) void adjacency_count_kernel(AdjacencyView X) {
-    const long long t = components_element();
+    const long long t = tile_element();
     int a, b, c;
     const bool in = t < X.T;
-    const bool valid = in && adjacency_triangle(X, t, a, b, c);
+    const bool valid = in && mesh_triangle(X.indices, X.V, t, a, b, c);
     if (valid) {
         atomicAdd(&X.deg[a], 1);
         if (b != a) atomicAdd(&X.deg[b], 1);
@@ -61,50 +54,29 @@ __global__ __launch_bounds__(COMPONENTS_TILE) void adjacency_count_kernel(Adjace
     if (threadIdx.x == 0 && invalid) atomicAdd(&X.ctl[AC_INVALID], (unsigned long long)invalid);
 }
 
-// the maximum of `mine` over the workgroup, in every lane (s_wave: one int a wave)
-__device__ inline int adjacency_block_max(int mine, int *s_wave) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mine = max(mine, __shfl_xor(mine, o));
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    int most = s_wave[0];
-#pragma unroll
-    for (int w = 1; w < COMPONENTS_TILE / 64; w++) most = max(most, s_wave[w]);
-    __syncthreads();
-    return most;
-}
-
 // values[n] and one 0 behind them: a tile's sum and a tile's maximum (not an atomicMax a wave into a control word: a million vertices
 // queue 8 800 of them up at that one word, 11 ns each -- 100 of a launch's 103 microseconds when it was measured)
 __global__ __launch_bounds__(COMPONENTS_TILE) void adjacency_sums_kernel(const int *__restrict__ values, int n, int *__restrict__ sums, int *__restrict__ maxes) {
     __shared__ int s_wave[COMPONENTS_TILE / 64];
-    const long long i = components_element();
+    const long long i = tile_element();
     const int mine = i < n ? values[i] : 0;
     int total;
     (void)block_exclusive_scan(mine, s_wave, total);
-    const int most = adjacency_block_max(mine, s_wave);
+    const int most = block_max(mine, s_wave);
     if (threadIdx.x == 0) {
         sums[blockIdx.x] = total;
         maxes[blockIdx.x] = most;
     }
 }
 
-// One workgroup.  components_scan_sums_kernel with the tiles' maxima beside it: sums[b] = the sums of the tiles in front of b;
-// ctl[total_word] = the total (<= 2^31 - 1), ctl[max_word] = the largest element.
+// One workgroup.  The tiles' maxima beside their sums: sums[b] = the sums of the tiles in front of b; ctl[total_word] = the total
+// (<= 2^31 - 1), ctl[max_word] = the largest element.
 __global__ __launch_bounds__(COMPONENTS_TILE) void adjacency_scan_sums_kernel(int *__restrict__ sums, const int *__restrict__ maxes, int n_tiles,
                                                                               unsigned long long *__restrict__ ctl, int total_word, int max_word) {
     __shared__ int s_wave[COMPONENTS_TILE / 64];
-    int run = 0, most = 0;
-    for (int base = 0; base < n_tiles; base += COMPONENTS_TILE) {
-        const int b = base + (int)threadIdx.x;
-        const int mine = b < n_tiles ? sums[b] : 0;
-        most = max(most, b < n_tiles ? maxes[b] : 0);
-        int total;
-        const int before = block_exclusive_scan(mine, s_wave, total);
-        if (b < n_tiles) sums[b] = run + before;
-        run += total;
-    }
-    most = adjacency_block_max(most, s_wave);
+    int most = 0;
+    const int run = scan_tile_sums<true>(sums, n_tiles, s_wave, maxes, &most);
+    most = block_max(most, s_wave);
     if (threadIdx.x == 0) {
         ctl[total_word] = (unsigned long long)run;
         ctl[max_word] = (unsigned long long)most;
@@ -114,7 +86,7 @@ __global__ __launch_bounds__(COMPONENTS_TILE) void adjacency_scan_sums_kernel(in
 // prefix[i] = the values in front of element i, for i = 0 ... n (prefix[n]: the total)
 __global__ __launch_bounds__(COMPONENTS_TILE) void adjacency_prefix_kernel(const int *__restrict__ values, int n, const int *__restrict__ sums, int *__restrict__ prefix) {
     __shared__ int s_wave[COMPONENTS_TILE / 64];
-    const long long i = components_element();
+    const long long i = tile_element();
     const int mine = i < n ? values[i] : 0;
     int total;
     const int at = sums[blockIdx.x] + block_exclusive_scan(mine, s_wave, total);
@@ -122,9 +94,9 @@ __global__ __launch_bounds__(COMPONENTS_TILE) void adjacency_prefix_kernel(const
 }
 
 __global__ __launch_bounds__(COMPONENTS_TILE) void adjacency_fill_kernel(AdjacencyView X) {
-    const long long t = components_element();
+    const long long t = tile_element();
     int a, b, c;
-    if (t >= X.T || !adjacency_triangle(X, t, a, b, c)) return;
+    if (t >= X.T || !mesh_triangle(X.indices, X.V, t, a, b, c)) return;
     // (the count kernel counted the same ids: a cursor stays below its row's length, a slot below 3 T)
     X.tri_items[X.tri_off[a] + atomicAdd(&X.cursor[a], 1)] = (int)t;
     if (b != a) X.tri_items[X.tri_off[b] + atomicAdd(&X.cursor[b], 1)] = (int)t;
@@ -156,7 +128,7 @@ __global__ __launch_bounds__(ADJACENCY_ROWS_THREADS) void adjacency_rows_kernel(
                 const int t = s_tri[k][lane];
                 X.tri_items[first + k] = t;
                 int a, b, c;
-                (void)adjacency_triangle(X, t, a, b, c);  // (a triangle of a row is valid)
+                (void)mesh_triangle(X.indices, X.V, t, a, b, c);  // (a triangle of a row is valid)
                 if (a != (int)v) adjacency_insert(s_nbr, lane, n, a);
                 if (b != (int)v && b != a) adjacency_insert(s_nbr, lane, n, b);
                 if (c != (int)v && c != a && c != b) adjacency_insert(s_nbr, lane, n, c);
@@ -187,7 +159,7 @@ __global__ __launch_bounds__(ADJACENCY_ROWS_THREADS) void adjacency_rows_kernel(
 }
 
 __global__ __launch_bounds__(COMPONENTS_TILE) void adjacency_compact_kernel(AdjacencyView X, int *__restrict__ nbr_items) {
-    const long long v = components_element();
+    const long long v = tile_element();
     if (v >= X.V) return;
     const int *row = X.nbr_rows + 2 * (size_t)X.tri_off[v];
     int *to = nbr_items + X.nbr_off[v];
@@ -197,13 +169,13 @@ __global__ __launch_bounds__(COMPONENTS_TILE) void adjacency_compact_kernel(Adja
 
 // DESIGN.md 3.17 VERTEX NORMALS: fp32, one operation per rounding (the library builds with -ffp-contract=off and IEEE divide / sqrt)
 __global__ __launch_bounds__(COMPONENTS_TILE) void mesh_vertex_normals_kernel(AdjacencyView X, const float *__restrict__ P, float *__restrict__ normals) {
-    const long long v = components_element();
+    const long long v = tile_element();
     if (v >= X.V) return;
     const int first = X.tri_off[v], d = min(X.tri_off[v + 1] - first, MESH_MAX_INCIDENT);
     float ax = 0.0f, ay = 0.0f, az = 0.0f;
     for (int k = 0; k < d; k++) {
         int i0, i1, i2;
-        (void)adjacency_triangle(X, X.tri_items[first + k], i0, i1, i2);
+        (void)mesh_triangle(X.indices, X.V, X.tri_items[first + k], i0, i1, i2);
         const float *p0 = P + 3 * (size_t)i0, *p1 = P + 3 * (size_t)i1, *p2 = P + 3 * (size_t)i2;
         const float pxx = p1[0] - p0[0], pxy = p1[1] - p0[1], pxz = p1[2] - p0[2];
         const float pyx = p2[0] - p0[0], pyy = p2[1] - p0[1], pyz = p2[2] - p0[2];
@@ -221,7 +193,7 @@ __global__ __launch_bounds__(COMPONENTS_TILE) void mesh_vertex_normals_kernel(Ad
 
 // DESIGN.md 3.17 SMOOTHING: one pass with factor f, P -> Q (never the same array)
 __global__ __launch_bounds__(COMPONENTS_TILE) void mesh_smooth_pass_kernel(AdjacencyView X, const float *__restrict__ P, float *__restrict__ Q, float f) {
-    const long long v = components_element();
+    const long long v = tile_element();
     if (v >= X.V) return;
     const int n = min(X.nbr_count[v], MESH_MAX_NEIGHBORS);
     const float *p = P + 3 * (size_t)v;
@@ -244,10 +216,6 @@ __global__ __launch_bounds__(COMPONENTS_TILE) void mesh_smooth_pass_kernel(Adjac
     const float dx = mx - p[0], dy = my - p[1], dz = mz - p[2];
     const float sx = f * dx, sy = f * dy, sz = f * dz;
     q[0] = p[0] + sx; q[1] = p[1] + sy; q[2] = p[2] + sz;
-}
-
-__global__ void adjacency_report_kernel(const unsigned long long *__restrict__ ctl, long long *__restrict__ host) {
-    if (threadIdx.x < ADJACENCY_HOST_WORDS) host[threadIdx.x] = (long long)ctl[threadIdx.x];
 }
 
 }  // namespace chisel_hip

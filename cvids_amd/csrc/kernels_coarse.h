@@ -2,7 +2,7 @@
 // selection's order (the host side: host_coarse.h; the stride rule and the request checks: coarse_checks.h; the definition:
 // DESIGN.md 3.14).  Beside the mesher (kernels_mesh.h), whose kernels it does not touch: it shares their tables, interpolate_vertex and
 // the face normal, and shade_vertices_kernel runs on its output unchanged.  The indexed mesh (kernels_indexed.h) is built from the
-// pieces of this file: the lattice, the two walks, the workgroup scan and the chunk scan are written here once.
+// pieces of this file: the lattice, the two walks and the chunk scan are written here once (the workgroup scan: kernels_workgroup.h).
 //
 // Chunk c of the selection has M^3 coarse cubes, M = N / s; cube (i, j, k) has its corners at the voxels s (i, j, k) + s offset_d, a
 // component N meaning voxel 0 of the + neighbour.  All corners of a chunk's cubes are the (M + 1)^3 LATTICE of voxels s (li, lj, lk),
@@ -26,35 +26,12 @@
 #include "kernels_map.h"
 #include "kernels_mesh.h"
 #include "kernels_rewrite.h"  // ChunkCentres, tally_count
+#include "kernels_workgroup.h"
 #include "coarse_checks.h"
 
 namespace chisel_hip {
 
-// The exclusive sum of `mine` over the lanes of a workgroup, and the workgroup's `total`.  EVERY lane of a COARSE_THREADS workgroup
-// calls it (a lane with nothing passes 0); s_wave: COARSE_THREADS / 64 words of LDS.  The function owns both barriers around s_wave:
-// one between the waves' sums and their readers, one behind the readers -- s_wave is free again on return, and what the workgroup
-// wrote in front of the call can be read behind it.
-template <class T>
-__device__ inline T block_exclusive_scan(T mine, T *s_wave, T &total) {
-    const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-    T incl = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T up = __shfl_up(incl, o);
-        if (lane >= o) incl += up;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    T before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < COARSE_THREADS / 64; w++) {
-        before += w < wave ? s_wave[w] : 0;
-        total += s_wave[w];
-    }
-    __syncthreads();
-    return before + incl - mine;
-}
+static_assert(COARSE_THREADS == WORKGROUP_THREADS, "the walks and the scans take block_exclusive_scan's workgroup");
 
 // One slab of a chunk's lattice in LDS, and the slots it is read from (trivially constructible: a kernel declares one __shared__).
 template <int N>

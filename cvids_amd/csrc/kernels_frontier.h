@@ -13,28 +13,28 @@
 //                             voxels of the tile are united among themselves with LDS compare-and-swaps, always the larger index
 //                             under the smaller, then every voxel's tile root goes to parent[] in global memory.
 //   frontier_merge_kernel     the pairs of neighbours that straddle two tiles (faces, edges and corners alike: every forward offset
-//                             of the connectivity that leaves the tile) are united in global memory by components_unite's rule --
+//                             of the connectivity that leaves the tile) are united in global memory by union_unite (kernels_workgroup.h) --
 //                             every access to parent[] an agent-scope relaxed atomic, nobody waits for anybody.
 //   frontier_label_kernel     behind the merge's end parent[] is read-only: plain loads to the root, root_of[v], the ROOT plane by
-//                             ballot, + 1 to count[root] (components_count: one atomic per wave and root).
+//                             ballot, + 1 to count[root] (wave_count: one atomic per wave and root).
 //   frontier_keep_kernel      the KEPT and KEPT ROOT planes (count[root] >= min_voxels), the largest cluster.
 //   frontier_sums_kernel / frontier_scan_sums_kernel / frontier_prefix_kernel
-//                             reduce-then-scan over the words of both planes at once (two 32-bit counts in one 64-bit word), no
-//                             look-back: the kept roots and the kept voxels in front of every word.  A kept cluster's number is its
-//                             root's word prefix plus the popcount below its bit; a kept voxel's row in the list likewise.
-//   frontier_report_kernel    the control words into pinned memory: what the host reads after its one wait.
+//                             reduce-then-scan over the words of both planes at once (two 32-bit counts in one 64-bit word;
+//                             scan_tile_sums in the middle), no look-back: the kept roots and the kept voxels in front of every
+//                             word.  A kept cluster's number is its root's word prefix plus the popcount below its bit; a kept
+//                             voxel's row in the list likewise.  Then the control words go to the host and the host waits.
 //   frontier_write_kernel     state (from the two planes), label and the voxel list, behind the wait and the capacity check.
 //   frontier_table_*          the cluster table: 64-bit integer atomics (add, min, max) into a device accumulator; a wave walks a run
 //                             of words and adds once per stretch of one cluster, its sums popcounts of wave-uniform words; then the
 //                             rows into pinned memory.
 #pragma once
 #include "kernels_distance.h"    // distance_chunk_slot, DistanceLog2
-#include "kernels_components.h"  // components_unite, components_count, block_exclusive_scan (helpers only: its kernels stay as they are)
+#include "kernels_workgroup.h"
 #include "frontier_checks.h"
 
 namespace chisel_hip {
 
-static_assert(FRONTIER_THREADS == COARSE_THREADS, "block_exclusive_scan is written for COARSE_THREADS lanes");
+static_assert(FRONTIER_THREADS == WORKGROUP_THREADS, "a scan tile is what one workgroup of kernels_workgroup.h takes");
 static_assert(FRONTIER_TILE_X == 16 && FRONTIER_TILE_ROWS * 2 == FRONTIER_THREADS, "a thread of a tile takes 8 bits of one of its 128 rows");
 
 struct FrontierView {
@@ -143,7 +143,7 @@ __device__ inline int frontier_wave_sum(int mine) {
 }
 
 __global__ __launch_bounds__(FRONTIER_THREADS) void frontier_mark_kernel(FrontierView X) {
-    const long long i = (long long)blockIdx.x * FRONTIER_THREADS + threadIdx.x;
+    const long long i = tile_element();
     int n_unknown = 0, n_free = 0, n_front = 0;
     if (i < X.words) {
         const long long row = i / X.words_per_row;
@@ -271,7 +271,7 @@ __global__ __launch_bounds__(FRONTIER_THREADS) void frontier_merge_kernel(Fronti
                     const int x = T.x0 + jx, y = T.y0 + jy, z = T.z0 + jz;
                     if ((unsigned)x >= (unsigned)X.dims[0] || (unsigned)y >= (unsigned)X.dims[1] || z >= X.dims[2]) continue;  // outside the window: joins nothing
                     const unsigned long long there = X.front[((long long)z * X.dims[1] + y) * X.words_per_row + (x >> 6)];
-                    if ((there >> (x & 63)) & 1ull) components_unite(X.parent, T.linear(X, i), (z * X.dims[1] + y) * X.dims[0] + x);
+                    if ((there >> (x & 63)) & 1ull) union_unite(X.parent, T.linear(X, i), (z * X.dims[1] + y) * X.dims[0] + x);
                 }
     }
 }
@@ -309,7 +309,7 @@ __global__ __launch_bounds__(FRONTIER_THREADS) void frontier_label_kernel(Fronti
         X.roots[L.word] = roots;
         if (roots) atomicAdd(&X.ctl[FC_CLUSTERS], (unsigned long long)__popcll(roots));
     }
-    components_count(X.count, r, front);
+    wave_count(X.count, r, front);
 }
 
 __global__ __launch_bounds__(FRONTIER_THREADS) void frontier_keep_kernel(FrontierView X) {
@@ -339,21 +339,13 @@ __device__ inline unsigned long long frontier_word_counts(const FrontierView &X,
 __global__ __launch_bounds__(FRONTIER_THREADS) void frontier_sums_kernel(FrontierView X) {
     __shared__ unsigned long long s_wave[FRONTIER_THREADS / 64];
     unsigned long long total;
-    (void)block_exclusive_scan(frontier_word_counts(X, (long long)blockIdx.x * FRONTIER_THREADS + threadIdx.x), s_wave, total);
+    (void)block_exclusive_scan(frontier_word_counts(X, tile_element()), s_wave, total);
     if (threadIdx.x == 0) X.sums[blockIdx.x] = total;
 }
 // One workgroup.  sums[b] = the sums of the tiles in front of b; the totals into their control words.
 __global__ __launch_bounds__(FRONTIER_THREADS) void frontier_scan_sums_kernel(unsigned long long *__restrict__ sums, long long n_tiles, unsigned long long *__restrict__ ctl) {
     __shared__ unsigned long long s_wave[FRONTIER_THREADS / 64];
-    unsigned long long run = 0;
-    for (long long base = 0; base < n_tiles; base += FRONTIER_THREADS) {
-        const long long b = base + threadIdx.x;
-        const unsigned long long mine = b < n_tiles ? sums[b] : 0ull;
-        unsigned long long total;
-        const unsigned long long before = block_exclusive_scan(mine, s_wave, total);
-        if (b < n_tiles) sums[b] = run + before;
-        run += total;
-    }
+    const unsigned long long run = scan_tile_sums(sums, n_tiles, s_wave);
     if (threadIdx.x == 0) {
         ctl[FC_KEPT_CLUSTERS] = run >> 32;
         ctl[FC_KEPT_VOXELS] = run & 0xffffffffull;
@@ -361,14 +353,10 @@ __global__ __launch_bounds__(FRONTIER_THREADS) void frontier_scan_sums_kernel(un
 }
 __global__ __launch_bounds__(FRONTIER_THREADS) void frontier_prefix_kernel(FrontierView X) {
     __shared__ unsigned long long s_wave[FRONTIER_THREADS / 64];
-    const long long i = (long long)blockIdx.x * FRONTIER_THREADS + threadIdx.x;
+    const long long i = tile_element();
     unsigned long long total;
     const unsigned long long before = block_exclusive_scan(frontier_word_counts(X, i), s_wave, total);
     if (i < X.words) X.prefix[i] = X.sums[blockIdx.x] + before;
-}
-
-__global__ void frontier_report_kernel(const unsigned long long *__restrict__ ctl, long long *__restrict__ host) {
-    if (threadIdx.x < FRONTIER_HOST_WORDS) host[threadIdx.x] = (long long)ctl[threadIdx.x];
 }
 
 // ---- behind the wait ---------------------------------------------------------------------------------------------------------------------
@@ -401,7 +389,7 @@ __global__ __launch_bounds__(FRONTIER_THREADS) void frontier_write_kernel(Fronti
 
 // acc: FRONTIER_TABLE_WORDS per kept cluster
 __global__ __launch_bounds__(FRONTIER_THREADS) void frontier_table_init_kernel(long long *__restrict__ acc, long long rows) {
-    const long long i = (long long)blockIdx.x * FRONTIER_THREADS + threadIdx.x;
+    const long long i = tile_element();
     if (i >= rows * FRONTIER_TABLE_WORDS) return;
     const int k = (int)(i % FRONTIER_TABLE_WORDS);
     acc[i] = k >= FT_MIN && k < FT_MAX ? 0x7fffffffffffffffll : (k >= FT_MAX && k < FT_FACES ? -1ll : 0ll);
@@ -491,7 +479,7 @@ __global__ __launch_bounds__(FRONTIER_THREADS) void frontier_table_kernel(Fronti
 }
 
 __global__ __launch_bounds__(FRONTIER_THREADS) void frontier_table_rows_kernel(const long long *__restrict__ acc, long long *__restrict__ host, long long words) {
-    const long long i = (long long)blockIdx.x * FRONTIER_THREADS + threadIdx.x;
+    const long long i = tile_element();
     if (i < words) host[i] = acc[i];
 }
 

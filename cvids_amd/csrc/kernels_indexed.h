@@ -1,7 +1,7 @@
 // kernels_indexed.h -- chisel_hip_indexed_mesh: the coarse mesh's triangles (kernels_coarse.h) over ONE vertex per crossed lattice edge
 // (the host side: host_indexed.h; the request checks, the extras and the size arithmetic: indexed_checks.h; the definition:
-// DESIGN.md 3.15).  Built from the coarse mesh's pieces: CoarseLattice, coarse_walk_strided, coarse_walk_batched, block_exclusive_scan
-// and scan_chunks are used as they are, and shade_vertices_kernel runs on the vertices unchanged.  What this file adds is what a walk's
+// DESIGN.md 3.15).  Built from the coarse mesh's pieces: CoarseLattice, coarse_walk_strided, coarse_walk_batched and scan_chunks are used
+// as they are (the workgroup scan: kernels_workgroup.h), and shade_vertices_kernel runs on the vertices unchanged.  What this file adds is what a walk's
 // callable does with a cube, the owners (indexed_owners) and the rows.
 //
 // A lattice point l = (li, lj, lk) in [0, M)^3 of an OWNER chunk owns the three edges l -> l + e_a.  An owner keeps R = 3 M^2 ROWS, row
@@ -22,6 +22,7 @@
 //                            triangle in MeshCube's push order (t + 2, t + 1, t), looked up through masks and prefixes
 #pragma once
 #include "kernels_coarse.h"
+#include "kernels_workgroup.h"
 #include "indexed_checks.h"
 
 namespace chisel_hip {

@@ -2,9 +2,10 @@
 // kernels (kernels_deintegrate.h), which rewrite voxels outside the integration path, have in common.  One workgroup of T = 256 (512
 // in the batched apply kernel from 16^3 on) per listed chunk at a time; a lane owns 4 consecutive x voxels (the map's lane layout:
 // 16-byte accesses), quads q = thread, thread + T, ...; thread 0 ends with the chunk's note (chisel_device.h: note_slot_updated; for
-// de-integration inside deintegrate_chunk_end).  And report_words_kernel, the way of a few words to the host.
+// de-integration inside deintegrate_chunk_end).  The way of their few words to the host is report_words_kernel (kernels_workgroup.h).
 #pragma once
 #include "chisel_device.h"
+#include "kernels_workgroup.h"
 
 namespace chisel_hip {
 
@@ -67,12 +68,6 @@ __device__ inline void tally_count(unsigned n, unsigned *s_word) {
 __device__ inline void tally_signs(bool pos, bool neg, unsigned *s_signs) {
     const unsigned signs = (__any(pos) ? SUM_POS : 0u) | (__any(neg) ? SUM_NEG : 0u);
     if ((threadIdx.x & 63) == 0 && signs) atomicOr(s_signs, signs);
-}
-
-// n words of device memory into pinned memory (one thread): what the host reads after its wait
-template <class T>
-__global__ void report_words_kernel(const T *src, T *dst, int n) {
-    for (int i = 0; i < n; i++) dst[i] = src[i];
 }
 
 }  // namespace chisel_hip

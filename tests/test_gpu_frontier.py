@@ -144,6 +144,39 @@ def test_window_placements():
     far.close()
 
 
+def test_a_window_of_more_than_256_scan_tiles():
+    """dims (2048, 64, 33): 32 words a row x 2112 rows = 67 584 words in 264 scan tiles of 256 words, so the one workgroup that scans
+    the tile sums goes round twice and carries its running 64-bit sum (kept clusters | kept voxels) into the second round.  A nearly
+    empty map with two small patches of free voxels in unknown space: one whose frontier lies in the first rows of the window, one in
+    the plane z = 32, whose first word is word 65 536, the first of tile 256 -- a lost carry numbers the second patch's clusters from
+    0 again and puts their voxels at the head of the list"""
+    N = 8
+    origin, dims = (-1000, 5, -11), (2048, 64, 33)
+    bars = np.zeros((3, 7, 12), np.uint8)
+    bars[1, 1:6:2, 1:11] = fr.FREE  # three bars along x, a row of unknown voxels between them: three clusters at every connectivity
+    plane = np.zeros((1, 9, 140), np.uint8)
+    plane[0, 1:8:2, 1:139] = fr.FREE  # four bars of 138 voxels over three or four words of a row
+    fields = fr.fields_from_states(bars, N, (origin[0] + 70, origin[1] + 2, origin[2]))
+    far = fr.fields_from_states(plane, N, (origin[0] + 950, origin[1] + 50, origin[2] + 32))
+    assert not set(fields) & set(far)
+    fields.update(far)
+    gm = new_map(N)
+    upload(gm, fields)
+    words = (dims[0] // 64) * dims[1] * dims[2]
+    assert words == 67584 and -(-words // 256) == 264
+    wide = fr.wide_states(fields, N, origin, dims)
+    for connectivity, min_voxels in ((26, 1), (6, 11)):
+        got, want = check_window(gm, None, N, origin, dims, 1, connectivity, min_voxels, wide=wide, what="264 scan tiles")
+        t = got["totals"]
+        kept = 7 if min_voxels == 1 else 4  # (a bar of the first patch has 10 voxels)
+        assert t["clusters"] == 7 and t["kept_clusters"] == kept and t["kept_voxels"] == (30 if min_voxels == 1 else 0) + 4 * 138, t
+        rows = got["table"]
+        first_word = (rows[:, 7] * dims[1] + rows[:, 6]) * (dims[0] // 64) + rows[:, 5] // 64  # of the cluster's first voxel: min z, min y, min x
+        assert (first_word >= 256 * 256).sum() == 4 and (first_word < 256 * 256).sum() == kept - 4  # behind and in front of the first round
+        assert np.array_equal(got["voxels"][-4 * 138:, 2], np.full(4 * 138, 32)) and set(got["voxels"][-4 * 138:, 3].tolist()) == set(range(kept - 4, kept))
+    gm.close()
+
+
 # ---- 3. the hand volumes ------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("N,absent", [(8, True), (8, False), (16, True)])
 def test_hand_volumes(N, absent):

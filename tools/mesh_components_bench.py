@@ -41,7 +41,7 @@ MIN_TRIANGLES = 64
 KERNELS = (("components_init_kernel", None, 1, 1), ("components_hook_kernel", None, 1, 1), ("components_label_vertices_kernel", None, 1, 1),
            ("components_label_triangles_kernel", None, 1, 1), ("components_sums_kernel", 0, 1, 1), ("components_sums_kernel", 1, 0, 1),
            ("components_sums_kernel", 2, 0, 1), ("components_scan_sums_kernel", None, 1, 3), ("components_prefix_kernel", 0, 1, 1),
-           ("components_prefix_kernel", 1, 0, 1), ("components_prefix_kernel", 2, 0, 1), ("components_report_kernel", None, 1, 1),
+           ("components_prefix_kernel", 1, 0, 1), ("components_prefix_kernel", 2, 0, 1), ("report_words_kernel", None, 1, 1),
            ("components_write_vertices_kernel", None, 1, 0), ("components_write_triangles_kernel", None, 1, 0),
            ("components_write_table_kernel", None, 1, 0), ("filter_vertices_kernel", None, 0, 1), ("filter_triangles_kernel", None, 0, 1))
 

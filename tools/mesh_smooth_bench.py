@@ -46,7 +46,7 @@ MIN_TRIANGLES = 64
 ITERATIONS, LAM, MU, PIN = 10, 0.5, -0.53, 3
 ENTRIES = ("adjacency", "normals", "smooth")
 KERNELS = ("adjacency_count_kernel", "adjacency_sums_kernel", "adjacency_scan_sums_kernel", "adjacency_prefix_kernel", "adjacency_fill_kernel",
-           "adjacency_rows_kernel", "adjacency_report_kernel", "adjacency_compact_kernel", "mesh_vertex_normals_kernel", "mesh_smooth_pass_kernel")
+           "adjacency_rows_kernel", "report_words_kernel", "adjacency_compact_kernel", "mesh_vertex_normals_kernel", "mesh_smooth_pass_kernel")
 
 
 def stats(us):
