@@ -123,6 +123,28 @@ FRONTIER_MAX_VOXELS = 1 << 26  # chisel_hip_frontiers' largest window, voxels
 FRONTIER_TABLE_COLUMNS = ("root", "voxels", "sum_x", "sum_y", "sum_z", "min_x", "min_y", "min_z", "max_x", "max_y", "max_z", "unknown_faces")
 
 
+class TravelWindow(C.Structure):
+    """chisel_hip_travel_window (include/chisel_hip.h): the window and the request of chisel_hip_travel_field, 56 bytes"""
+    _fields_ = [("origin", C.c_int * 3), ("dims", C.c_int * 3), ("connectivity", C.c_int), ("step_cost", C.c_int * 3), ("max_cost", C.c_int),
+                ("clearance", C.c_int), ("unknown_is_obstacle", C.c_int), ("surface_offset", C.c_float)]
+
+
+TRAVEL_TOTALS = ("unknown", "free", "occupied", "traversable", "seeds_used", "seeds_ignored", "reached", "largest_cost", "targets_reached",
+                 "targets_ignored", "rounds", "tile_visits")  # the last two: diagnostics of the implementation
+
+
+class TravelTotals(C.Structure):
+    """chisel_hip_travel_totals (include/chisel_hip.h): what chisel_hip_travel_field found, 96 bytes"""
+    _fields_ = [(n, C.c_int64) for n in TRAVEL_TOTALS]
+
+
+assert C.sizeof(TravelWindow) == 56 and C.sizeof(TravelTotals) == 96
+TRAVEL_TABLE_COLUMNS = ("rows", "reached", "least_cost", "least_index")
+TRAVEL_ROUNDS_PER_WAIT = 16  # travel_checks.h: round launches between two looks at the flagged tiles
+TRAVEL_MAX_SEEDS = 1 << 20
+TRAVEL_MAX_COST = 1 << 30
+
+
 class MeshRequest(C.Structure):
     """chisel_hip_mesh_request (include/chisel_hip.h): the selection and the marker colours of chisel_hip_gather_meshes, 56 bytes"""
     _fields_ = [("ids_xyz", C.POINTER(C.c_int)), ("n_ids", C.c_int64), ("marker_colors", C.c_int), ("light0", C.c_float * 3),
@@ -214,7 +236,7 @@ EXPORTS = [
     "chisel_hip_gather_chunks", "chisel_hip_scatter_chunks", "chisel_hip_coarse_mesh", "chisel_hip_indexed_mesh",
     "chisel_hip_mesh_components", "chisel_hip_filter_mesh",
     "chisel_hip_mesh_adjacency", "chisel_hip_mesh_vertex_normals", "chisel_hip_smooth_mesh",
-    "chisel_hip_frontiers",
+    "chisel_hip_frontiers", "chisel_hip_travel_field", "chisel_hip_travel_path",
 ]
 # the device self-tests and debug read-outs include/chisel_hip_selftest.h declares
 SELFTEST_EXPORTS = [
@@ -372,6 +394,9 @@ def load_library():
                         ("chisel_hip_deintegrate_batch", [vp, C.c_int, C.POINTER(DepthFrame), C.c_int, C.POINTER(DeintegrateStats), i32p, C.c_int]),
                         ("chisel_hip_distance_field", [vp, C.POINTER(DistanceWindow), vp, vp, vp, C.c_int]),
                         ("chisel_hip_frontiers", [vp, C.POINTER(FrontierWindow), vp, vp, C.c_int64, vp, C.c_int64, i64p, C.c_int, C.POINTER(FrontierTotals)]),
+                        ("chisel_hip_travel_field", [vp, C.POINTER(TravelWindow), i32p, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, i64p, C.c_int,
+                                                     C.POINTER(TravelTotals)]),
+                        ("chisel_hip_travel_path", [vp, i32p, i32p, C.c_int64, i32p, i64p]),
                         ("chisel_hip_gather_meshes", [vp, C.POINTER(MeshRequest), C.c_int64, C.c_int64, vp, vp, vp, vp, vp, C.c_int, i64p, i32p,
                                                       C.POINTER(MeshTotals)]),
                         ("chisel_hip_gather_meshes_size", [vp, C.POINTER(MeshRequest), C.POINTER(MeshTotals)]),

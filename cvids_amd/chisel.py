@@ -719,6 +719,89 @@ class Chisel:
         res.update(table=table, centres=self.FrontierCentres(origin, table), totals=totals)
         return res
 
+    def TravelField(self, origin, dims, seeds, connectivity=26, step_cost=(10, 14, 17), max_cost=1 << 30, clearance=0, unknown_is_obstacle=False,
+                    surface_offset=0.0, cost=True, step=True, state=False, targets=None, n_groups=0, out=None):
+        """chisel_hip_travel_field: over the window of dims = (nx, ny, nz) voxels whose first voxel has the global index
+        `origin`, the least travel cost from the `seeds` ((n, 3) window-relative x, y, z) to every TRAVERSABLE voxel -- free, and with
+        clearance r >= 1 no obstacle of the map within r voxels (DistanceField's dist2 == -1 at radius r) -- over the moves of
+        `connectivity` 6, 18 or 26, a move with k non-zero coordinates costing step_cost[k - 1], up to max_cost.
+        -> {"cost": int32 (nz, ny, nx), -1 unreached; "step": uint8, 13 at a seed, 255 unreached, else the smallest code
+        (dz + 1) 9 + (dy + 1) 3 + (dx + 1) of a move that leads back towards a seed; "state": uint8, DistanceField's; None for what was
+        not asked for; "table": int64 (n_groups, 4) -- capi.TRAVEL_TABLE_COLUMNS: rows, reached rows, least cost, the smallest linear
+        index with it, -1 without a reached row -- when `targets` ((n, 4) int32 x, y, z, group: the "voxels" of Frontiers; a numpy
+        array or a torch CUDA tensor) are given, else None; "totals": capi.TRAVEL_TOTALS, "rounds" and "tile_visits" diagnostics}.
+        `out`: a dict of contiguous torch CUDA tensors "cost", "step", "state" of that shape: exactly those are filled in place on the
+        map's stream; it is returned with "table" and "totals" (host) added; numpy targets are uploaded first.  The map is only read."""
+        w = capi.TravelWindow()
+        w.origin[:] = [int(v) for v in origin]
+        w.dims[:] = [int(v) for v in dims]
+        w.step_cost[:] = [int(v) for v in step_cost]
+        w.connectivity, w.max_cost, w.clearance = int(connectivity), int(max_cost), int(clearance)
+        w.unknown_is_obstacle, w.surface_offset = int(bool(unknown_is_obstacle)), float(surface_offset)
+        seeds = np.ascontiguousarray(np.asarray(seeds, np.int32).reshape(-1, 3))
+        shape = (int(dims[2]), int(dims[1]), int(dims[0]))
+        on_device = out is not None
+        is_tensor = targets is not None and not isinstance(targets, np.ndarray) and hasattr(targets, "data_ptr")
+        if is_tensor:
+            self._device_rows(targets, "targets", "int32", 4, 0)
+            n_targets = int(targets.shape[0])
+            if not on_device:
+                targets = targets.cpu().numpy()
+                is_tensor = False
+        if targets is not None and not is_tensor:
+            targets = np.ascontiguousarray(np.asarray(targets, np.int32).reshape(-1, 4))
+            n_targets = int(targets.shape[0])
+            if on_device:
+                import torch
+                targets = torch.from_numpy(targets).cuda()
+                is_tensor = True
+        if targets is None:
+            n_targets = 0
+        target_ptr = None
+        if n_targets:
+            target_ptr = targets.data_ptr() if is_tensor else targets.ctypes.data
+        table = np.zeros((int(n_groups), 4), np.int64) if n_targets else None
+        if on_device:
+            import torch
+            unknown = set(out) - {"cost", "step", "state"}
+            assert not unknown, "out: unknown outputs %s" % sorted(unknown)
+            ptrs = []
+            for name, want in (("cost", torch.int32), ("step", torch.uint8), ("state", torch.uint8)):
+                t = out.get(name)
+                assert t is None or (t.is_cuda and t.dtype == want and t.is_contiguous() and tuple(t.shape) == shape), \
+                    "out[%r]: a contiguous %s CUDA tensor of shape %s" % (name, want, shape)
+                ptrs.append(t.data_ptr() if t is not None else None)
+            self._keep = [out, targets]
+            res = dict(out)
+        else:
+            res = {"cost": np.empty(shape, np.int32) if cost else None, "step": np.empty(shape, np.uint8) if step else None,
+                   "state": np.empty(shape, np.uint8) if state else None}
+            ptrs = [res[k].ctypes.data if res[k] is not None and res[k].size else None for k in ("cost", "step", "state")]
+        totals = capi.TravelTotals()
+        check(self.L.chisel_hip_travel_field(self.h, C.byref(w), seeds.ctypes.data_as(C.POINTER(C.c_int32)) if seeds.size else None, int(seeds.shape[0]),
+                                             target_ptr, n_targets, int(n_groups), ptrs[0], ptrs[1], ptrs[2], self._table_ptr(table, C.c_int64),
+                                             int(on_device), C.byref(totals)))
+        res.update(table=table, totals=self._totals_dict(totals))
+        return res
+
+    def TravelPath(self, step, start):
+        """chisel_hip_travel_path: the walk along the steps of TravelField (a numpy array or a torch tensor (nz, ny, nx) uint8) from
+        the voxel `start` (x, y, z window-relative) to its seed -> (n, 3) int32 rows (x, y, z), both ends included"""
+        if not isinstance(step, np.ndarray) and hasattr(step, "cpu"):
+            step = step.cpu().numpy()
+        step = np.ascontiguousarray(step, np.uint8)
+        assert step.ndim == 3, "step: (nz, ny, nx)"
+        dims = (C.c_int32 * 3)(step.shape[2], step.shape[1], step.shape[0])
+        start = (C.c_int32 * 3)(*[int(v) for v in start])
+        length = C.c_int64(0)
+        path = np.empty((1, 3), np.int32)
+        rc = self.L.chisel_hip_travel_path(step.ctypes.data, dims, start, 1, path.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(length))
+        if rc and length.value > 1:  # (the capacity was short: the length is known now)
+            path = np.empty((length.value, 3), np.int32)
+            rc = self.L.chisel_hip_travel_path(step.ctypes.data, dims, start, length.value, path.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(length))
+        check(rc)
+        return path[:length.value]
+
     _GATHER_OUTPUTS = (("vertices", 3), ("normals", 3), ("colors", 3), ("rgba", 4), ("grids", 3))
     # ChiselServer's marker lights (chisel_ros/src/ChiselServer.cpp:652-655, :657-658): lightDir normalised twice, lightDir1 as it stands
     MARKER_LIGHTS = {"light0": marker_light_dir(), "light1": (-0.5, 0.2, 0.2), "diffuse": 0.5, "ambient": 0.2}

@@ -58,6 +58,8 @@
 #include "kernels_adjacency.h"
 #include "frontier_checks.h"
 #include "kernels_frontier.h"
+#include "travel_checks.h"
+#include "kernels_travel.h"
 #include "kernels_filter.h"
 #include "kernels_stereo.h"
 #include "kernels_stereo_prep.h"
@@ -493,6 +495,14 @@ struct chisel_hip_map {
         DeviceBuffer<long long> acc;                                   // [12 kept clusters] the table's accumulator
         PinnedWords table_host;                                        // [12 kept clusters] the table's rows
     } frontier_mem;
+    struct TravelMemory {                                              // chisel_hip_travel_field (host_travel.h), allocated on first use, grown on demand
+        DeviceBuffer<unsigned long long> planes;                       // [TravelPlan::plane_words] free and unknown over the widened window | traversable over the window
+        DeviceBuffer<int> ints;                                        // [TravelPlan::ints] cost | dist2 with a clearance | the tiles' flags of this round and the next
+        DeviceBuffer<int> seeds;                                       // [3 n_seeds] the seeds of the call
+        ControlWords ctl;                                              // [TRAVEL_HOST_WORDS] the control words (TC_*)
+        DeviceBuffer<long long> acc;                                   // [4 n_groups] the group table's accumulator
+        PinnedWords table_host;                                        // [4 n_groups] the group table's rows
+    } travel_mem;
 };
 
 namespace {
@@ -3061,4 +3071,5 @@ int chisel_hip_frustum_from_vectors(const float forward[3], const float pos[3], 
 #include "host_components.h"
 #include "host_adjacency.h"
 #include "host_frontier.h"
+#include "host_travel.h"
 #include "host_selftest.h"

@@ -28,6 +28,43 @@ int ensure_distance_scratch(chisel_hip_map *m, const DistancePlan &plan, bool pa
     return CHISEL_HIP_OK;
 }
 
+// The seed and, where dist2 or distance is asked for, the three passes of a call, queued on the map's stream into device memory
+// (chisel_hip_travel_field launches them too, as they are, with a dist2 of its own call's scratch).  ensure_distance_scratch first.
+void launch_distance_passes(chisel_hip_map *m, const chisel_hip_distance_window *window, const DistancePlan &plan, uint8_t *dstate, int32_t *dd2, float *ddist) {
+    const bool passes = dd2 || ddist;
+    chisel_hip_map::DistanceMemory &O = m->distance_mem;
+    const int R = window->radius, nx = window->dims[0], ny = window->dims[1], nz = window->dims[2];
+    DistanceSeedArgs A;
+    for (int a = 0; a < 3; a++) {
+        A.wo[a] = plan.wo[a];
+        A.wd[a] = plan.wd[a];
+        A.dims[a] = window->dims[a];
+    }
+    A.R = R;
+    A.unknown_is_obstacle = window->unknown_is_obstacle != 0;
+    A.surface_offset = window->surface_offset;
+    A.words_per_row = plan.words_per_row;
+    const long long n_runs = plan.bits_words;  // (<= 2^30: a run holds a voxel of the widened window)
+    FOR_CHUNK_SIZE(m->N, hipLaunchKernelGGL(distance_seed_kernel<N>, dim3((unsigned)((n_runs + 3) / 4)), dim3(256), 0, m->stream, m->view, A, n_runs, dstate,
+                                            O.bits.get()));
+    if (passes) {
+        const long long n1 = plan.g1_elems;  // along x: every row of the widened y and z
+        hipLaunchKernelGGL(distance_x_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, m->stream, O.bits.get(), (long long)plan.words_per_row, nx, n1, R,
+                           O.g1.get());
+        const size_t lds = (size_t)(DIST_TILE + 2 * R) * 64 * sizeof(unsigned short);
+        {  // along y: every plane of the widened z
+            const long long X = nx, bx = (X + 63) / 64, ba = (ny + DIST_TILE - 1) / DIST_TILE;
+            hipLaunchKernelGGL(distance_axis_kernel<false>, dim3((unsigned)(bx * ba * plan.wd[2])), dim3(256), lds, m->stream, O.g1.get(), O.g2.get(),
+                               (int *)nullptr, (float *)nullptr, (const float *)nullptr, X, ny, bx, ba, R);
+        }
+        {  // along z: the planes of the window are one contiguous dimension
+            const long long X = (long long)nx * ny, bx = (X + 63) / 64, ba = (nz + DIST_TILE - 1) / DIST_TILE;
+            hipLaunchKernelGGL(distance_axis_kernel<true>, dim3((unsigned)(bx * ba)), dim3(256), lds, m->stream, O.g2.get(), (unsigned short *)nullptr, dd2, ddist,
+                               O.table.get(), X, nz, bx, ba, R);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -68,37 +105,7 @@ int chisel_hip_distance_field(chisel_hip_map *m, const chisel_hip_distance_windo
         int rc_w = wait_for_input(m, m->stream);  // chisel_hip_wait_event / _order_map_after_stream: the outputs may be written behind it
         if (rc_w) return rc_w;
     }
-    chisel_hip_map::DistanceMemory &O = m->distance_mem;
-    const int R = window->radius, nx = window->dims[0], ny = window->dims[1], nz = window->dims[2];
-    DistanceSeedArgs A;
-    for (int a = 0; a < 3; a++) {
-        A.wo[a] = plan.wo[a];
-        A.wd[a] = plan.wd[a];
-        A.dims[a] = window->dims[a];
-    }
-    A.R = R;
-    A.unknown_is_obstacle = window->unknown_is_obstacle != 0;
-    A.surface_offset = window->surface_offset;
-    A.words_per_row = plan.words_per_row;
-    const long long n_runs = plan.bits_words;  // (<= 2^30: a run holds a voxel of the widened window)
-    FOR_CHUNK_SIZE(m->N, hipLaunchKernelGGL(distance_seed_kernel<N>, dim3((unsigned)((n_runs + 3) / 4)), dim3(256), 0, m->stream, m->view, A, n_runs, dstate,
-                                            O.bits.get()));
-    if (passes) {
-        const long long n1 = plan.g1_elems;  // along x: every row of the widened y and z
-        hipLaunchKernelGGL(distance_x_kernel, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, m->stream, O.bits.get(), (long long)plan.words_per_row, nx, n1, R,
-                           O.g1.get());
-        const size_t lds = (size_t)(DIST_TILE + 2 * R) * 64 * sizeof(unsigned short);
-        {  // along y: every plane of the widened z
-            const long long X = nx, bx = (X + 63) / 64, ba = (ny + DIST_TILE - 1) / DIST_TILE;
-            hipLaunchKernelGGL(distance_axis_kernel<false>, dim3((unsigned)(bx * ba * plan.wd[2])), dim3(256), lds, m->stream, O.g1.get(), O.g2.get(),
-                               (int *)nullptr, (float *)nullptr, (const float *)nullptr, X, ny, bx, ba, R);
-        }
-        {  // along z: the planes of the window are one contiguous dimension
-            const long long X = (long long)nx * ny, bx = (X + 63) / 64, ba = (nz + DIST_TILE - 1) / DIST_TILE;
-            hipLaunchKernelGGL(distance_axis_kernel<true>, dim3((unsigned)(bx * ba)), dim3(256), lds, m->stream, O.g2.get(), (unsigned short *)nullptr, dd2, ddist,
-                               O.table.get(), X, nz, bx, ba, R);
-        }
-    }
+    launch_distance_passes(m, window, plan, dstate, dd2, ddist);
     const hipError_t e = st.finish(hipGetLastError());
     if (e != hipSuccess) return fail(CHISEL_HIP_ERR_HIP, std::string("chisel_hip_distance_field: ") + hipGetErrorString(e));
     return CHISEL_HIP_OK;

@@ -1297,6 +1297,56 @@ class Chisel {  // Chisel.h:38-230
         if (table) table->swap(rows);
         return totals;
     }
+    // Not in the reference: the travel cost over free space from seed voxels (chisel_hip_travel_field).  Over the window
+    // of DistanceField, the least sum of move costs (stepCost: face, edge, corner) from the seeds (3 ints a row, window-relative
+    // x, y, z) to every traversable voxel -- free, and with clearance r >= 1 no obstacle of the map within r voxels -- under
+    // `connectivity` 6, 18 or 26, up to maxCost.  A null vector is not asked for; the others are resized: cost (-1 unreached), step
+    // (13 a seed, 255 unreached, else the code (dz + 1) 9 + (dy + 1) 3 + (dx + 1) of the move back towards a seed) and state per voxel;
+    // table: 4 int64 per group (rows, reached rows, least cost, the smallest linear index with it) when targets (4 ints a row:
+    // x, y, z, group -- the voxels of Frontiers) are given.  The map is only read.  -> the totals
+    chisel_hip_travel_totals TravelField(const Eigen::Vector3i &origin, const Eigen::Vector3i &dims, const std::vector<int32_t> &seeds, int connectivity,
+                                         const Eigen::Vector3i &stepCost, int maxCost, int clearance, bool unknownIsObstacle, float surfaceOffset,
+                                         std::vector<int32_t> *cost, std::vector<uint8_t> *step, std::vector<uint8_t> *state = nullptr,
+                                         const std::vector<int32_t> *targets = nullptr, int64_t nGroups = 0, std::vector<int64_t> *table = nullptr) const {
+        chisel_hip_travel_window w;
+        for (int a = 0; a < 3; a++) {
+            w.origin[a] = origin(a);
+            w.dims[a] = dims(a);
+            w.step_cost[a] = stepCost(a);
+        }
+        w.connectivity = connectivity;
+        w.max_cost = maxCost;
+        w.clearance = clearance;
+        w.unknown_is_obstacle = unknownIsObstacle ? 1 : 0;
+        w.surface_offset = surfaceOffset;
+        const size_t n = dims(0) > 0 && dims(1) > 0 && dims(2) > 0 ? (size_t)dims(0) * dims(1) * dims(2) : 0;
+        const int64_t nTargets = targets ? (int64_t)(targets->size() / 4) : 0;
+        const bool big = n > ((size_t)1 << 26);  // (refused below: nothing is resized for it)
+        if (cost && !big) cost->resize(n);
+        if (step && !big) step->resize(n);
+        if (state && !big) state->resize(n);
+        if (table) table->assign(nTargets > 0 && nGroups > 0 ? (size_t)nGroups * 4 : 0, 0);
+        chisel_hip_travel_totals totals;
+        hip_check(chisel_hip_travel_field(map, &w, seeds.data(), (int64_t)(seeds.size() / 3), nTargets ? targets->data() : nullptr, nTargets, nGroups,
+                                          cost && !big ? cost->data() : nullptr, step && !big ? step->data() : nullptr, state && !big ? state->data() : nullptr,
+                                          table && !table->empty() ? table->data() : nullptr, 0, &totals));
+        return totals;
+    }
+    // The walk along the steps of TravelField from `start` (window-relative) to its seed: 3 ints a row, both ends included
+    // (chisel_hip_travel_path; needs no device)
+    static std::vector<int32_t> TravelPath(const std::vector<uint8_t> &step, const Eigen::Vector3i &dims, const Eigen::Vector3i &start) {
+        const int d[3] = {dims(0), dims(1), dims(2)}, from[3] = {start(0), start(1), start(2)};
+        std::vector<int32_t> path(3);
+        int64_t length = 0;
+        int rc = chisel_hip_travel_path(step.data(), d, from, 1, path.data(), &length);
+        if (rc != CHISEL_HIP_OK && length > 1) {  // (the capacity was short: the length is known now)
+            path.resize((size_t)length * 3);
+            rc = chisel_hip_travel_path(step.data(), d, from, length, path.data(), &length);
+        }
+        hip_check(rc);
+        path.resize((size_t)length * 3);
+        return path;
+    }
     chisel_hip_map *HipMap() const { return map; }
 
   protected:

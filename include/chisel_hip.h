@@ -50,7 +50,8 @@ extern "C" {
  *      chisel_hip_distance_field, chisel_hip_gather_meshes,
  *      chisel_hip_gather_meshes_size, chisel_hip_save_ply_binary, chisel_hip_gather_chunks, chisel_hip_scatter_chunks, chisel_hip_coarse_mesh,
  *      chisel_hip_indexed_mesh, chisel_hip_mesh_components, chisel_hip_filter_mesh, chisel_hip_mesh_adjacency,
- *      chisel_hip_mesh_vertex_normals, chisel_hip_smooth_mesh, chisel_hip_frontiers (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
+ *      chisel_hip_mesh_vertex_normals, chisel_hip_smooth_mesh, chisel_hip_frontiers, chisel_hip_travel_field,
+ *      chisel_hip_travel_path (no slot in the hipEvent profiler: CHISEL_HIP_NUM_KERNELS stays) */
 #define CHISEL_HIP_ABI_VERSION 3
 
 typedef struct chisel_hip_map chisel_hip_map; /* opaque: one TSDF map (or one shard of it) on one GPU */
@@ -942,6 +943,71 @@ typedef struct { int64_t unknown, free, occupied, frontier, clusters, largest_vo
 int chisel_hip_frontiers(chisel_hip_map *map, const chisel_hip_frontier_window *window, uint8_t *state, int32_t *label,
                          int64_t capacity_voxels, int32_t *voxels, int64_t capacity_clusters, int64_t *cluster_table, int on_device,
                          chisel_hip_frontier_totals *totals);
+/* ---- travel cost over free space from seed voxels (DESIGN.md 3.19 "Travel field") ----
+ * Not in the reference: can the robot get there, and how far is the way -- a planner's third question after the distance to the nearest
+ * obstacle and the frontiers.  The window is chisel_hip_distance_window's: origin and dims = (nx, ny, nz); every per-voxel array is
+ * [z][y][x], element (x, y, z) at the LINEAR INDEX (z ny + y) nx + x.  The STATE of a voxel (0 unknown, 1 free, 2 occupied) is
+ * chisel_hip_distance_field's, bit for bit: one fp32 compare sdf < surface_offset.  A voxel of the window is TRAVERSABLE when it is free
+ * and, with clearance r >= 1, no obstacle voxel o of the MAP has |v - o|^2 <= r^2: exactly chisel_hip_distance_field at radius r
+ * reading dist2 == -1, with the same unknown_is_obstacle rule, read beyond the window's rim.  With clearance 0 only the voxel's own
+ * state counts and no distance transform is run.  Voxels outside the window are not traversable.  The MOVES are the offsets of
+ * connectivity 6, 18 or 26 as the frontiers define them; a move with k non-zero coordinates costs step_cost[k - 1] (face, edge,
+ * corner; each 1 ... 65535, all three checked at every connectivity) and needs only its two end voxels traversable: nothing is checked
+ * about cut corners, the clearance is the caller's tool for that.  The SEEDS are n_seeds (1 ... 2^20) rows of window-relative
+ * (x, y, z) int32, HOST memory always; a seed on a voxel that is not traversable is ignored and counted, duplicates are harmless.
+ * COST(v) is the least sum of move costs over paths of traversable voxels from any used seed to v provided the sum is <= max_cost
+ * (0 ... 2^30), else -1; a seed has cost 0; no candidate exceeds 2^30 + 65535.  STEP(v) is 13 at a seed (cost 0), 255 at an unreached
+ * voxel, otherwise the smallest code (dz + 1) 9 + (dy + 1) 3 + (dx + 1) among the moves o of the connectivity with
+ * cost(v + o) + cost_of(o) == cost(v): computed from the converged costs alone; following steps strictly lowers the cost and ends at a
+ * seed.  TARGETS (optional) are n_targets rows of int32 (x, y, z, group) -- exactly the `voxels` list chisel_hip_frontiers writes --
+ * with n_groups >= 1; a row with a coordinate outside the window or a group outside 0 ... n_groups - 1 is ignored and counted. */
+typedef struct {
+    int origin[3];
+    int dims[3];
+    int connectivity;          /* 6, 18 or 26 */
+    int step_cost[3];          /* face, edge, corner: 1 ... 65535 each */
+    int max_cost;              /* 0 ... 2^30 */
+    int clearance;             /* 0 ... 64 voxels */
+    int unknown_is_obstacle;   /* for the clearance: unknown voxels are obstacles too */
+    float surface_offset;      /* metres: a voxel is occupied when it is observed with sdf < surface_offset */
+} chisel_hip_travel_window;     /* 56 bytes */
+typedef struct {
+    int64_t unknown, free, occupied, traversable;   /* voxels of the window */
+    int64_t seeds_used, seeds_ignored;
+    int64_t reached, largest_cost;                  /* voxels with a cost; the largest of them, -1 without one */
+    int64_t targets_reached, targets_ignored;
+    int64_t rounds, tile_visits;                    /* diagnostics of the implementation: round launches that found a flagged tile,
+                                                       tiles relaxed over all rounds.  Not part of the definition */
+} chisel_hip_travel_totals;     /* 96 bytes */
+/* Outputs, each optional:
+ *   cost (int32 per voxel), step (uint8 per voxel), state (uint8 per voxel)
+ *   group_table (4 int64 a row, n_groups rows, HOST memory whatever on_device says)   rows of the group, reached rows, the least
+ *                             cost over the reached rows (-1 without one), the smallest linear index among the rows with that cost
+ *                             (-1 without one)
+ *   totals (required, host)
+ * on_device says where cost, step, state and targets live.  Everything is queued on the map's stream behind what is queued.  The host
+ * waits once per TRAVEL_ROUNDS_PER_WAIT relaxation rounds and once for the totals, so every output is complete on return.  With no
+ * array and no table asked for the call is the size and reachability query: only totals is filled.  The map is only read; the scratch
+ * (two bits per voxel of the window widened by one, a bit and 4 bytes per voxel -- 8 with a clearance, beside the distance field's own
+ * scratch --, 8 bytes per tile of 16 x 16 x 8 voxels, 12 bytes per seed, 32 per group) is kept in the map, grown on demand and freed
+ * with it.  Integers throughout: the same call gives the same bytes.
+ * Refused with nothing written, in this order: CHISEL_HIP_ERR_UNSUPPORTED for a group, CHISEL_HIP_ERR_INVALID for a null map,
+ * CHISEL_HIP_ERR_UNSUPPORTED for one shard of several; then CHISEL_HIP_ERR_INVALID for a null window, null seeds, null totals, n_seeds
+ * outside 1 ... 2^20, a dimension < 1, a seed outside the window, a connectivity other than 6 / 18 / 26, a step_cost outside
+ * 1 ... 65535, max_cost outside 0 ... 2^30, clearance outside 0 ... 64, a NaN surface_offset, a negative count, more than 2^26 targets
+ * or groups, a target count without targets, targets without n_groups >= 1, a group table without targets, a coordinate of the window
+ * widened by max(clearance, 1) beyond +-2^30; then CHISEL_HIP_ERR_UNSUPPORTED for a window of more than 2^26 voxels, or with a
+ * clearance one that widened by it holds more than 2^30. */
+int chisel_hip_travel_field(chisel_hip_map *map, const chisel_hip_travel_window *window, const int32_t *seeds, int64_t n_seeds,
+                            const int32_t *targets, int64_t n_targets, int64_t n_groups, int32_t *cost, uint8_t *step, uint8_t *state,
+                            int64_t *group_table, int on_device, chisel_hip_travel_totals *totals);
+/* Needs no device (as chisel_hip_align_solve): walks the steps of a chisel_hip_travel_field result in HOST memory from the voxel `from`
+ * (window-relative x, y, z) to its seed and writes (x, y, z) rows, both ends included; *length is the number of rows.
+ * CHISEL_HIP_ERR_INVALID for a null argument, a negative capacity, a dimension < 1 or more than 2^26 voxels, a start outside the
+ * window, an unreached start (255), a code that is no move, a step that leaves the window, a walk longer than the window has voxels,
+ * a capacity below the length -- then *length is filled all the same (and the first `capacity` rows written), so that the caller can
+ * retry. */
+int chisel_hip_travel_path(const uint8_t *step, const int dims[3], const int from[3], int64_t capacity, int32_t *path, int64_t *length);
 /* Not in the reference: the normal equations of one Gauss-Newton step that aligns a depth frame to the map (point-to-surface against the
  * TSDF; DESIGN.md "Aligning a frame to the map" has the definition to the bit).  frame->pose is the guess, camera -> world.  Pixel i
  * with depth z is VALID when z is finite and near <= z <= far; its point p = o + z d lies on chisel_hip_render_view's ray of that pixel;
